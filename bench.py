@@ -14,7 +14,9 @@ the ranks frame by frame (rank r holds frames r, r+N, ...), 256 frames per rank 
 Contract: `python bench.py --gpus N --steps K --warmup W`, one rank per GPU; for N > 1 either launched by
 torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, from the plain command,
 by this file itself (self_launch: N child processes started before anything touches the GPU).  Rank 0 prints ONE
-JSON line.
+JSON line.  The plain command times the headline only; `--full` adds every other leg (per-stage timings and rooflines,
+other classifier modes, sizes and schedules, the CPU baseline); `--dump-outputs DIR` writes what the last timed step
+computed (dump_outputs).
 """
 import argparse
 import json
@@ -223,6 +225,45 @@ def close_all(things):
         raise first
 
 
+DUMP_BUDGET = 64 << 20      # bytes: what --dump-outputs may write in all
+
+
+def dump_outputs(dirname, records, counts, emitted, mtx, budget=DUMP_BUDGET):
+    """--dump-outputs: what the last timed step handed over, as DIR/<name>.npy in float32 / float64.
+    records: the batch's REC array in frame order (or pipeline.Gathered); counts: the background model's foreground counts
+    per frame (or None); emitted: the fold's per-frame request lists; mtx: the transform after the step (or None).
+    Per frame: board_result (status, n_contours, n_lines, flags, biggest_area), board_lines, region_label, region_conf,
+    fg_counts; frame_index says which frames of the batch they are -- all of them, or a fixed seeded sample when they would
+    not fit in `budget`.  requests: one row (frame, kind, colour 0/1/2 = E/B/W, row, column) per move of every request;
+    transform: 3 x 3 (NaN when there is none).  -> the names written"""
+    from camkifu_amd import pipeline
+    if hasattr(records, "in_frame_order"):
+        records = records.in_frame_order()
+    records = pipeline.records_view(records)
+    n = len(records)
+    fg = None if counts is None else np.asarray(pipeline.GpuCore._host(counts)).reshape(n, -1).astype(np.float32)
+    req = np.array([(f, kind, "EBW".index(str(col)), r, c) for f, per_frame in enumerate(emitted or ())
+                    for kind, moves in per_frame for col, r, c in moves], np.float64).reshape(-1, 5)
+    per_frame = (5 * 8 + records.dtype["lines"].shape[0] * 2 * 4 + 100 * 4 + 100 * 8 + 8
+                 + (0 if fg is None else fg.shape[1] * 4))
+    room = max(0, budget - req.nbytes - 9 * 8 - 1024)
+    idx = np.arange(n)
+    if n * per_frame > room:
+        idx = np.sort(np.random.default_rng(0).choice(n, room // per_frame, replace=False))
+    rec = records[idx]
+    out = dict(frame_index=idx.astype(np.float64),
+               board_result=np.stack([rec[k].astype(np.float64) for k in ("status", "n_contours", "n_lines", "flags", "biggest_area")], 1),
+               board_lines=rec["lines"].astype(np.float32), region_label=rec["region_label"].astype(np.float32),
+               region_conf=rec["region_conf"].astype(np.float64), requests=req,
+               transform=np.full((3, 3), np.nan) if mtx is None else np.asarray(mtx, np.float64).reshape(3, 3))
+    if fg is not None:
+        out["fg_counts"] = fg[idx]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
+
+
 def self_launch(n, argv, silent_limit=None):
     """`python bench.py --gpus N` from the plain command: start the N ranks here (one process per GPU, RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment -- what torch.distributed.run would set), relay rank 0's JSON line and
@@ -382,7 +423,16 @@ def main():
                                                            "a driver's record is sure to keep)" % LINE_BUDGET)
     ap.add_argument("--launch-check", default=None, metavar="ok|fail:R|hang:R",
                     help="test the N-rank launcher alone (gloo, no GPU): every rank joins a group and rank 0 prints one line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: per-stage timings and rooflines, the other classifier modes, "
+                         "hold-off-aware, single-frame, exchange, PCIe-inclusive and 4K legs, K1 content, the CPU baseline "
+                         "(--no-extras / --no-cpu-baseline leave parts of it out); off: the headline's timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0: per-frame records, foreground counts, requests, "
+                         "transform) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("CK_SWITCH_INTERVAL"):                   # (developer A/B knob: the interpreter's thread switch interval)
         sys.setswitchinterval(float(os.environ["CK_SWITCH_INTERVAL"]))
 
@@ -601,6 +651,8 @@ def main():
         quality["stone_grid_match_pct"] = round(100.0 * float((grid[calm[:64]] == truth[mine[:64]][calm[:64]]).mean()), 3)
 
     # ---- timed region: two batches in flight ------------------------------------------------------------------------
+    last = {}                           # the last step of the last run_steps: its ticket and the requests it emitted
+
     def run_steps(p, k, batch, nt):
         DEPTH = int(os.environ.get("CK_BENCH_DEPTH", "2"))      # batches in flight (developer knob; 3 measured no faster)
         tickets = [p.submit(batch, nt) for _ in range(min(DEPTH, k))]
@@ -609,7 +661,8 @@ def main():
             if i + DEPTH < k:
                 tickets.append(p.submit(batch, nt))
             p.stones = pipeline.StonesFold(ControllerHeadless())        # every step folds the same film from its start
-            p.finish(t)
+            last["emitted"] = p.finish(t)
+        last["ticket"], last["mtx"] = t, p.mtx
 
     def timed(p, steps, warmup, batch, nt=None):
         nt = n_total if nt is None else nt
@@ -633,6 +686,9 @@ def main():
     gc.freeze()                         # what exists now is setup: keep full collections out of the timed steps
     dt = timed(pipe, args.steps, args.warmup, frames)
     host_ms = {k: round(1e3 * v / args.steps, 3) for k, v in pipe.host_seconds.items()}
+    if args.dump_outputs and rank == 0:
+        full_recs, counts = last["ticket"].exchange.result()[:2]
+        dump_outputs(args.dump_outputs, full_recs, counts, last["emitted"], last["mtx"])
 
     if args.timed_only:
         sync()
@@ -645,7 +701,7 @@ def main():
             dist.destroy_process_group()
         return
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (1) the equal-precision chain: same region, classifier in plain f32 MFMA
         if args.cnn != "fp32":
             for _, c in lanes:
@@ -923,7 +979,7 @@ def main():
     sync()
     out_line = None
     if rank == 0:
-        stages = stage_pass(frames, M, F)
+        stages = stage_pass(frames, M, F) if args.full else {}      # --full: per-stage timings of a serial pass, rooflines
 
         def roof_of(stage):
             return roofline_of(stage, stages, args.cnn, F, H, W)
@@ -952,10 +1008,20 @@ def main():
             finally:
                 for c in cs:
                     c.timing_enable(False)
-        dom = busiest_stage_as_timed()
-        if dom not in stages:
+        dom = busiest_stage_as_timed() if args.full else None
+        if args.full and dom not in stages:
             dom = max(stages, key=lambda s: stages[s]["ms_total"])
         conv = [s for s in stages if s in MACS]
+        per_stage = {
+            "roofline": dict(roof_of(dom), protocol="dominant = the stage that holds its stream longest in an overlapped pass of the "
+                                                     "timed region's shape; its duration from the serial pass (HIP events)"),
+            "mfma_kernel": roof_of(max(conv, key=lambda s: stages[s]["ms_total"])) if conv else None,
+            "filter_pass": roof_of("median") if "median" in stages else None,
+            "filter_pass_fused": filter_fused_of(stages, H, W),
+            "stages": stages,
+            "stage_timing": "HIP events per context stream over %d serial steps after the timed region (256-frame launches); "
+                            "the timed region overlaps board and stones paths of two lanes on five streams" % prof_steps,
+        } if args.full else {}
         out_line = {
             "metric": "frames/sec on 1920x1080 video + 19x19 stone-grid match % vs reference SGF",
             "value": round((world if args.streams else 1) * n_total * args.steps / dt, 2),
@@ -970,14 +1036,7 @@ def main():
                        "cnn": args.cnn,
                        "frames_per_gpu": F, "height": H, "width": W, "parallelism": ("%d independent streams, one per GPU" % world) if args.streams else ("frames of one video dealt x%d" % world),
                        "lanes_per_gpu": len(lanes), "batches_in_flight": 2},
-            "roofline": dict(roof_of(dom), protocol="dominant = the stage that holds its stream longest in an overlapped pass of the "
-                                                     "timed region's shape; its duration from the serial pass (HIP events)"),
-            "mfma_kernel": roof_of(max(conv, key=lambda s: stages[s]["ms_total"])) if conv else None,
-            "filter_pass": roof_of("median") if "median" in stages else None,
-            "filter_pass_fused": filter_fused_of(stages, H, W),
-            "stages": stages,
-            "stage_timing": "HIP events per context stream over %d serial steps after the timed region (256-frame launches); "
-                            "the timed region overlaps board and stones paths of two lanes on five streams" % prof_steps,
+            **per_stage,
             "host_ms_per_step": dict(host_ms, note="rank 0, overlapped with the GPU work of the next batch; fold = "
                                                    "ck_boardfold_step + ck_policy_run over all %d records" % n_total),
             "board_found_by_fold": board_found,
@@ -986,7 +1045,7 @@ def main():
         }
         out_line.update(quality)
         out_line.update(extras)
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             # K1's cost follows the content: the bench scene, a textured frame, uniform noise (worst case)
             import torch.nn.functional as TF
             g = torch.Generator(device=dev)
@@ -1059,7 +1118,7 @@ def main():
             out_line["cv2_version"] = cv.pop("cv2")
             if cv:
                 out_line["cv2_crosscheck"] = cv
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out_line["cpu_baseline"] = cpu_baseline(frames, M, weights, n_warm=8, n_frames=args.cpu_frames, reps=5)
         line = bench_line(out_line, args.verbose)
         if not args.verbose and len(line) > LINE_BUDGET:

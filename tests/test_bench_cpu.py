@@ -97,3 +97,43 @@ def test_the_bench_line_fits_the_drivers_record_and_keeps_every_number():
         assert key in short
     assert short["roofline"]["bound"] == "mfma" and "traffic" in short["roofline"] and "frac" in short["roofline"]
     assert {"value", "unit", "cores", "kind", "sample"} <= set(short["cpu_baseline"])
+
+
+def test_dump_outputs_writes_every_array_as_float_within_the_budget(tmp_path):
+    """--dump-outputs: the last step's records, counts, requests and transform as float32 / float64 .npy files; over the
+    byte budget a fixed seeded sample of the frames, the same one every time"""
+    import bench
+    from camkifu_amd import pipeline
+    n = 40
+    rng = np.random.default_rng(3)
+    rec = np.zeros(n, pipeline.REC)
+    rec["status"], rec["n_lines"], rec["biggest_area"] = 1, rng.integers(0, 9, n), rng.random(n) * 1e5
+    rec["lines"] = rng.random(rec["lines"].shape).astype(np.float32)
+    rec["region_label"] = rng.integers(0, 3, rec["region_label"].shape)
+    rec["region_conf"] = rng.random(rec["region_conf"].shape)
+    counts = rng.integers(0, 50, (n, 19, 19)).astype(np.int32)
+    emitted = [()] * n
+    emitted[7] = [(2, [("B", 3, 4), ("W", 15, 16)])]
+    emitted[30] = [(1, [("W", 0, 18)])]
+    mtx = rng.random((3, 3))
+    names = bench.dump_outputs(str(tmp_path / "all"), rec, counts, emitted, mtx)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in names}
+    assert set(got) == {"frame_index", "board_result", "board_lines", "region_label", "region_conf", "fg_counts", "requests", "transform"}
+    for a in got.values():
+        assert a.dtype in (np.float32, np.float64)
+    assert np.array_equal(got["frame_index"], np.arange(n))
+    assert np.array_equal(got["board_lines"], rec["lines"]) and np.array_equal(got["region_conf"], rec["region_conf"])
+    assert np.array_equal(got["region_label"], rec["region_label"]) and np.array_equal(got["board_result"][:, 2], rec["n_lines"])
+    assert np.array_equal(got["fg_counts"], counts.reshape(n, -1))
+    assert got["requests"].tolist() == [[7, 2, 1, 3, 4], [7, 2, 2, 15, 16], [30, 1, 2, 0, 18]]
+    assert np.array_equal(got["transform"], mtx)
+    # a budget for 10 frames: a sorted seeded sample of 10, the same on a second call
+    small = 10 * 3200 + 4096
+    a = bench.dump_outputs(str(tmp_path / "a"), rec, counts, emitted, None, budget=small)
+    bench.dump_outputs(str(tmp_path / "b"), rec, counts, emitted, None, budget=small)
+    total = sum(os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) for k in a)
+    assert total <= small
+    ia, ib = np.load(str(tmp_path / "a" / "frame_index.npy")), np.load(str(tmp_path / "b" / "frame_index.npy"))
+    assert 0 < len(ia) < n and np.array_equal(ia, ib) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "region_conf.npy")), rec["region_conf"][ia.astype(int)])
+    assert np.isnan(np.load(str(tmp_path / "a" / "transform.npy"))).all()

@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline"], env=dict(os.environ, CK_PROFILE_HOST="1"),
+r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline"], env=dict(os.environ, CK_PROFILE_HOST="1"),
                    stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
 inside, laps, calls = False, collections.OrderedDict(), 0
 for line in r.stderr.splitlines():

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/switch_interval.txt}
 : > $out
 for round in 1 2; do
   for si in "" 0.001 0.0002; do
-    CK_SWITCH_INTERVAL=$si python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+    CK_SWITCH_INTERVAL=$si python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 h = d['holdoff_aware']

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out
 R=${ROUND:-r06}
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 bench.py --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 bench.py --full --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof_bench.err
 echo "bench stats done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial -- python3 tools/board_serial.py > $O/board_serial.log 2> $O/prof_serial.err
 echo "serial stats done"
@@ -39,7 +39,7 @@ else
 fi
 rm -rf $O/pmc_calib
 # the headline bench line FIRST among what is left: nothing below may keep it from being produced
-python bench.py > $O/bench_full.json 2> $O/bench_full.err
+python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 echo "bench done"
 python tools/stonefind_timing.py > $O/stonefind_timing.json 2> $O/stonefind_timing.err
 echo "stonefind timing done"

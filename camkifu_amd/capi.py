@@ -26,7 +26,7 @@ EXPORTS = [
     "ck_timing_enable", "ck_timing_reset", "ck_timing_get",
     "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
     "ck_i420_to_bgr", "ck_get_perspective_transform", "ck_warp_perspective",
-    "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy",
+    "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
     "ck_board_detect_records", "ck_cnn_regions_records",
@@ -142,6 +142,7 @@ class Context:
         if rc != 0:
             raise CkError("ck_ctx_create failed: " + (lib().ck_last_error(None) or b"").decode())
         self.device = device
+        self._mog2_shape = {}                    # handle -> (h, w) of the models this context created
 
     def close(self):
         """free the context.  A context another thread is still inside (for more than 5 s) is NOT freed and keeps its
@@ -377,6 +378,7 @@ class Context:
     def mog2_create(self, h=380, w=380):
         hd = C.c_int(-1)
         self._chk(lib().ck_mog2_create(self._h, h, w, C.byref(hd)))
+        self._mog2_shape[hd.value] = (int(h), int(w))
         return hd.value
 
     def mog2_apply(self, handle, img3, learning_rate):
@@ -385,8 +387,22 @@ class Context:
         self._chk(lib().ck_mog2_apply(self._h, int(handle), p, sp, C.c_double(learning_rate), fp_, osp))
         return fg
 
+    def mog2_state(self, handle):
+        """the model's mixture on the host: dict(weight (5, npx) f32, variance (5, npx) f32, mean (5, 3, npx) f32,
+        nmodes (npx,) u8), npx = h * w; slots k >= nmodes[px] are unspecified"""
+        st = self._mog2_shape.get(int(handle))
+        if st is None:
+            raise CkError("bad mog2 handle %d" % int(handle))
+        npx = st[0] * st[1]
+        out = dict(weight=np.empty((5, npx), np.float32), variance=np.empty((5, npx), np.float32),
+                   mean=np.empty((5, 3, npx), np.float32), nmodes=np.empty(npx, np.uint8))
+        self._chk(lib().ck_mog2_get_state(self._h, int(handle), *(out[k].ctypes.data_as(C.c_void_p)
+                                                                  for k in ("weight", "variance", "mean", "nmodes"))))
+        return out
+
     def mog2_destroy(self, handle):
         self._chk(lib().ck_mog2_destroy(self._h, int(handle)))
+        self._mog2_shape.pop(int(handle), None)
 
     # ---- K10..K12 ----------------------------------------------------------------------------
     def cnn_set_weights(self, weights):

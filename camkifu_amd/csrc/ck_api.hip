@@ -954,6 +954,23 @@ int ck_mog2_apply(ck_ctx* ctx, int handle, const uint8_t* img3, int in_space,
     CK_API_END(ctx)
 }
 
+int ck_mog2_get_state(ck_ctx* ctx, int handle, float* weight, float* variance, float* mean, uint8_t* nmodes)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    if (handle < 0 || handle >= (int)ctx->mog2.size() || !ctx->mog2[handle].alive)
+        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", handle);
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    const Mog2State& st = ctx->mog2[handle];
+    const size_t npx = (size_t)st.h * st.w;
+    CK_TRY(ck_from_device(ctx, weight, st.weight.p, npx * 5 * sizeof(float), CK_HOST));
+    CK_TRY(ck_from_device(ctx, variance, st.variance.p, npx * 5 * sizeof(float), CK_HOST));
+    CK_TRY(ck_from_device(ctx, mean, st.mean.p, npx * 15 * sizeof(float), CK_HOST));
+    CK_TRY(ck_from_device(ctx, nmodes, st.nmodes.p, npx, CK_HOST));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
 int ck_mog2_destroy(ck_ctx* ctx, int handle)
 {
     CK_API_BEGIN(ctx)

@@ -111,10 +111,14 @@ __device__ __forceinline__ bool mix_update(Mix& m, const float x0, const float x
         }
     }
     nmodes = bound;
-    totalWeight = 1.f / totalWeight;
+    // every live mode pruned in this update (rates >= ~0.67 only): no renormalisation, the surviving slots keep weight 0
+    // (1 / 0 = inf and 0 * inf = NaN would poison the pixel for good)
+    if (totalWeight != 0.f) {
+        totalWeight = 1.f / totalWeight;
 #pragma unroll
-    for (int mode = 0; mode < NMIX; mode++)
-        if (mode < nmodes) gw[mode] *= totalWeight;
+        for (int mode = 0; mode < NMIX; mode++)
+            if (mode < nmodes) gw[mode] *= totalWeight;
+    }
 
     if (!fitsPDF && alphaT > 0.f) {
         const int mode = (nmodes == NMIX) ? NMIX - 1 : nmodes++;

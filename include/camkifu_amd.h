@@ -137,6 +137,10 @@ int ck_mog2_create(ck_ctx* ctx, int h, int w, int* handle);
 int ck_mog2_apply(ck_ctx* ctx, int handle, const uint8_t* img3, int in_space,
                   double learning_rate, uint8_t* fgmask, int out_space);
 int ck_mog2_destroy(ck_ctx* ctx, int handle);
+/* the model's mixture, copied to HOST memory in the kernel's structure-of-arrays layout (npx = h * w, px = y * w + x):
+ * weight[k*npx + px], variance[k*npx + px], mean[(k*3 + c)*npx + px] for the 5 mode slots k, nmodes[px].  Slots at or
+ * above nmodes[px] hold no live mode and are unspecified.  Any pointer may be NULL (that array is skipped). */
+int ck_mog2_get_state(ck_ctx* ctx, int handle, float* weight, float* variance, float* mean, uint8_t* nmodes);
 
 /* ---- K10..K12 stone classifier                stone/nn_manager.py:216-298, nn_cache.py:16-52
  * weights: 12 float32 arrays in Keras-1 'tf' layout, order

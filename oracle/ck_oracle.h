@@ -103,6 +103,23 @@ typedef struct ora_mog2 ora_mog2;
 ora_mog2* ora_mog2_create(int h, int w, int cn);
 void ora_mog2_destroy(ora_mog2*);
 void ora_mog2_apply(ora_mog2*, const uint8_t* img, double learning_rate, uint8_t* fgmask);
+/* the mixture in the HIP kernel's structure-of-arrays layout (npx = h*w): weight[k*npx+px], variance[k*npx+px],
+ * mean[(k*cn+c)*npx+px], nmodes[px]; slots k >= nmodes[px] are stale.  NULL pointers are skipped. */
+void ora_mog2_get_state(const ora_mog2*, float* weight, float* variance, float* mean, uint8_t* nmodes);
+/* how often each rarely taken branch of the update ran since create, summed over pixels and frames
+ * (test infrastructure: tests/test_mog2_cpu.py holds the scenes to a floor on each) */
+enum {
+    ORA_MOG2_EV_PRUNE,        /* a live mode pruned */
+    ORA_MOG2_EV_PRUNE_INNER,  /* ... that was not the last live one (its slot stays inside the bound with weight 0) */
+    ORA_MOG2_EV_NEW,          /* a new mode opened (no match, alpha > 0) */
+    ORA_MOG2_EV_REPLACE,      /* ... replacing the weakest one because all NMIX were in use */
+    ORA_MOG2_EV_BUBBLE,       /* a match at mode >= 1 moved up at least one slot */
+    ORA_MOG2_EV_VARMIN,       /* the matched mode's new variance clamped up to varMin */
+    ORA_MOG2_EV_VARMAX,       /* ... clamped down to varMax */
+    ORA_MOG2_EV_ZERO_TOTAL,   /* a pixel that held modes ended the loop with totalWeight 0 (every live mode pruned) */
+    ORA_MOG2_NEVENTS
+};
+void ora_mog2_events(const ora_mog2*, int64_t out[ORA_MOG2_NEVENTS]);
 
 /* K10-K12  NNManager._get_x / create_net / NNCache.predict_*   stone/nn_manager.py:216-298,
  *          stone/nn_cache.py:16-52

@@ -17,7 +17,8 @@
  * ASSUMPTION below: (1) the order of the per-mode loop body (decay, match test on the first fitting mode only,
  * sort by bubbling the matched mode up, prune); (2) the prune test `w < -prune` with prune = -alpha * CT sits at
  * the END of the loop body and shortens the loop bound itself (see PRUNE NOTE); (3) a new mode replaces the
- * weakest one when all five are in use.  tests/test_gpu_parity.py::test_cv2_live_crosscheck compares masks with
+ * weakest one when all five are in use; (4) an update that prunes every live mode skips the renormalisation (see
+ * ALL-PRUNED GUARD).  tests/test_gpu_parity.py::test_cv2_live_crosscheck compares masks with
  * the real library whenever a machine has it.
  */
 #include "ck_oracle.h"
@@ -32,6 +33,7 @@ struct ora_mog2 {
     float* variance;  /* h*w*NMIX */
     float* mean;      /* h*w*NMIX*cn */
     uint8_t* nmodes;  /* h*w */
+    int64_t events[ORA_MOG2_NEVENTS];   /* how often each rarely taken branch ran (ora_mog2_events) */
 };
 
 ora_mog2* ora_mog2_create(int h, int w, int cn)
@@ -50,6 +52,26 @@ void ora_mog2_destroy(ora_mog2* m)
 {
     if (!m) return;
     free(m->weight); free(m->variance); free(m->mean); free(m->nmodes); free(m);
+}
+
+void ora_mog2_get_state(const ora_mog2* m, float* weight, float* variance, float* mean, uint8_t* nmodes)
+{
+    const size_t npx = (size_t)m->h * m->w;
+    const int cn = m->cn;
+    for (size_t px = 0; px < npx; px++) {
+        for (int k = 0; k < NMIX; k++) {
+            if (weight) weight[k * npx + px] = m->weight[px * NMIX + k];
+            if (variance) variance[k * npx + px] = m->variance[px * NMIX + k];
+            if (mean)
+                for (int c = 0; c < cn; c++) mean[((size_t)k * cn + c) * npx + px] = m->mean[(px * NMIX + k) * cn + c];
+        }
+        if (nmodes) nmodes[px] = m->nmodes[px];
+    }
+}
+
+void ora_mog2_events(const ora_mog2* m, int64_t out[ORA_MOG2_NEVENTS])
+{
+    memcpy(out, m->events, sizeof(m->events));
 }
 
 void ora_mog2_apply(ora_mog2* m, const uint8_t* img, double learning_rate, uint8_t* fgmask)
@@ -72,6 +94,7 @@ void ora_mog2_apply(ora_mog2* m, const uint8_t* img, double learning_rate, uint8
     const float prune = (float)(-lr * fCT);
 
     size_t npx = (size_t)m->h * m->w;
+    int64_t* ev = m->events;
     for (size_t px = 0; px < npx; px++) {
         float* gw = m->weight + px * NMIX;
         float* gv = m->variance + px * NMIX;
@@ -104,6 +127,8 @@ void ora_mog2_apply(ora_mog2* m, const uint8_t* img, double learning_rate, uint8
                     float k = alphaT / weight;
                     for (int c = 0; c < cn; c++) mean_m[c] -= k * dData[c];
                     float varnew = var + k * (dist2 - var);
+                    ev[ORA_MOG2_EV_VARMIN] += varnew < varMin;
+                    ev[ORA_MOG2_EV_VARMAX] += varnew > varMax;
                     varnew = varnew > varMin ? varnew : varMin;
                     varnew = varnew < varMax ? varnew : varMax;
                     gv[mode] = varnew;
@@ -117,6 +142,7 @@ void ora_mog2_apply(ora_mog2* m, const uint8_t* img, double learning_rate, uint8
                             t = mean[i * cn + c]; mean[i * cn + c] = mean[(i - 1) * cn + c]; mean[(i - 1) * cn + c] = t;
                         }
                     }
+                    ev[ORA_MOG2_EV_BUBBLE] += swap_count > 0;
                 }
             }
             /* PRUNE NOTE (ASSUMPTION 2).  Zivkovic's complexity-reduction prior subtracts alpha * CT from every
@@ -125,15 +151,30 @@ void ora_mog2_apply(ora_mog2* m, const uint8_t* img, double learning_rate, uint8
              * `weight` above, the test is weight < -prune (i.e. below +alpha * CT: the component could not survive
              * the next subtraction), and discarding = zero weight + one fewer live mode; because `nmodes` is the
              * bound of this very loop and the modes are sorted by weight, only trailing modes are ever cut. */
-            if (weight < -prune) { weight = 0.f; nmodes--; }
+            if (weight < -prune) {
+                weight = 0.f; nmodes--;
+                ev[ORA_MOG2_EV_PRUNE]++;
+                ev[ORA_MOG2_EV_PRUNE_INNER] += mode - swap_count < nmodes;   /* the slot stays live with weight 0 */
+            }
             gw[mode - swap_count] = weight;
             totalWeight += weight;
         }
-        totalWeight = 1.f / totalWeight;
-        for (int mode = 0; mode < nmodes; mode++) gw[mode] *= totalWeight;
-        (void)nNewModes;
+        /* ALL-PRUNED GUARD (ASSUMPTION 4).  At a rate of ~0.67 or more every live mode of a pixel that matches none of
+         * them can fall below the prune threshold in one update; totalWeight is then 0, and 1/0 = inf times the 0
+         * weights of the slots still inside the loop bound would write NaN that no later update removes.  The
+         * renormalisation is skipped instead: those slots keep weight 0 and are replaced or pruned by the ordinary
+         * rules.  This is the totalWeight > FLT_EPSILON guard later library releases are believed to carry (not
+         * verified against their source); no rate the product uses reaches it. */
+        if (totalWeight != 0.f) {
+            totalWeight = 1.f / totalWeight;
+            for (int mode = 0; mode < nmodes; mode++) gw[mode] *= totalWeight;
+        } else if (nNewModes > 0) {
+            ev[ORA_MOG2_EV_ZERO_TOTAL]++;
+        }
 
         if (!fitsPDF && alphaT > 0.f) {
+            ev[ORA_MOG2_EV_NEW]++;
+            ev[ORA_MOG2_EV_REPLACE] += nmodes == NMIX;
             int mode = (nmodes == NMIX) ? NMIX - 1 : nmodes++;
             if (nmodes == 1) gw[mode] = 1.f;
             else {

@@ -218,6 +218,10 @@ def i420_to_bgr(i420, h, w):
     return out
 
 
+# ora_mog2_events, in the order of ck_oracle.h's ORA_MOG2_EV_*
+MOG2_EVENTS = ("prune", "prune_inner", "new_mode", "replace", "bubble", "var_min", "var_max", "zero_total")
+
+
 class MOG2:
     def __init__(self, h, w, cn=3):
         self.h, self.w, self.cn = h, w, cn
@@ -228,6 +232,21 @@ class MOG2:
         fg = np.empty((self.h, self.w), np.uint8)
         lib().ora_mog2_apply(self._p, _vp(img), C.c_double(learning_rate), _vp(fg))
         return fg
+
+    def state(self):
+        """the mixture in the HIP library's layout (Context.mog2_state): dict(weight (5, npx) f32, variance (5, npx) f32,
+        mean (5, cn, npx) f32, nmodes (npx,) u8), npx = h * w; slots k >= nmodes[px] are stale"""
+        npx = self.h * self.w
+        out = dict(weight=np.empty((5, npx), np.float32), variance=np.empty((5, npx), np.float32),
+                   mean=np.empty((5, self.cn, npx), np.float32), nmodes=np.empty(npx, np.uint8))
+        lib().ora_mog2_get_state(self._p, *(_vp(out[k]) for k in ("weight", "variance", "mean", "nmodes")))
+        return out
+
+    def events(self):
+        """{name: count} of the update's rarely taken branches since create, over all pixels and frames (MOG2_EVENTS)"""
+        out = np.zeros(len(MOG2_EVENTS), np.int64)
+        lib().ora_mog2_events(self._p, _vp(out))
+        return dict(zip(MOG2_EVENTS, (int(v) for v in out)))
 
     def __del__(self):
         try:

@@ -1127,10 +1127,26 @@ def test_cv2_live_crosscheck(ck, ora, synth):
         report["transform"] = float(np.abs(M - ora.get_perspective_transform(sc["corners"], dst)).max())
         warp = cv2.warpPerspective(fr, M, (380, 380))
         report["warp"] = int((warp != ck.warp_perspective(fr, M)).sum()) + int((warp != ora.warp_perspective(fr, M)).sum())
+        report["mog2"] = 0
         for rate in (0.01, 0.005):
             mask = bg_cv.apply(warp, learningRate=rate)
-            report["mog2"] = int((mask != ck.mog2_apply(bg_hip, warp, rate)).sum()) + int((mask != bg_ora.apply(warp, rate)).sum())
+            report["mog2"] += int((mask != ck.mog2_apply(bg_hip, warp, rate)).sum()) + int((mask != bg_ora.apply(warp, rate)).sum())
         print("cv2 %s cross-check, scene %d:" % (cv2.__version__, k), report)
         assert report["median"] == 0 and report["canny"] == 0 and report["n_contours"] == 0 and report["ghost"] == 0
         assert report["hough"] == 0 and report["warp"] == 0 and report["mog2"] == 0
         assert report["biggest_area"] <= 1e-3 and report["transform"] <= 1e-9
+    # MOG2 long enough to prune (tests/mog2_scenes.py, the product's rates): 150 applies on fresh models, every mask
+    from tests import mog2_scenes as S
+    bg_cv = cv2.createBackgroundSubtractorMOG2(detectShadows=False)
+    bg_hip, bg_ora = ck.mog2_create(380, 380), ora.MOG2(380, 380, 3)
+    rates = S.rates("product", 150)
+    diff = 0
+    for t0 in range(0, 150, 50):
+        for t, img in enumerate(S.mosaic(380, 380, range(t0, t0 + 50), seed=41), t0):
+            mask = bg_cv.apply(img, learningRate=float(rates[t]))
+            diff += int((mask != ck.mog2_apply(bg_hip, img, float(rates[t]))).sum())
+            diff += int((mask != bg_ora.apply(img, float(rates[t]))).sum())
+    ck.mog2_destroy(bg_hip)
+    print("cv2 %s cross-check, MOG2 over 150 frames: %d pixels differ, oracle events %s" % (cv2.__version__, diff, bg_ora.events()))
+    assert bg_ora.events()["prune"] > 0
+    assert diff == 0

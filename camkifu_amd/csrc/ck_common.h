@@ -204,9 +204,6 @@ static inline int ck_pitch(int w) { return (w + 63) & ~63; }
 // d_range (nullable): per (frame, channel, CK_RANGE_TILE^2 tile) two bytes lo, hi with lo <= every median of the tile <= hi
 // (n * 3 * ceil(h / T) * ceil(w / T) * 2 bytes; what k_canny_planar takes to skip its flat tiles)
 #define CK_RANGE_TILE 48
-#ifndef CK_TILE_RANGE
-#define CK_TILE_RANGE 1        // 0: no bounds written, no tile skipped (A/B builds)
-#endif
 static inline size_t ck_range_bytes(int n, int h, int w)
 {
     return (size_t)n * 3 * ((h + CK_RANGE_TILE - 1) / CK_RANGE_TILE) * ((w + CK_RANGE_TILE - 1) / CK_RANGE_TILE) * 2;

@@ -16,10 +16,6 @@
 // (The gradient phase on the fp16 matrix pipe -- canny_nms_mfma_kernel, built and measured in round 4: 8.1 us per 1080p frame
 // against this file's 5.5 -- is archived in tools/variants/canny_nms_mfma.hip.txt.)
 
-#ifndef NMS_LOCAL_UF
-#define NMS_LOCAL_UF 1     // tile-local union-find of the candidates inside the NMS kernel
-#endif
-
 namespace {
 
 constexpr int TW = 64;
@@ -319,7 +315,6 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
         km[it] = keepmask;
     }
     if (NMS_STOP == 3) return;
-#if NMS_LOCAL_UF
     // Tile-local part of the hysteresis union-find, in LDS: every candidate is linked with its W / N (or NW, NE)
     // neighbours inside this tile, so the global pass (canny_link_kernel) only has to visit the candidates on the
     // tile's left, right and top edges.  Hooking is by smaller index and local order = raster order, so a local root
@@ -383,14 +378,6 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
     }
     __syncthreads();
     if (NMS_STOP == 4) return;
-#else
-    {
-        int mine = 0;
-#pragma unroll
-        for (int it = 0; it < NQ; it++) mine |= km[it];
-        if (!__syncthreads_or(mine)) return;           // the pixel tile is dead from here on (cbuf)
-    }
-#endif
 #pragma unroll
     for (int it = 0; it < NQ; it++) {
         const int q = tid + 256 * it;
@@ -403,12 +390,8 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
         for (int k = 0; k < 4; k++)
             if (km[it] & (1 << k)) {
                 const int p = y * w + ox + col0 + k;
-#if NMS_LOCAL_UF
                 const int root = lfind(4 * q + k);
                 labels[(size_t)f * h * w + p] = (oy + (root >> 6)) * w + ox + (root & 63);
-#else
-                labels[(size_t)f * h * w + p] = p;
-#endif
                 cbuf[slot++] = p;
             }
     }
@@ -449,11 +432,9 @@ __global__ __launch_bounds__(256) void canny_link_kernel(const uint8_t* __restri
     for (int i = bx * 256 + threadIdx.x; i < n; i += LIST_BLOCKS * 256) {
         const int p = C[i];
         const int y = p / w, x = p - y * w;
-#if NMS_LOCAL_UF
         // links inside a tile of the NMS kernel were made there, in LDS: only a tile's left / right / top edge has
         // a W, N, NW or NE neighbour in another tile
         { const int c = x % NTW; if (c != 0 && c != NTW - 1 && y % NTH != 0) continue; }
-#endif
         if (x > 0 && m[p - 1] != 1) uf_union(L, p, p - 1);
         if (y > 0) {
             if (m[p - w] != 1) uf_union(L, p, p - w);
@@ -512,9 +493,6 @@ int k_canny_planar(ck_ctx* ctx, const uint8_t* d_planes, int n, int h, int w, in
                    const int* d_thr, const uint8_t* d_range)
 {
     if (low > high) { int t = low; low = high; high = t; }
-#if !CK_TILE_RANGE
-    d_range = nullptr;
-#endif
     const size_t npx = (size_t)n * h * w;
     CK_TRY(ck_ensure(ctx, ctx->labels2, npx * 4));                 // candidate lists (one slab per frame)
     CK_TRY(ck_ensure(ctx, ctx->misc, (size_t)n * 64 + 4096));

@@ -38,18 +38,6 @@
 #ifndef H2_STAGE_UNROLL
 #define H2_STAGE_UNROLL 8
 #endif
-#ifndef H2C2_SWZ
-#define H2C2_SWZ 1      // conv2: swizzled LDS tile, 24 pixel tiles per block (3 per wave); 0 = padded tile, 16 per block
-#endif
-#ifndef H2_FC1
-#define H2_FC1 1         // first dense layer in split precision too
-#endif
-#ifndef H2_FUSE34
-#define H2_FUSE34 1      // conv3 and conv4 in one workgroup, conv3's output stays in LDS
-#endif
-#ifndef H2_FUSE1
-#define H2_FUSE1 1       // conv1 computed inside conv2 (needs H2C2_SWZ)
-#endif
 #ifndef H2C2S_PF
 #define H2C2S_PF 1      // 3 x 2 accumulator tiles leave room for a 2-slot weight ring only (PF 2: 141 VGPRs, 3 waves per SIMD, 17.3 us)
 #endif
@@ -62,17 +50,8 @@
 #ifndef H2C3_SB
 #define H2C3_SB false
 #endif
-#ifndef H2C2_PF
-#define H2C2_PF 2
-#endif
 #ifndef H2C34_PF
 #define H2C34_PF 2
-#endif
-#ifndef H2C2_TB
-#define H2C2_TB 16
-#endif
-#ifndef H2C2_WM
-#define H2C2_WM 8
 #endif
 constexpr float H2_WSCALE = 256.f;      // split-precision mode: weights are stored x 2^8 (their lo halves stay normal fp16)
 #ifndef C1_R
@@ -116,12 +95,6 @@ __device__ unsigned long long g_h2_log[3 * H2_LOG_CAP];
 #define H2_STAMP(K) do { } while (0)
 #define H34_STAMP(K) do { } while (0)
 #endif
-#ifndef H2_REBALANCE
-#define H2_REBALANCE 1    // conv2: the tiles of a patch's short last block dealt out evenly over its waves
-#endif
-#ifndef H2_PRIO
-#define H2_PRIO 1         // wave priority 3 outside the k-loop (staging, fused conv1, epilogue), 0 inside: see conv_h2_body
-#endif
 #ifndef H2C34_RN
 #define H2C34_RN 3        // channel tiles per wave in the fused conv3 + conv4 kernel: 3 -> 4 waves per workgroup, 2 -> 6 waves
 #endif
@@ -133,10 +106,6 @@ __device__ unsigned long long g_h2_log[3 * H2_LOG_CAP];
 #endif
 #ifndef H2C2S_WM
 #define H2C2S_WM 8       // waves per conv2 workgroup along the pixel tiles: R = H2C2S_TB / H2C2S_WM tiles per wave
-#endif
-#ifndef CK_H2_OPMAJOR
-#define CK_H2_OPMAJOR 0     // developer knob: product-major order of the split-precision MFMAs inside a k-step (same sums bit for bit;
-                            // measured: 14.8 vs 14.9 us per frame when held to 128 VGPRs, 16.6 at 130 -- the chain order is not the limit)
 #endif
 
 namespace {
@@ -532,13 +501,14 @@ constexpr int h2_tile_halves()
 }
 
 // The layer itself, as a device function over a caller-owned LDS tile so that two layers can share one workgroup:
+//   FUSE1   : conv2 -- its input, conv1's output, is computed here from the u8 pixels into a swizzled tile;
 //   IN_LDS  : the input tile is already in `lds` (written by the previous layer's call), nothing is staged;
 //   NXT_W>0 : the output (relu, not pooled) is not written to `out` but split into hi/lo halves straight into `lds`
 //             in the NEXT layer's tile layout (NXT_W pixels per row, NXT_PS halves per pixel, NXT_RS per row,
 //             NXT_CINP channels per plane, channels COUT..NXT_CINP-1 zeroed) -- after a barrier, because that tile
 //             overlays this layer's input.
-template <int H, int W, int CIN, int KH, int KW, int COUT, int TB, int YB, int WAVES_M, int RN, bool POOL, int PF, bool SB, bool SWZ = false,
-          bool FUSE1 = false, bool IN_LDS = false, int NXT_W = 0, int NXT_PS = 0, int NXT_RS = 0, int NXT_CINP = 0>
+template <int H, int W, int CIN, int KH, int KW, int COUT, int TB, int YB, int WAVES_M, int RN, bool POOL, int PF, bool SB, bool FUSE1 = false,
+          bool IN_LDS = false, int NXT_W = 0, int NXT_PS = 0, int NXT_RS = 0, int NXT_CINP = 0>
 __device__ __forceinline__ void conv_h2_body(
     _Float16* __restrict__ lds, const int patch, const int blk_y,
     const float* __restrict__ in, const uint16_t* __restrict__ wt, const float* __restrict__ bias,
@@ -549,8 +519,8 @@ __device__ __forceinline__ void conv_h2_body(
     constexpr int OH = H - KH + 1, OW = W - KW + 1, M = OH * OW;
     constexpr int NT = cdiv(COUT, 16), WAVES_N = NT / RN;
     constexpr int CINP = cdiv(CIN, 32) * 32;
-    // SWZ: no padding -- a pixel is exactly its 8 chunks of 16 bytes (hi 0..3, lo 4..7), rows are whole multiples of
-    // 256 bytes, and chunk c of the pixel at column x of tile row y sits in slot c ^ h2_swz(x, y) =
+    // FUSE1, the swizzled tile: no padding -- a pixel is exactly its 8 chunks of 16 bytes (hi 0..3, lo 4..7), rows are
+    // whole multiples of 256 bytes, and chunk c of the pixel at column x of tile row y sits in slot c ^ h2_swz(x, y) =
     // c ^ (2 (x >> 1) ^ (x & 1) ^ 4 (y & 1)).  ds_read_b128 is served in four groups of 16 lanes that are NOT contiguous
     // ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, + 32: MI355X_MICROARCH.md, LDS): a group holds the two diagonal 2x2
     // windows of the pooling tile with k-quarter kq and the two off-diagonal ones with kq ^ 1.  Found by exhaustive
@@ -559,9 +529,9 @@ __device__ __forceinline__ void conv_h2_body(
     // fused conv1 (16 consecutive pixels of a row per lane group) spread over the 32 store banks two deep, as before.
     // (The round-2 swizzle, (x >> 1) & 7 with rows 32 bytes apart, is conflict-free for CONTIGUOUS groups of 16
     // lanes; with the real groups the model gives 9.6 LDS cycles per read instead of 4.)
-    static_assert(!SWZ || (CINP == 32 && POOL), "swizzled layout: 32 channels, pooling tiles");
-    constexpr int PS = SWZ ? 2 * CINP : 2 * CINP + h2_pspad<CINP, POOL>();              // halves per pixel
-    constexpr int RS = SWZ ? W * PS : lds_stride_b(W * PS, h2_rsrem<CINP, POOL, OW>(), 64);     // halves per row
+    static_assert(!FUSE1 || (CINP == 32 && POOL), "swizzled layout: 32 channels, pooling tiles");
+    constexpr int PS = FUSE1 ? 2 * CINP : 2 * CINP + h2_pspad<CINP, POOL>();              // halves per pixel
+    constexpr int RS = FUSE1 ? W * PS : lds_stride_b(W * PS, h2_rsrem<CINP, POOL, OW>(), 64);     // halves per row
     constexpr int KS = KH * KW * (CINP / 32);
     constexpr int NTHREADS = 64 * WAVES_M * WAVES_N;
     constexpr int R = cdiv(TB, WAVES_M);
@@ -571,7 +541,7 @@ __device__ __forceinline__ void conv_h2_body(
     static_assert(CIN % 2 == 0, "channel pairs");
     constexpr int ROWS_RAW = POOL ? 4 * (TB / (OW / 4)) + KH - 1 : (TB * 16 + OW - 2) / OW + 1 + KH - 1;
     constexpr int ROWS = ROWS_RAW < H ? ROWS_RAW : H;
-    static_assert(ROWS * RS == h2_tile_halves<H, W, CIN, KH, KW, TB, POOL, SWZ>(), "tile size helper out of step");
+    static_assert(ROWS * RS == h2_tile_halves<H, W, CIN, KH, KW, TB, POOL, FUSE1>(), "tile size helper out of step");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = wave % WAVES_N, wm = wave / WAVES_N;
@@ -586,18 +556,18 @@ __device__ __forceinline__ void conv_h2_body(
     // (measured per workgroup: 7.8 us of staging + conv1 next to 8.4 us of k-loop, for 6 % of the flops).  They run
     // at wave priority 3, the k-loop at 0: the issue arbiter serves the short phase first, the matrix pipe stays fed
     // by the other workgroup.
-    if constexpr (H2_PRIO != 0) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     const int tile_blk = blk_y * TB;
     const int oy_min = POOL ? 4 * (tile_blk / (OW / 4)) : (tile_blk * 16) / OW;
     int row_cnt = H - oy_min;
     if (row_cnt > ROWS) row_cnt = ROWS;
     if constexpr (FUSE1) {
         // conv1 (5x5x3 -> 32, relu) of the 40x40 u8 patch computed HERE for the rows this block needs: its output goes
-        // straight into the swizzled tile as hi/lo halves and never exists in HBM.  Same arithmetic as conv1_h2_kernel
-        // (K = 6 kernel rows x 16 slots in three k-steps, weights as the A operand, two MFMAs per product), so the
-        // values are bit-identical to the unfused pair of kernels; a block recomputes the 4 halo rows it shares with
-        // its neighbour (+33 % of a layer that is 6 % of the network).
-        static_assert(SWZ && W == 36 && CIN == 32 && KH == 5, "conv1 fusion is wired for conv2");
+        // straight into the swizzled tile as hi/lo halves and never exists in HBM.  The u8 pixels are exact in fp16, so
+        // only the weights are split (K = 6 kernel rows x 16 slots in three k-steps, weights as the A operand, two MFMAs
+        // per product); a block recomputes the 4 halo rows it shares with its neighbour (+33 % of a layer that is 6 % of
+        // the network).
+        static_assert(W == 36 && CIN == 32 && KH == 5, "conv1 fusion is wired for conv2");
         constexpr int IRS = 128;                              // halves per staged input row: 120 used, 8 zero
         constexpr int IROWS = ROWS + 4;
         static_assert((IROWS + 1) * IRS == H2_IN1_HALVES, "staged pixel rows: helper out of step");
@@ -734,16 +704,9 @@ __device__ __forceinline__ void conv_h2_body(
                 big = fmaxf(big, fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)));
                 h2v hh, ll;
                 split_h2x2(v.x, v.y, hh, ll);
-                if constexpr (SWZ) {
-                    const int x = pxl % W, sw = h2_swz(x, pxl / W);
-                    _Float16* d = &lds[(pxl / W) * RS + x * PS + (2 * c & 7)];
-                    *reinterpret_cast<h2v*>(d + (((c >> 2) ^ sw) << 3)) = hh;
-                    *reinterpret_cast<h2v*>(d + (((c >> 2) ^ sw ^ 4) << 3)) = ll;
-                } else {
-                    _Float16* d = &lds[(pxl / W) * RS + (pxl % W) * PS + 2 * c];
-                    *reinterpret_cast<h2v*>(d) = hh;
-                    *reinterpret_cast<h2v*>(d + CINP) = ll;
-                }
+                _Float16* d = &lds[(pxl / W) * RS + (pxl % W) * PS + 2 * c];
+                *reinterpret_cast<h2v*>(d) = hh;
+                *reinterpret_cast<h2v*>(d + CINP) = ll;
             }
         }
         if (overflow && !(big <= 65000.f)) *overflow = 1;       // also true for NaN
@@ -761,9 +724,9 @@ __device__ __forceinline__ void conv_h2_body(
 
     // The last block of a patch may hold fewer tiles than TB (conv2: 64 pooling tiles = 24 + 24 + 16).  With the fixed
     // R tiles per wave five of its eight waves would do three tiles and the rest next to nothing, and the block would take as
-    // long as a full one for two thirds of the work: its tiles are dealt out evenly instead (H2_REBALANCE).
+    // long as a full one for two thirds of the work: its tiles are dealt out evenly instead.
     int r_blk = R;
-    if constexpr (H2_REBALANCE && FUSE1) {
+    if constexpr (FUSE1) {
         const int left = RT - tile_blk;
         if (left < TB) r_blk = (left + WAVES_M - 1) / WAVES_M;
     }
@@ -783,8 +746,8 @@ __device__ __forceinline__ void conv_h2_body(
             if (m > M - 1) m = M - 1;
             oy = m / OW; ox = m % OW;
         }
-        abase[r] = SWZ ? (oy - oy_min) * RS + ox * PS : (oy - oy_min) * RS + ox * PS + 8 * kq;
-        axr[r] = SWZ ? (ox | ((oy - oy_min) & 1) << 18) : ox;      // swizzled layout: column, and 4 x the parity of the tile row
+        abase[r] = FUSE1 ? (oy - oy_min) * RS + ox * PS : (oy - oy_min) * RS + ox * PS + 8 * kq;
+        axr[r] = FUSE1 ? (ox | ((oy - oy_min) & 1) << 18) : ox;      // swizzled layout: column, and 4 x the parity of the tile row
     }
     // The accumulators start at bias x weight scale (a power of two: exact), so the epilogue has no global load to wait
     // for -- the bias fetch hides behind the staging instead of sitting between the last MFMA and the stores.
@@ -801,7 +764,7 @@ __device__ __forceinline__ void conv_h2_body(
 
     int nv = TB - wm * R;
     nv = nv > R ? R : nv;
-    if constexpr (H2_REBALANCE && FUSE1) {
+    if constexpr (FUSE1) {
         const int left = RT - tile_blk;
         if (left < TB) {
             nv = left - wm * r_blk;
@@ -820,7 +783,7 @@ __device__ __forceinline__ void conv_h2_body(
         // A fragment of a step live and the occupancy collapses.
         constexpr int NS = PF + 1;
         uint4 bq[NS][RN][2];
-        if constexpr (SWZ) {
+        if constexpr (FUSE1) {
             // column tap outermost: the swizzle of a pixel depends on its column x = ox + j and on the parity of its row.
             // The two fragment addresses of a pixel tile are computed once per tap column; a row of the other parity
             // flips bit 2 of the slot, which is exactly what tells the hi plane from the lo plane -- so for odd taps i the
@@ -862,29 +825,6 @@ __device__ __forceinline__ void conv_h2_body(
                         bh[n] = __builtin_bit_cast(h8, bq[seq % NS][n][0]);
                         bl[n] = __builtin_bit_cast(h8, bq[seq % NS][n][1]);
                     }
-#if CK_H2_OPMAJOR
-                    // product-major order: the three products of a step go round all NV x RN accumulators before any
-                    // accumulator is touched again (each still sees al*bh, ah*bl, ah*bh in that order: same sums, bit for
-                    // bit), and every A fragment of the step is requested before the first MFMA
-                    h8 ahv[NV > 0 ? NV : 1], alv[NV > 0 ? NV : 1];
-#pragma unroll
-                    for (int r = 0; r < NV; r++) {
-                        ahv[r] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(&lds[((i & 1) ? a1j[r] : a0j[r]) + i * RS]));
-                        alv[r] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(&lds[((i & 1) ? a0j[r] : a1j[r]) + i * RS]));
-                    }
-#pragma unroll
-                    for (int r = 0; r < NV; r++)
-#pragma unroll
-                        for (int n = 0; n < RN; n++) acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alv[r], bh[n], acc[r][n], 0, 0, 0);
-#pragma unroll
-                    for (int r = 0; r < NV; r++)
-#pragma unroll
-                        for (int n = 0; n < RN; n++) acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv[r], bl[n], acc[r][n], 0, 0, 0);
-#pragma unroll
-                    for (int r = 0; r < NV; r++)
-#pragma unroll
-                        for (int n = 0; n < RN; n++) acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv[r], bh[n], acc[r][n], 0, 0, 0);
-#else
 #pragma unroll
                     for (int r = 0; r < NV; r++) {
                         const h8 ah = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(&lds[((i & 1) ? a1j[r] : a0j[r]) + i * RS]));
@@ -896,7 +836,6 @@ __device__ __forceinline__ void conv_h2_body(
                             acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[n], acc[r][n], 0, 0, 0);
                         }
                     }
-#endif
                     if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -948,17 +887,17 @@ __device__ __forceinline__ void conv_h2_body(
         }
     };
     const bool idle = tile0 >= RT;             // the last block of a patch may hold fewer tiles than waves x R
-    if constexpr (H2_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     if (!idle && H2_DBG_SKIP != 1) {
         if (nv == R) k_loop(std::integral_constant<int, R>{});
-        else if constexpr (R * WAVES_M > TB || (H2_REBALANCE && FUSE1)) {
-            if (nv == R - 1 || !(H2_REBALANCE && FUSE1)) k_loop(std::integral_constant<int, R - 1>{});
+        else if constexpr (R * WAVES_M > TB || FUSE1) {
+            if (nv == R - 1 || !FUSE1) k_loop(std::integral_constant<int, R - 1>{});
             else if constexpr (R >= 3) { if (nv == R - 2) k_loop(std::integral_constant<int, R - 2>{}); }
         }
     }
 
     float nxt_big = 0.f;
-    if constexpr (H2_PRIO != 0) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     if constexpr (NXT_W > 0) __syncthreads();          // every wave is done with the input tile the output overlays
     H2_STAMP(2);                                       // wave 0's k-loop
     H34_STAMP(5);                                      // conv3: k-loop + barrier
@@ -1044,22 +983,21 @@ __device__ __forceinline__ void conv_h2_body(
 #endif
 }
 
-template <int H, int W, int CIN, int KH, int KW, int COUT, int TB, int YB, int WAVES_M, int RN, bool POOL, int PF, bool SB, bool SWZ = false,
-          bool FUSE1 = false>
+template <int H, int W, int CIN, int KH, int KW, int COUT, int TB, int YB, int WAVES_M, int RN, bool POOL, int PF, bool SB, bool FUSE1>
 // (two workgroups of 8 waves must fit a CU: 4 waves per SIMD = 128 VGPRs -- the second launch bound is HIP's minimum waves per SIMD; said explicitly, because one register more halves the occupancy)
 __global__ __launch_bounds__(64 * WAVES_M * (cdiv(COUT, 16) / RN), (64 * WAVES_M * (cdiv(COUT, 16) / RN) >= 512 ? 4 : 1)) void conv_mfma16_h2_kernel(
     const float* __restrict__ in, const uint16_t* __restrict__ wt, const float* __restrict__ bias,
     float* __restrict__ out, float wscale_inv, int* __restrict__ overflow,
     const uint8_t* __restrict__ goban1 = nullptr, const uint16_t* __restrict__ wf1 = nullptr, const float* __restrict__ bias1 = nullptr)
 {
-    __shared__ __attribute__((aligned(16))) _Float16 lds[h2_tile_halves<H, W, CIN, KH, KW, TB, POOL, SWZ>()];
-    conv_h2_body<H, W, CIN, KH, KW, COUT, TB, YB, WAVES_M, RN, POOL, PF, SB, SWZ, FUSE1>(lds, blockIdx.x, blockIdx.y, in, wt, bias, out,
-                                                                                        wscale_inv, overflow, goban1, wf1, bias1);
+    __shared__ __attribute__((aligned(16))) _Float16 lds[h2_tile_halves<H, W, CIN, KH, KW, TB, POOL, FUSE1>()];
+    conv_h2_body<H, W, CIN, KH, KW, COUT, TB, YB, WAVES_M, RN, POOL, PF, SB, FUSE1>(lds, blockIdx.x, blockIdx.y, in, wt, bias, out,
+                                                                                  wscale_inv, overflow, goban1, wf1, bias1);
 }
 
 // conv3 (3x3x32 -> 90, relu) and conv4 (3x3x90 -> 90, relu, 2x2 max-pool) of one patch in one workgroup: conv3's
 // 14x14x90 output is written as hi/lo halves into conv4's LDS tile (which overlays conv3's own input tile once its
-// k-loop is done) instead of going to HBM and back.  Same arithmetic in the same order as the two kernels apart.
+// k-loop is done) instead of going to HBM and back.
 __global__ __launch_bounds__(64 * 2 * (6 / H2C34_RN), H2C34_MINW) void conv34_h2_kernel(
     const float* __restrict__ in, const uint16_t* __restrict__ wt3, const float* __restrict__ bias3,
     const uint16_t* __restrict__ wt4, const float* __restrict__ bias4, float* __restrict__ out, float wscale_inv,
@@ -1071,7 +1009,7 @@ __global__ __launch_bounds__(64 * 2 * (6 / H2C34_RN), H2C34_MINW) void conv34_h2
 #if H2_DBG_TIME
     const unsigned long long t0__ = wall_clock64();
 #endif
-    conv_h2_body<16, 16, 32, 3, 3, 90, 13, 1, 2, H2C34_RN, false, H2C3_PF, H2C3_SB, false, false, false, 14, PS4, RS4, 96>(
+    conv_h2_body<16, 16, 32, 3, 3, 90, 13, 1, 2, H2C34_RN, false, H2C3_PF, H2C3_SB, false, false, 14, PS4, RS4, 96>(
         lds, blockIdx.x, 0, in, wt3, bias3, nullptr, wscale_inv, overflow);
 #if H2_DBG_TIME
     const unsigned long long t1__ = wall_clock64();
@@ -1080,7 +1018,7 @@ __global__ __launch_bounds__(64 * 2 * (6 / H2C34_RN), H2C34_MINW) void conv34_h2
 #if H2_DBG_TIME
     const unsigned long long t2__ = wall_clock64();
 #endif
-    conv_h2_body<14, 14, 90, 3, 3, 90, 9, 1, 2, H2C34_RN, true, H2C34_PF, true, false, false, true>(
+    conv_h2_body<14, 14, 90, 3, 3, 90, 9, 1, 2, H2C34_RN, true, H2C34_PF, true, false, true>(
         lds, blockIdx.x, 0, nullptr, wt4, bias4, out, wscale_inv, overflow);
 #if H2_DBG_TIME
     if (threadIdx.x == 0) {
@@ -1088,116 +1026,6 @@ __global__ __launch_bounds__(64 * 2 * (6 / H2C34_RN), H2C34_MINW) void conv34_h2
         atomicAdd(&g_h34_prof[3], 1ull);
     }
 #endif
-}
-
-// conv1 in split-precision mode.  The u8 pixels are exact in fp16, so only the weights are split and a product
-// is two MFMAs (x*lo + x*hi).  K = 75 is laid out as 6 kernel rows x 16 slots (slot = kw*3 + cin, slot 15 and
-// row 5 are zero weights): three k-steps of 32; a lane's fragment is 8 consecutive halves of one input row of
-// the staged fp16 tile (unaligned, read as 8 ds_read_u16 -- there are only nine fragments per wave and unit).
-// Same persistent unit walk, operand swap and 16-byte stores as conv1_mfma16_kernel.
-//   wf : [2 channel tiles][3 steps][hi|lo][64 lanes][8] fp16 (pack_conv1_h2), weights x 2^8
-template <int R>
-__global__ __launch_bounds__(64 * (27 / R)) void conv1_h2_kernel(
-    const uint8_t* __restrict__ goban, const uint16_t* __restrict__ wf, const float* __restrict__ bias,
-    float* __restrict__ out, int nunits, float wscale_inv)
-{
-#pragma clang fp contract(off)
-    constexpr int WAVES = 27 / R, NTHREADS = 64 * WAVES;
-    constexpr int OW = 36, ROWS = 16, RS = 128;           // halves per staged row: 120 used, 8 zero
-    constexpr int NPT = cdiv(ROWS * 30, NTHREADS);
-    __shared__ _Float16 lds[(ROWS + 1) * RS];            // one extra all-zero row for kernel row 5
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kq = lane >> 4;
-
-    uint32_t raw[NPT];
-    auto fetch = [&](int unit) {
-#pragma unroll
-        for (int q = 0; q < NPT; q++) {
-            const int d = tid + q * NTHREADS;
-            raw[q] = 0u;
-            if (unit < nunits && d < ROWS * 30) {
-                const int patch = unit / 3, by = unit % 3;
-                const int frame = patch / 100, reg = patch % 100;
-                const int py0 = region_origin(reg / 10) + 12 * by, px0 = region_origin(reg % 10);
-                const uint8_t* src = goban + ((size_t)frame * 380 + py0 + d / 30) * 380 * 3 + (size_t)px0 * 3;
-                raw[q] = reinterpret_cast<const uint32_t*>(src)[d % 30];
-            }
-        }
-    };
-    int unit = blockIdx.x;
-    fetch(unit);
-    for (int i = tid; i < ROWS * 8 + RS; i += NTHREADS) {                      // zero the padding columns and the extra row
-        if (i < ROWS * 8) lds[(i / 8) * RS + 120 + i % 8] = (_Float16)0.f;
-        else lds[ROWS * RS + i - ROWS * 8] = (_Float16)0.f;
-    }
-    h8 wq[3][2][2];
-#pragma unroll
-    for (int s = 0; s < 3; s++)
-#pragma unroll
-        for (int n = 0; n < 2; n++)
-#pragma unroll
-            for (int pl = 0; pl < 2; pl++)
-                wq[s][n][pl] = __builtin_bit_cast(h8, reinterpret_cast<const uint4*>(wf)[((n * 3 + s) * 2 + pl) * 64 + lane]);
-    float4 bv[2];
-#pragma unroll
-    for (int n = 0; n < 2; n++) bv[n] = *reinterpret_cast<const float4*>(bias + n * 16 + 4 * kq);
-    int abase[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int m = (wave * R + r) * 16 + l15;
-        abase[r] = (m / OW + (kq >> 1)) * RS + (m % OW) * 3 + 8 * (kq & 1);
-    }
-
-    for (; unit < nunits; unit += gridDim.x) {
-#pragma unroll
-        for (int q = 0; q < NPT; q++) {
-            const int d = tid + q * NTHREADS;
-            if (d < ROWS * 30) {
-                _Float16* o = &lds[(d / 30) * RS + 4 * (d % 30)];
-                o[0] = (_Float16)(float)(raw[q] & 0xFFu); o[1] = (_Float16)(float)((raw[q] >> 8) & 0xFFu);
-                o[2] = (_Float16)(float)((raw[q] >> 16) & 0xFFu); o[3] = (_Float16)(float)(raw[q] >> 24);
-            }
-        }
-        __syncthreads();
-        fetch(unit + gridDim.x);
-
-        f32x4 acc[R][2];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-#pragma unroll
-            for (int n = 0; n < 2; n++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc[r][n][e] = 0.f;
-#pragma unroll
-        for (int s = 0; s < 3; s++) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const _Float16* ap = &lds[abase[r] + 2 * s * RS];
-                h8 a;
-#pragma unroll
-                for (int e = 0; e < 8; e++) a[e] = ap[e];
-#pragma unroll
-                for (int n = 0; n < 2; n++) {
-                    acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[s][n][1], a, acc[r][n], 0, 0, 0);
-                    acc[r][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[s][n][0], a, acc[r][n], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-        const int patch = unit / 3, by = unit % 3;
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const size_t m = (size_t)patch * 1296 + (size_t)by * 432 + (wave * R + r) * 16 + l15;
-                float4 v;
-                v.x = acc[r][n][0] * wscale_inv + bv[n].x; v.y = acc[r][n][1] * wscale_inv + bv[n].y;
-                v.z = acc[r][n][2] * wscale_inv + bv[n].z; v.w = acc[r][n][3] * wscale_inv + bv[n].w;
-                v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                *reinterpret_cast<float4*>(out + m * 32 + n * 16 + 4 * kq) = v;
-            }
-        }
-    }
 }
 
 // dense 3240 -> 160 + relu as an MFMA GEMM over patches (v_mfma_f32_16x16x4_f32, K ascending).
@@ -1678,11 +1506,6 @@ int k_cnn_pack_weights(ck_ctx* ctx, const float* const w[12], int space)
     return CK_OK;
 }
 
-// Tuning knob (developer only): extra dynamic LDS requested by the two big classifier kernels.  Enough of it leaves ONE
-// workgroup per CU instead of two, i.e. room (registers, wave slots) for waves of the board path running on other streams.
-static int lds_pad_conv2() { static const int v = getenv("CK_CONV2_LDS_PAD") ? atoi(getenv("CK_CONV2_LDS_PAD")) : 0; return v; }
-static int lds_pad_conv34() { static const int v = getenv("CK_CONV34_LDS_PAD") ? atoi(getenv("CK_CONV34_LDS_PAD")) : 0; return v; }
-
 int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, uint8_t* d_labels, double* d_conf,
                   int* d_nonfinite, uint8_t* d_rlabel, double* d_rconf)
 {
@@ -1727,14 +1550,9 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
         float* p4 = p4_all + (size_t)f0 * 100 * 3240;
         {
             TimeScope ts(ctx, "cnn_conv1");
-            if (q8 || (h2 && H2C2_SWZ && H2_FUSE1)) {
-                // conv1 is computed inside conv2's staging (below)
-            } else if (h2)
-                hipLaunchKernelGGL((conv1_h2_kernel<C1_R>), dim3(std::min(np * 3, C1_GRID)), dim3(64 * (27 / C1_R)), 0, ctx->stream, gob,
-                                   (const uint16_t*)W.c1w_h2.p, (const float*)W.c1b.p, a1, np * 3, 1.f / H2_WSCALE);
-            else
-            hipLaunchKernelGGL((conv1_mfma16_kernel<C1_R>), dim3(std::min(np * 3, C1_GRID)), dim3(64 * (27 / C1_R)), 0,
-                               ctx->stream, gob, (const float*)W.c1w.p, (const float*)W.c1b.p, a1, np * 3);
+            if (!q8 && !h2)     // (q8, h2: conv1 is computed inside conv2's staging, below)
+                hipLaunchKernelGGL((conv1_mfma16_kernel<C1_R>), dim3(std::min(np * 3, C1_GRID)), dim3(64 * (27 / C1_R)), 0,
+                                   ctx->stream, gob, (const float*)W.c1w.p, (const float*)W.c1b.p, a1, np * 3);
         }
         {
             TimeScope ts(ctx, "cnn_conv2");
@@ -1743,8 +1561,7 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
             if (q8) {
                 CK_TRY(k_cnn_q8_conv12(ctx, gob, np, p2, d_nonfinite));
             } else if (h2) {
-#if H2C2_SWZ
-                hipLaunchKernelGGL((conv_mfma16_h2_kernel<36, 36, 32, 5, 5, 32, H2C2S_TB, 64 / H2C2S_TB + (64 % H2C2S_TB != 0), H2C2S_WM, 2, true, H2C2S_PF, H2C2S_SB, true, H2_FUSE1 != 0>), dim3(np, 64 / H2C2S_TB + (64 % H2C2S_TB != 0)), dim3(64 * H2C2S_WM), (size_t)lds_pad_conv2(), ctx->stream,
+                hipLaunchKernelGGL((conv_mfma16_h2_kernel<36, 36, 32, 5, 5, 32, H2C2S_TB, 64 / H2C2S_TB + (64 % H2C2S_TB != 0), H2C2S_WM, 2, true, H2C2S_PF, H2C2S_SB, true>), dim3(np, 64 / H2C2S_TB + (64 % H2C2S_TB != 0)), dim3(64 * H2C2S_WM), 0, ctx->stream,
                                    (const float*)a1, (const uint16_t*)W.c2w_h2.p, (const float*)W.c2b.p, p2, 1.f / H2_WSCALE, d_nonfinite,
                                    gob, (const uint16_t*)W.c1w_h2.p, (const float*)W.c1b.p);
 #if H2_DBG_TIME
@@ -1802,10 +1619,6 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
                     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h2_log), lg.data(), lg.size() * 8);
                 }
 #endif
-#else
-                hipLaunchKernelGGL((conv_mfma16_h2_kernel<36, 36, 32, 5, 5, 32, H2C2_TB, 64 / H2C2_TB, H2C2_WM, 2, true, H2C2_PF, true>), dim3(np, 64 / H2C2_TB), dim3(64 * H2C2_WM), 0, ctx->stream,
-                                   (const float*)a1, (const uint16_t*)W.c2w_h2.p, (const float*)W.c2b.p, p2, 1.f / H2_WSCALE, d_nonfinite);
-#endif
             }
             else
             hipLaunchKernelGGL((conv_mfma16_f32_kernel<36, 36, 32, 5, 5, 32, C2_TB, 64 / C2_TB, C2_WM, C2_RN, true>), dim3(np, 64 / C2_TB),
@@ -1816,10 +1629,10 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
         if (q8) {
             TimeScope ts(ctx, "cnn_conv4");
             CK_TRY(k_cnn_q8_conv34(ctx, p2, np, p4, d_nonfinite));
-        } else if (h2 && H2_FUSE34) {
+        } else if (h2) {
             TimeScope ts(ctx, "cnn_conv4");
             // conv3 + conv4 of a patch in one workgroup; pooled 6x6x90 written directly
-            hipLaunchKernelGGL(conv34_h2_kernel, dim3(np), dim3(64 * 2 * (6 / H2C34_RN)), (size_t)lds_pad_conv34(), ctx->stream, (const float*)p2, (const uint16_t*)W.c3w_h2.p,
+            hipLaunchKernelGGL(conv34_h2_kernel, dim3(np), dim3(64 * 2 * (6 / H2C34_RN)), 0, ctx->stream, (const float*)p2, (const uint16_t*)W.c3w_h2.p,
                                (const float*)W.c3b.p, (const uint16_t*)W.c4w_h2.p, (const float*)W.c4b.p, p4, 1.f / H2_WSCALE, d_nonfinite);
 #if H2_DBG_TIME
             {
@@ -1836,10 +1649,6 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
             {
                 TimeScope ts(ctx, "cnn_conv3");
                 // 13 pixel tiles x 6 channel tiles of 16
-                if (h2)
-                    hipLaunchKernelGGL((conv_mfma16_h2_kernel<16, 16, 32, 3, 3, 90, 13, 1, 2, 3, false, H2C3_PF, H2C3_SB>), dim3(np), dim3(256), 0, ctx->stream,
-                                       (const float*)p2, (const uint16_t*)W.c3w_h2.p, (const float*)W.c3b.p, a3, 1.f / H2_WSCALE, d_nonfinite);
-                else
                 hipLaunchKernelGGL((conv_mfma16_f32_kernel<16, 16, 32, 3, 3, 90, 13, 1, C3_WM, 1, false>), dim3(np), dim3(384 * C3_WM), 0,
                                    ctx->stream, (const float*)p2, (const float*)W.c3w.p, (const float*)W.c3b.p, a3);
             }
@@ -1847,10 +1656,6 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
             {
                 TimeScope ts(ctx, "cnn_conv4");
                 // 9 tiles of four pooling windows x 6 channel tiles; pooled 6x6x90 written directly
-                if (h2)
-                    hipLaunchKernelGGL((conv_mfma16_h2_kernel<14, 14, 90, 3, 3, 90, 9, 1, 2, 3, true, H2C34_PF, true>), dim3(np), dim3(256), 0, ctx->stream,
-                                       (const float*)a3, (const uint16_t*)W.c4w_h2.p, (const float*)W.c4b.p, p4, 1.f / H2_WSCALE, d_nonfinite);
-                else
                 hipLaunchKernelGGL((conv_mfma16_f32_kernel<14, 14, 90, 3, 3, 90, 9, 1, C4_WM, 1, true>), dim3(np), dim3(384 * C4_WM), 0,
                                    ctx->stream, (const float*)a3, (const float*)W.c4w.p, (const float*)W.c4b.p, p4);
             }
@@ -1860,7 +1665,7 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
     {
         TimeScope ts(ctx, "cnn_tail");
         const int np = nframes * 100;
-        if (h2 && H2_FC1)
+        if (h2)
             hipLaunchKernelGGL(fc1_h2_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream, (const float*)p4_all,
                                (const uint16_t*)W.d1w_h2.p, (const float*)W.d1b.p, h1, np, 1.f / H2_WSCALE, d_nonfinite);
         else

@@ -91,10 +91,7 @@ __device__ __forceinline__ int swz32(int x) { return (x >> 1) & 3; }
 // workgroups per CU.  (With two padding columns per pixel row, 54 144 B, only TWO were resident -- tools/micro/wave_placement.hip:
 // LDS is handed out in units of 1 280 B and 3 x 43 of them exceed the CU's 128.  The sixth tap of a kernel row, which the
 // padding fed, has zero weights and needs finite halves only: the last pixel tile column re-reads its fifth.)
-#ifndef BF_C12_PIXPAD
-#define BF_C12_PIXPAD 0      // developer A/B: 1 = the two padding columns back (54 144 B, two workgroups per CU)
-#endif
-constexpr int C12_PIX_RS = (40 + 2 * BF_C12_PIXPAD) * 4, C12_PIX_ROWS = 24;          // halves
+constexpr int C12_PIX_RS = 40 * 4, C12_PIX_ROWS = 24;          // halves
 constexpr int C12_TILE_RS = 36 * 32, C12_TILE_ROWS = 20;       // halves
 
 __global__ __launch_bounds__(256, BF_C12_MINW) void conv12_bf16_kernel(
@@ -141,10 +138,6 @@ __global__ __launch_bounds__(256, BF_C12_MINW) void conv12_bf16_kernel(
             d[0] = lo; d[1] = hi;
         }
     };
-#if BF_C12_PIXPAD
-    if (tid >= 240)
-        for (int r = tid - 240; r < C12_PIX_ROWS; r += 16) *reinterpret_cast<uint4*>(&pix[r * C12_PIX_RS + 160]) = make_uint4(0, 0, 0, 0);
-#endif
     const int half = blockIdx.x & 1;
     load_raw(half);
     store_pix();

@@ -43,9 +43,6 @@
 #ifndef Q8_C4_D
 #define Q8_C4_D 6            // conv4: depth of the fragment ring
 #endif
-#ifndef Q8_PRIO
-#define Q8_PRIO 1            // wave priority 3 outside the k-loops (staging, conv1, relayout, epilogue): these short phases of loads, LDS traffic
-#endif                       // and vector arithmetic otherwise wait behind the other workgroup's matrix instructions for every issue slot
 #ifndef Q8_DBG_TIME
 #define Q8_DBG_TIME 0        // profiling aid: phase times per workgroup (thread 0, 100 MHz wall clock) summed into g_q8_prof
 #endif
@@ -160,7 +157,9 @@ __device__ __forceinline__ void conv12_q8_body(
     const int frame = patch / 100, reg = patch % 100;
     const int px0 = region_origin(reg % 10);
     Q8_STAMP_BEGIN;
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(3);
+    // wave priority 3 outside the k-loops (staging, conv1, relayout, epilogue): these short phases of loads, LDS traffic
+    // and vector arithmetic otherwise wait behind the other workgroup's matrix instructions for every issue slot
+    __builtin_amdgcn_s_setprio(3);
     // the PROWS x 40 pixels of the item: a thread fetches 12 bytes (4 pixels) and turns them into 32 bytes of halves (byte b
     // becomes the half 0x6400 | b = 1024 + b by one v_perm_b32 per two values, minus 1024 by one packed subtraction)
     if (tid < PROWS * 10) {
@@ -273,7 +272,7 @@ __device__ __forceinline__ void conv12_q8_body(
     Q8_STAMP(1);                                           // wave 0's conv1 tiles
     __syncthreads();
     Q8_STAMP(2);                                           // ... the other waves'
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
     // ---- conv2: wave = (channel tile n, 16-column strip s), T output rows.  Eight sweeps over the strip's ROWS input rows:
     // M0 M1 X01 M2 M3 X23 M4 X4 (M j: main term of tap column j; X: cross terms of a pair of columns).  The five weight
@@ -350,7 +349,7 @@ __device__ __forceinline__ void conv12_q8_body(
         }
     }
     Q8_STAMP(3);                                           // wave 0's k-loop
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
 
     // ---- 2x2 max-pool in the lane (bias in the sums already; max commutes with the relu), x 2^-8, f32 out
     float* o = out + (size_t)patch * 256 * 32 + 16 * n + l15;
@@ -424,7 +423,7 @@ __device__ __forceinline__ void conv34_q8_body(
     const int patch = blockIdx.x;
     Q8_STAMP_BEGIN;
     const int s_act = scale_act(kq), s_wgt = scale_wgt(kq);
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
 
     {   // stage: four consecutive channels of a pixel per step -> hi plane at 0, q plane at C34_PLANE.  All loads of a thread
         // first (left as a loop the compiler keeps one in flight: 3.9 us per workgroup, measured)
@@ -451,7 +450,7 @@ __device__ __forceinline__ void conv34_q8_body(
     }
     __syncthreads();
     Q8_STAMP(8);                                           // input staged
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
     // ---- conv3
     auto store_px = [&](int n, int oy, const Split4& sp) {
@@ -618,7 +617,7 @@ __device__ __forceinline__ void conv34_q8_body(
     };
     static_for<PF>([&](auto kc) { wload4(kc, wb4[decltype(kc)::value]); });     // (requested before the barriers of the relayout: an L2 round trip ahead)
     Q8_STAMP(9);                                           // wave 0's conv3
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     __syncthreads();                                       // every wave is done with conv3's input, which rows 0 .. 6 overlay
 #pragma unroll
     for (int u = 0; u < NU; u++)
@@ -629,7 +628,7 @@ __device__ __forceinline__ void conv34_q8_body(
     if (overflow && big3 != 0.f) *overflow = 1;
     __syncthreads();
     Q8_STAMP(10);                                          // barrier, rows 0 .. 6 stored, barrier
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
     static_for<D4 - 1>([&](auto uc) { a_read4(uc, ar4[decltype(uc)::value]); });
     static_for<NT4>([&](auto uc) {
@@ -650,7 +649,7 @@ __device__ __forceinline__ void conv34_q8_body(
         __builtin_amdgcn_sched_barrier(0);
     });
     Q8_STAMP(11);                                          // wave 0's conv4 loop
-    if (Q8_PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     float* o = out + (size_t)patch * 3240;
     float big4 = 0.f;
 #pragma unroll

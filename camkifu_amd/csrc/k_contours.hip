@@ -446,12 +446,6 @@ __global__ __launch_bounds__(256) void border_list_kernel(const uint8_t* __restr
 //     stay in the dense label image, which only ever holds them at edge pixels: Canny's labels when no edge touched
 //     the image frame, rebuilt here otherwise.
 // prep then moves 2 MB in + 2.4 MB out per 1080p frame instead of 2 + 10.3.
-#ifndef CCL_RUNS_EZ
-#define CCL_RUNS_EZ 0           // 1: prep_runs also writes the cleared-frame edge bytes (round 3; nothing in the run-table form reads them)
-#endif
-#ifndef CCL_PRELINK
-#define CCL_PRELINK 1
-#endif
 struct RunTab {
     unsigned long long* bits;
     uint16_t* rank;
@@ -559,7 +553,7 @@ __global__ __launch_bounds__(256) void prep_runs_kernel(const uint8_t* __restric
         // the run that starts at x = 0.  Column 0 of the cleared frame is background in every row: these runs are one
         // component by construction, so they start out pointing at node 0 (row 0, the root of the outer background)
         // instead of being chained row to row by h - 1 unions
-        rp[y] = CCL_PRELINK ? 0 : y;
+        rp[y] = 0;
     }
     unsigned long long* bw = rt.bits + ((size_t)f * h + y) * rt.w64;
     uint16_t* rw = rt.rank + ((size_t)f * h + y) * rt.w64;
@@ -585,7 +579,7 @@ __global__ __launch_bounds__(256) void prep_runs_kernel(const uint8_t* __restric
                         E[slot] = p;
                         // the stretch right of the row's LAST edge pixel reaches column w - 1, background in every row and
                         // joined to row 0 through it: born into the outer background as well
-                        if (nodes_fit) rp[h + slot] = (CCL_PRELINK && slot == base + total - 1) ? 0 : h + slot;
+                        if (nodes_fit) rp[h + slot] = slot == base + total - 1 ? 0 : h + slot;
                         if (!keep_edge_parents) L[(size_t)f * h * w + p] = p;
                         slot++;
                     }
@@ -613,29 +607,24 @@ __global__ __launch_bounds__(256) void link_runs_kernel(int h, int w, int32_t* _
     const uint16_t* rk = rt.rank + (size_t)f * h * w64;
     const int32_t* rb = rt.rowbase + (size_t)f * h;
     int32_t* rp = rt.rp + (size_t)f * rt.rp_stride;
-    for (int i = bx * 256 + threadIdx.x; i < ne + (CCL_PRELINK ? 0 : h - 1); i += LIST_BLOCKS * 256) {
-        if (i < ne) {
-            const int p = E[i];                        // 1 <= x <= w-2, 1 <= y <= h-2
-            const int y = p / w, x = p - y * w;
-            const bool e_n = rt_edge(bf, w64, y - 1, x), e_ne = rt_edge(bf, w64, y - 1, x + 1);
-            const bool e_e = rt_edge(bf, w64, y, x + 1), e_s = rt_edge(bf, w64, y + 1, x), e_se = rt_edge(bf, w64, y + 1, x + 1);
-            if (!edges_linked) {
-                if (rt_edge(bf, w64, y, x - 1)) uf_union(L, p, p - 1);
-                if (e_n) uf_union(L, p, p - w);
-                else {
-                    if (rt_edge(bf, w64, y - 1, x - 1)) uf_union(L, p, p - w - 1);
-                    if (e_ne) uf_union(L, p, p - w + 1);
-                }
+    for (int i = bx * 256 + threadIdx.x; i < ne; i += LIST_BLOCKS * 256) {
+        const int p = E[i];                        // 1 <= x <= w-2, 1 <= y <= h-2
+        const int y = p / w, x = p - y * w;
+        const bool e_n = rt_edge(bf, w64, y - 1, x), e_ne = rt_edge(bf, w64, y - 1, x + 1);
+        const bool e_e = rt_edge(bf, w64, y, x + 1), e_s = rt_edge(bf, w64, y + 1, x), e_se = rt_edge(bf, w64, y + 1, x + 1);
+        if (!edges_linked) {
+            if (rt_edge(bf, w64, y, x - 1)) uf_union(L, p, p - 1);
+            if (e_n) uf_union(L, p, p - w);
+            else {
+                if (rt_edge(bf, w64, y - 1, x - 1)) uf_union(L, p, p - w - 1);
+                if (e_ne) uf_union(L, p, p - w + 1);
             }
-            // the stretch opening right of p: (y, x + 1) and the pixel above it both background
-            if (!e_e && !e_ne) uf_union(rp, h + i, rt_run(bf, rk, rb, h, w64, y - 1, x + 1));
-            // the one opening right of p in the row below (if the pixel below p is an edge pixel too -- a vertical
-            // stroke -- that pixel's own stretch is this very one: leave it to it)
-            if (!e_se && !e_e && !e_s) uf_union(rp, rt_run(bf, rk, rb, h, w64, y + 1, x + 1), h + i);
-        } else {
-            const int yy = i - ne + 1;                 // x = 0 of rows 1 .. h-1: always background
-            uf_union(rp, yy, yy - 1);
         }
+        // the stretch opening right of p: (y, x + 1) and the pixel above it both background
+        if (!e_e && !e_ne) uf_union(rp, h + i, rt_run(bf, rk, rb, h, w64, y - 1, x + 1));
+        // the one opening right of p in the row below (if the pixel below p is an edge pixel too -- a vertical
+        // stroke -- that pixel's own stretch is this very one: leave it to it)
+        if (!e_se && !e_e && !e_s) uf_union(rp, rt_run(bf, rk, rb, h, w64, y + 1, x + 1), h + i);
     }
 }
 
@@ -1205,11 +1194,11 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
             rt.rowbase = (int32_t*)((char*)ctx->runs.p + rb_o);
             rt.rp = (int32_t*)((char*)ctx->runs.p + rp_o);
             if (w <= 1024)
-                hipLaunchKernelGGL(prep_runs_kernel<4>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, CCL_RUNS_EZ ? ez : (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
+                hipLaunchKernelGGL(prep_runs_kernel<4>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
             else if (w <= 2048)
-                hipLaunchKernelGGL(prep_runs_kernel<8>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, CCL_RUNS_EZ ? ez : (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
+                hipLaunchKernelGGL(prep_runs_kernel<8>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
             else
-                hipLaunchKernelGGL(prep_runs_kernel<16>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, CCL_RUNS_EZ ? ez : (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
+                hipLaunchKernelGGL(prep_runs_kernel<16>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
             hipLaunchKernelGGL(link_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, L, (const FrameTab*)d_tab, (const int32_t*)elist, rt, kflag);
             hipLaunchKernelGGL(flatten_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, L, (const FrameTab*)d_tab, (const int32_t*)elist, rt, kflag);
             hipLaunchKernelGGL(roots_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, compid, d_tab, maxc,
@@ -1332,7 +1321,7 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
             CK_HIP(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)n * 4, ctx->stream));
             CK_HIP(ctx, hipMemsetAsync(d_counter, 0, 8, ctx->stream));
             // (run-table form: the cleared-frame bytes were not written; the hull-candidate test reads the edge image as it came in)
-            const bool raw_edges = run_table && !CCL_RUNS_EZ;
+            const bool raw_edges = run_table;
             const uint8_t* e_img = raw_edges ? d_edges : (const uint8_t*)ez;
             hipLaunchKernelGGL(gather_segments_kernel, lgrid, lblock, 0, ctx->stream, e_img, h, w,
                                (const int32_t*)L, (const int32_t*)compid, maxc, (const uint8_t*)d_want, nc_max,
@@ -1350,7 +1339,7 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
             if (two[1]) {                                   // a segment overflowed: the whole round again, one counter for all
                 TimeScope ts(ctx, "contour_gather");
                 CK_HIP(ctx, hipMemsetAsync(d_counter, 0, 4, ctx->stream));
-                const bool raw_edges = run_table && !CCL_RUNS_EZ;
+                const bool raw_edges = run_table;
                 hipLaunchKernelGGL(gather_points_kernel, lgrid, lblock, 0, ctx->stream, raw_edges ? d_edges : (const uint8_t*)ez, h, w,
                                    (const int32_t*)L, (const int32_t*)compid, maxc, (const uint8_t*)d_want, nc_max,
                                    (const FrameTab*)d_tab, (const int32_t*)blist, d_counter, gcap, d_pts, 0, (int)raw_edges);

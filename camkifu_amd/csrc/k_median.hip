@@ -488,9 +488,6 @@ __global__ void interleaved_to_planar_kernel(const uint8_t* __restrict__ in, int
 int k_median_planar(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int ksize, uint8_t* d_planes, int pitch, uint8_t* d_range)
 {
     TimeScope ts(ctx, "median");
-#if !CK_TILE_RANGE
-    d_range = nullptr;
-#endif
     dim3 grid((w + MT - 1) / MT, (h + MT - 1) / MT, n * 3);
 #define CK_MEDIAN_CASE(KS) case KS: hipLaunchKernelGGL(median_mfma_kernel<KS>, grid, dim3(64), 0, ctx->stream, d_bgr, h, w, d_planes, pitch, d_range); break;
     switch (ksize) {

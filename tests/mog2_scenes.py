@@ -166,6 +166,16 @@ SCHEDULES = ("auto", "product", "zero", "reset", "high", "mixed")
 
 
 # ---------------------------------------------------------------- state comparison
+def zone_counts(mask):
+    """ora.zone_counts as one block sum (20 x 20 zones, pixel row and column 379 not counted): the oracle's loop over
+    the 361 zones costs ~0.1 s a frame.  tests/test_gpu_mog2.py::test_band_run_lengths_against_the_oracle checks the
+    two agree."""
+    m = (np.asarray(mask) != 0).astype(np.int32)
+    m[379, :] = 0
+    m[:, 379] = 0
+    return m.reshape(19, 20, 19, 20).sum((1, 3), dtype=np.int32)
+
+
 def state_mismatch(a, b):
     """None if two mixtures (Context.mog2_state / oracle MOG2.state layout) agree -- nmodes equal, and for every slot
     k < nmodes the weight, variance and mean bit-equal, NaN counting equal to NaN of any payload; slots at or above

@@ -30,15 +30,6 @@ def _same_state(ck, handle, model, what):
     assert bad is None, "%s: %s" % (what, bad)
 
 
-def _zone_counts(mask):
-    """ora.zone_counts as one block sum (20 x 20 zones, pixel row and column 379 not counted): the oracle's loop over
-    the 361 zones costs ~0.1 s a frame.  test_band_run_lengths_against_the_oracle checks the two agree."""
-    m = (np.asarray(mask) != 0).astype(np.int32)
-    m[379, :] = 0
-    m[:, 379] = 0
-    return m.reshape(19, 20, 19, 20).sum((1, 3), dtype=np.int32)
-
-
 def _dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -112,7 +103,7 @@ def test_band_run_lengths_against_the_oracle(ck, ora):
         assert got.shape == (k, 19, 19)
         for j in range(k):
             mask = model.apply(band[j], float(r[t0 + j]))
-            want = _zone_counts(mask)
+            want = S.zone_counts(mask)
             if j in (0, k - 1):
                 assert np.array_equal(want, ora.zone_counts(mask))
             assert np.array_equal(got[j], want), "run of %d, frame %d: %d zones differ" % (k, t0 + j, int((got[j] != want).sum()))
@@ -149,7 +140,7 @@ def test_band_states_are_rows_of_the_whole_image(ck, ora, world, whole_image_run
     and each band's mixture is the matching rows of the whole-image oracle's, bit for bit (two runs: 17 + 23 frames)"""
     from camkifu_amd import pipeline
     frames, r, masks, state = whole_image_run
-    want_counts = np.stack([_zone_counts(m) for m in masks])
+    want_counts = np.stack([S.zone_counts(m) for m in masks])
     for a, b in pipeline.band_rows(world):
         y0, y1 = 20 * a, min(20 * b, 380)
         last = b == 19
@@ -180,7 +171,7 @@ def test_apply_and_run_interleaved_on_one_handle(ck, ora):
         else:
             got = _host(ck.mog2_band_run(hd, frames[t0:t0 + k], r[t0:t0 + k], last_band=True))
             for j in range(k):
-                assert np.array_equal(got[j], _zone_counts(model.apply(frames[t0 + j], float(r[t0 + j])))), t0 + j
+                assert np.array_equal(got[j], S.zone_counts(model.apply(frames[t0 + j], float(r[t0 + j])))), t0 + j
         _same_state(ck, hd, model, "after %s of frames %d .. %d" % (form, t0, t0 + k - 1))
         t0 += k
     ck.mog2_destroy(hd)
@@ -201,7 +192,7 @@ def test_stones_run_hand_clip_against_the_oracle(ck, ora):
     for t0 in (0, 50, 100):
         got = _host(ck.stones_run(frames[t0:t0 + 50], M, mog2=hd, learning_rates=r[t0:t0 + 50])["fgcount"])
         for j in range(50):
-            want = _zone_counts(model.apply(ora.warp_perspective(frames[t0 + j], M), float(r[t0 + j])))
+            want = S.zone_counts(model.apply(ora.warp_perspective(frames[t0 + j], M), float(r[t0 + j])))
             assert np.array_equal(got[j], want), "frame %d: %d zones differ" % (t0 + j, int((got[j] != want).sum()))
     _same_state(ck, hd, model, "after 150 frames")
     assert model.events()["prune"] > 0

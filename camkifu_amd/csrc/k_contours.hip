@@ -1412,45 +1412,61 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
             trig[k] = (float)(cos((double)ang) * 1.f);
         }
     }
-    CK_TRY(ck_ensure(ctx, ctx->peaks, (size_t)n * PEAK_CAP * 8 + (size_t)n * pcap * 4));
-    int32_t* d_peaks = (int32_t*)ctx->peaks.p;
-    uint32_t* d_hpts = (uint32_t*)(d_peaks + (size_t)n * PEAK_CAP * 2);
-    {
-        TimeScope ts(ctx, "ghost");
-        CK_HIP(ctx, hipMemcpyAsync(d_sel, sel.data(), sel_bytes, hipMemcpyHostToDevice, ctx->stream));
-        CK_HIP(ctx, hipMemcpyAsync(d_trig, trig.data(), trig.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ghost_list_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, (const int32_t*)compid,
-                           (const int32_t*)d_sel, d_tab, (const int32_t*)blist, pcap, d_hpts, d_ghost_out);
-        CK_HIP(ctx, hipGetLastError());
+    const size_t row_bytes = (size_t)((stride + 1) / 2) * 4;               // 16-bit counters, two per dword
+    int rb = (int)((144 * 1024) / row_bytes) - 2;                          // inner rows per workgroup (+ 2 halo rows)
+    if (rb > 10) rb = 10;
+    if (rb < 1) return ck_fail(ctx, CK_ERR_ARG, "image too large for the Hough LDS slab");
+    int threads = HOUGH_THREADS;
+    // A call of a few frames (the hold-off-aware fold's windows, a live finder's single frame) is a latency matter, and
+    // next to the classifier -- two workgroups of 79 KB on every CU -- a workgroup that wants a whole CU's LDS waits until
+    // that kernel's grid drains: 1.5 ms of a 16-frame call's 3.0 (tools/board_call_latency.py).  Small batches take
+    // slabs that fit the hole ONE retiring classifier workgroup leaves (<= 72 KB, 512 threads): same peaks (rows with
+    // their halo, sorted on the host), more workgroups re-reading the point list.
+    if (n <= HOUGH_SMALL_N) {
+        const int rs = (int)((72 * 1024) / row_bytes) - 2;
+        if (rs >= 1) { rb = rs < rb ? rs : rb; threads = HOUGH_THREADS < 512 ? HOUGH_THREADS : 512; }
     }
-    {
-        TimeScope ts(ctx, "hough_vote");
-        const size_t row_bytes = (size_t)((stride + 1) / 2) * 4;           // 16-bit counters, two per dword
-        int rb = (int)((144 * 1024) / row_bytes) - 2;                      // inner rows per workgroup (+ 2 halo rows)
-        if (rb > 10) rb = 10;
-        if (rb < 1) return ck_fail(ctx, CK_ERR_ARG, "image too large for the Hough LDS slab");
-        int threads = HOUGH_THREADS;
-        // A call of a few frames (the hold-off-aware fold's windows, a live finder's single frame) is a latency matter, and
-        // next to the classifier -- two workgroups of 79 KB on every CU -- a workgroup that wants a whole CU's LDS waits until
-        // that kernel's grid drains: 1.5 ms of a 16-frame call's 3.0 (tools/board_call_latency.py).  Small batches take
-        // slabs that fit the hole ONE retiring classifier workgroup leaves (<= 72 KB, 512 threads): same peaks (rows with
-        // their halo, sorted on the host), more workgroups re-reading the point list.
-        if (n <= HOUGH_SMALL_N) {
-            const int rs = (int)((72 * 1024) / row_bytes) - 2;
-            if (rs >= 1) { rb = rs < rb ? rs : rb; threads = HOUGH_THREADS < 512 ? HOUGH_THREADS : 512; }
+    // the ghost's point list holds pc points per frame; ghost_list_kernel counts every point, also past pc
+    auto launch_ghost_hough = [&](int pc) -> int {
+        CK_TRY(ck_ensure(ctx, ctx->peaks, (size_t)n * PEAK_CAP * 8 + (size_t)n * pc * 4));
+        int32_t* d_peaks = (int32_t*)ctx->peaks.p;
+        uint32_t* d_hpts = (uint32_t*)(d_peaks + (size_t)n * PEAK_CAP * 2);
+        {
+            TimeScope ts(ctx, "ghost");
+            hipLaunchKernelGGL(ghost_list_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, (const int32_t*)compid,
+                               (const int32_t*)d_sel, d_tab, (const int32_t*)blist, pc, d_hpts, d_ghost_out);
+            CK_HIP(ctx, hipGetLastError());
         }
-        CK_HIP(ctx, hipFuncSetAttribute((const void*)hough_vote_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(144 * 1024)));
-        hipLaunchKernelGGL(hough_vote_peaks_kernel, dim3((NUMANGLE + rb - 1) / rb, n), dim3(threads), (rb + 2) * row_bytes, ctx->stream,
-                           (const uint32_t*)d_hpts, d_tab, pcap, (const float*)d_trig, numrho, rb, hough_thresh, d_peaks);
-        CK_HIP(ctx, hipGetLastError());
-    }
+        {
+            TimeScope ts(ctx, "hough_vote");
+            CK_HIP(ctx, hipFuncSetAttribute((const void*)hough_vote_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)(144 * 1024)));
+            hipLaunchKernelGGL(hough_vote_peaks_kernel, dim3((NUMANGLE + rb - 1) / rb, n), dim3(threads), (rb + 2) * row_bytes, ctx->stream,
+                               (const uint32_t*)d_hpts, d_tab, pc, (const float*)d_trig, numrho, rb, hough_thresh, d_peaks);
+            CK_HIP(ctx, hipGetLastError());
+        }
+        CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CK_OK;
+    };
+    CK_HIP(ctx, hipMemcpyAsync(d_sel, sel.data(), sel_bytes, hipMemcpyHostToDevice, ctx->stream));
+    CK_HIP(ctx, hipMemcpyAsync(d_trig, trig.data(), trig.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    CK_TRY(launch_ghost_hough(pcap));
     lap("ghost+hough");
-    CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // A ghost with more points than the list holds (a comb of 1-px teeth is all outer border): the whole call again with
+    // the list sized by the largest count, as the labelling falls back to its dense form.  overflow also marks more than
+    // PEAK_CAP peaks; only n_hough_pts > pcap tells the point list's overflow apart.
+    int pts_max = 0;
+    for (int f = 0; f < n; f++) pts_max = std::max(pts_max, tab[f].n_hough_pts);
+    if (pts_max > pcap) {
+        for (int f = 0; f < n; f++) tab[f].n_hough_pts = tab[f].n_peaks = tab[f].overflow = 0;
+        CK_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+        CK_TRY(launch_ghost_hough(pts_max));
+        lap("ghost+hough again");
+    }
     int np_max = 0;
     for (int f = 0; f < n; f++) {
-        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: Hough point/peak capacity exceeded", f);
+        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: more than %d Hough peaks", f, PEAK_CAP);
         if (res[f].status == CK_BOARD_LINES) np_max = std::max(np_max, tab[f].n_peaks);
     }
     if (!np_max) return CK_OK;
@@ -1459,7 +1475,7 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
         const size_t cnt = (size_t)n * np_max;
         CK_TRY(ck_ensure(ctx, ctx->pts, cnt * 8 + 64));
         hipLaunchKernelGGL(pack_peaks_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const int32_t*)d_peaks, np_max, n, (int32_t*)ctx->pts.p);
+                           (const int32_t*)ctx->peaks.p, np_max, n, (int32_t*)ctx->pts.p);
         CK_HIP(ctx, hipMemcpyAsync(pk.data(), ctx->pts.p, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     CK_HIP(ctx, hipStreamSynchronize(ctx->stream));

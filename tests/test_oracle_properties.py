@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 from scipy import ndimage
 
+from tests.board_ref import _hough_naive, _min_area_brute
+
 
 def _rand_img(rng, h, w, cn=3, smooth=True):
     img = rng.integers(0, 256, (h, w, cn), dtype=np.uint8)
@@ -163,25 +165,6 @@ def test_suzuki_edge_cases(ora):
 
 
 # ---------------------------------------------------------------- K4 minAreaRect / top-3
-def _min_area_brute(pts):
-    pts = np.unique(np.asarray(pts, np.float64), axis=0)
-    if len(pts) < 3:
-        return 0.0
-    from scipy.spatial import ConvexHull, QhullError
-    try:
-        hull = pts[ConvexHull(pts).vertices]
-    except QhullError:
-        return 0.0
-    best = np.inf
-    for i in range(len(hull)):
-        d = hull[(i + 1) % len(hull)] - hull[i]
-        d /= np.linalg.norm(d)
-        nrm = np.array([-d[1], d[0]])
-        u, v = hull @ d, hull @ nrm
-        best = min(best, (u.max() - u.min()) * (v.max() - v.min()))
-    return best
-
-
 def test_min_area_rect(ora):
     w, h = ora.min_area_rect([[0, 0], [10, 0], [10, 4], [0, 4], [5, 2]])
     assert sorted((w, h)) == [4.0, 10.0]
@@ -214,35 +197,6 @@ def test_top3_is_insort_order(ora):
 
 
 # ---------------------------------------------------------------- K6 hough
-def _hough_naive(img, thr):
-    h, w = img.shape
-    theta = np.float32(math.pi / 180)
-    numangle, numrho = 180, 2 * (w + h) + 1
-    ang = np.float32(0)
-    ts, tc = [], []
-    for _ in range(numangle):
-        ts.append(np.float32(math.sin(float(ang))))
-        tc.append(np.float32(math.cos(float(ang))))
-        ang = np.float32(ang + theta)
-    ts, tc = np.array(ts, np.float32), np.array(tc, np.float32)
-    acc = np.zeros((numangle + 2, numrho + 2), np.int32)
-    ys, xs = np.nonzero(img)
-    for y, x in zip(ys, xs):
-        v = (np.float32(x) * tc + np.float32(y) * ts).astype(np.float32)
-        r = np.rint(v.astype(np.float64)).astype(np.int64) + (numrho - 1) // 2
-        acc[np.arange(1, numangle + 1), r + 1] += 1
-    peaks = []
-    for r in range(numrho):
-        for n in range(numangle):
-            a = acc[n + 1, r + 1]
-            if a > thr and a > acc[n + 1, r] and a >= acc[n + 1, r + 2] and a > acc[n, r + 1] and a >= acc[n + 2, r + 1]:
-                peaks.append((-int(a), (n + 1) * (numrho + 2) + r + 1, r, n))
-    peaks.sort()
-    lines = [((np.float32(r) - np.float32(numrho - 1) * np.float32(0.5)), np.float32(0) + np.float32(n) * theta)
-             for _, _, r, n in peaks]
-    return np.array(lines, np.float32).reshape(-1, 2), acc
-
-
 def test_hough_vs_naive(ora):
     img = np.zeros((60, 80), np.uint8)
     img[10, 5:70] = 255

@@ -30,7 +30,7 @@ EXPORTS = [
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
     "ck_board_detect_records", "ck_cnn_regions_records",
-    "ck_contour_stones", "ck_contours_external", "ck_find_intersections", "ck_update_grid",
+    "ck_contour_stones", "ck_cluster_stones", "ck_rng_get", "ck_rng_set", "ck_contours_external", "ck_find_intersections", "ck_update_grid",
     "ck_ordered_hull", "ck_boardfold_create", "ck_boardfold_destroy", "ck_boardfold_reset", "ck_boardfold_step", "ck_boardfold_run", "ck_round10", "ck_round10_reference",
     "ck_policy_create", "ck_policy_destroy", "ck_policy_run", "ck_policy_run_records", "ck_policy_get_state", "ck_policy_set_state",
     "ck_policy_watch",
@@ -112,6 +112,10 @@ def lib():
         L.ck_policy_get_state.argtypes = [C.c_void_p] * 6
         L.ck_policy_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ck_policy_watch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_longlong]
+        L.ck_cluster_stones.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int] + [C.c_void_p] * 5 + [C.c_longlong] + [C.c_void_p] * 3)
+        L.ck_rng_get.argtypes = [C.c_void_p, C.c_void_p]
+        L.ck_rng_set.argtypes = [C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -539,6 +543,70 @@ class Context:
         if single:
             return (stones[0], zones[0], mask[0]) if want_all else stones[0]
         return (stones, zones, mask) if want_all else stones
+
+    def cluster_stones(self, goban, rects, mask, jobs=None, rs=0, re=19, cs=0, ce=19, want_all=False):
+        """SfClustering.find_stones (stone/sf_clustering.py:48-168) for a list of jobs in one call (ck_cluster_stones).
+        goban: one image (side, side, 3) or a batch (n, side, side, 3), uint8 or float32, host or device; rects: the
+        (19, 19, 4) getrect table; mask: (side, side) StonesFinder.getmask(); jobs: (m, 5) rows of (image, rs, re, cs, ce) --
+        None: one job per image over rows [rs, re) x columns [cs, ce).
+        -> stones uint8 (m, 19, 19) of 0 E / 1 B / 2 W, trusted bool (m,) -- for one image and jobs=None: (19, 19) and a bool.
+        want_all: also a dict of ratios (m, 19, 19, 3), centers (m, 3, 3), labels (list of (hs, ws) uint8 arrays), passes
+        (m, 3), compactness (m, 3), winner (m,).  Each job draws 21 numbers from the context's generator (`rng_state`)."""
+        single = len(goban.shape) == 3
+        n = 1 if single else int(goban.shape[0])
+        side = int(goban.shape[-2])
+        if tuple(goban.shape[-3:]) != (side, side, 3):
+            raise ValueError("goban %r: expected (.., s, s, 3)" % (tuple(goban.shape),))
+        is_f32 = "float32" in str(goban.dtype)
+        if not is_f32 and "uint8" not in str(goban.dtype):
+            raise ValueError("goban images are uint8 or float32, not %s" % goban.dtype)
+        rects = np.ascontiguousarray(rects, np.int32).reshape(19, 19, 4)
+        mask = np.ascontiguousarray(mask, np.uint8)
+        if mask.shape != (side, side):
+            raise ValueError("mask %r: expected (%d, %d)" % (mask.shape, side, side))
+        plain = jobs is None
+        if plain:
+            jobs = [(f, rs, re, cs, ce) for f in range(n)]
+        jobs = np.ascontiguousarray(jobs, np.int32).reshape(-1, 5)
+        m = len(jobs)
+        p, sp, keep = self._in(goban, np.float32 if is_f32 else np.uint8)
+        stones = np.zeros((m, 19, 19), np.uint8)
+        trusted = np.zeros(m, np.uint8)
+        extra, ptrs, cap = {}, [None] * 3 + [0] + [None] * 3, 0
+        if want_all:
+            views = []
+            for f, a, b, c, d in jobs:                  # (a bad job is refused by the library; sizes here only bound the buffer)
+                ok = 0 <= a < b <= 19 and 0 <= c < d <= 19
+                views.append((max(int(rects[b - 1, d - 1, 2] - rects[a, c, 0]), 0), max(int(rects[b - 1, d - 1, 3] - rects[a, c, 1]), 0)) if ok else (0, 0))
+            cap = sum(h * w for h, w in views)
+            extra = dict(ratios=np.zeros((m, 19, 19, 3), np.uint8), centers=np.zeros((m, 3, 3), np.float32),
+                         labels=np.zeros(max(cap, 1), np.uint8), passes=np.zeros((m, 3), np.int32),
+                         compactness=np.zeros((m, 3), np.float64), winner=np.zeros(m, np.int32))
+            ptrs = [extra[k].ctypes.data_as(C.c_void_p) for k in ("ratios", "centers", "labels")] + [cap] + \
+                   [extra[k].ctypes.data_as(C.c_void_p) for k in ("passes", "compactness", "winner")]
+        self._chk(lib().ck_cluster_stones(self._h, p, n, side, int(is_f32), sp, rects.ctypes.data_as(C.c_void_p),
+                                          mask.ctypes.data_as(C.c_void_p), jobs.ctypes.data_as(C.c_void_p), m,
+                                          stones.ctypes.data_as(C.c_void_p), trusted.ctypes.data_as(C.c_void_p), *ptrs))
+        trusted = trusted.astype(bool)
+        if want_all:
+            flat, off, extra["labels"] = extra["labels"], 0, []
+            for h, w in views:
+                extra["labels"].append(flat[off:off + h * w].reshape(h, w))
+                off += h * w
+        if single and plain:
+            stones, trusted = stones[0], bool(trusted[0])
+        return (stones, trusted, extra) if want_all else (stones, trusted)
+
+    @property
+    def rng_state(self):
+        """the cv::RNG state the context's k-means draws from (64 bits; a fresh context holds 0xffffffff)"""
+        v = C.c_uint64(0)
+        self._chk(lib().ck_rng_get(self._h, C.byref(v)))
+        return int(v.value)
+
+    @rng_state.setter
+    def rng_state(self, state):
+        self._chk(lib().ck_rng_set(self._h, C.c_uint64(int(state) & 0xffffffffffffffff)))
 
     def contours_external(self, edges, want_points=False):
         """cv2.findContours(edges, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) as SfContours reads it: for one (h, w) edge map or a

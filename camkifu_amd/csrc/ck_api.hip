@@ -841,6 +841,41 @@ int ck_contour_stones(ck_ctx* ctx, const uint8_t* goban, const uint8_t* fg, int 
     CK_API_END(ctx)
 }
 
+int ck_cluster_stones(ck_ctx* ctx, const void* goban, int n, int side, int is_f32, int in_space, const int32_t* rects,
+                      const uint8_t* mask, const int32_t* jobs, int m, uint8_t* stones, uint8_t* trusted, uint8_t* ratios,
+                      float* centers, uint8_t* labels, long long labels_cap, int32_t* passes, double* compactness, int32_t* winner)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    if (!goban || !rects || !mask || !jobs || !stones || !trusted || n <= 0 || m <= 0)
+        return ck_fail(ctx, CK_ERR_ARG, "NULL argument, n <= 0 or no job");
+    if (side < 19 * 4 || side > 4096) return ck_fail(ctx, CK_ERR_ARG, "goban image side %d", side);
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    const void* d_img;
+    CK_TRY(ck_to_device(ctx, goban, (size_t)n * side * side * 3 * (is_f32 ? 4 : 1), in_space, ctx->in_stage, &d_img));
+    CK_TRY(k_cluster_stones(ctx, d_img, n, side, is_f32 != 0, rects, mask, jobs, m, stones, trusted, ratios, centers, labels,
+                            labels_cap, passes, compactness, winner));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_rng_get(ck_ctx* ctx, uint64_t* state)
+{
+    CK_API_BEGIN(ctx)
+    if (!state) return ck_fail(ctx, CK_ERR_ARG, "state is NULL");
+    *state = ctx->rng_state;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_rng_set(ck_ctx* ctx, uint64_t state)
+{
+    CK_API_BEGIN(ctx)
+    ctx->rng_state = state;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
 int ck_contours_external(ck_ctx* ctx, const uint8_t* edges, int n, int h, int w, int in_space,
                          int32_t* counts, int32_t* table, int table_cap, int32_t* points, int points_cap)
 {

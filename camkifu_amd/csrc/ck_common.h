@@ -116,6 +116,7 @@ struct ck_ctx {
     int cnn_fallbacks = 0;           // batches the split-precision mode handed back to the f32 kernels
     int cnn_mode = CK_CNN_F16X2;     // f32-accurate and 2.3x faster than the k-ordered f32 chain (CK_CNN_FP32)
     std::vector<Mog2State> mog2;
+    uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 };
 
 extern thread_local std::string g_ck_create_error;
@@ -237,6 +238,10 @@ int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, s
 int ck_goban_canny_dev(ck_ctx* ctx, const uint8_t* d_in, int n, int h, int w, uint8_t* d_edges, double* otsu_out);   // ck_api.hip
 int k_contour_stones(ck_ctx* ctx, const uint8_t* d_goban, const uint8_t* d_fg, int n, int side, const int32_t* rects,
                      int rs, int re, int cs, int ce, uint8_t* stones, int16_t* zones_out, uint8_t* mask_out);
+// SfClustering.find_stones for m jobs (k_cluster.hip); draws 21 numbers per job from ctx->rng_state
+int k_cluster_stones(ck_ctx* ctx, const void* d_imgs, int n, int side, int is_f32, const int32_t* rects, const uint8_t* mask,
+                     const int32_t* jobs, int m, uint8_t* stones, uint8_t* trusted, uint8_t* ratios, float* centers,
+                     uint8_t* labels, long long labels_cap, int32_t* passes, double* compact, int32_t* winner);
 double ck_otsu_level(const int* hist, size_t npx);                        // ck_api.hip: getThreshVal_Otsu_8u restated
 // StonesFinder.find_intersections, device half: Canny of the grey image + HoughLinesP of the 361 zones -> host tables
 // (*lines_out / *nlines_out point into the context's pinned host arena: valid until the next call on this context)

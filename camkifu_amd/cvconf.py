@@ -15,6 +15,8 @@ bfinders = [
 sfinders = [
     ("camkifu_amd.stone.sf_neural", "SfNeural"),
     ("camkifu_amd.stone.sf_contours", "SfContours"),
+    ("camkifu_amd.stone.sf_meta", "SfMeta"),
+    ("camkifu_amd.stone.sf_clustering", "SfClustering"),
     ("None", "None"),
 ]
 bf_loc = None

@@ -349,6 +349,30 @@ class StonesFinder(VidProcessor):
             raise TypeError("cursor must be a float in ]0, 2[")
         return tuple(int(v) for v in self._posgrid.zones(cursor)[r, c])
 
+    def stone_radius(self):
+        """radius of a stone in the canonical image, in pixels (stonesfinder.py:578-584)"""
+        return self._posgrid.size / gsize / 2
+
+    def getmask(self, depth=1):
+        """a disc around every intersection (stonesfinder.py:452-490): (side, side) uint8 of 0 / 1 -- (side, side, depth)
+        for depth > 1 -- built from the zone table and kept until that table or `depth` changes.  Each zone holds the disc
+        of radius min(h, w) / 2 about its centre; zones are written in raster order; pixels no zone covers are 0 (the
+        reference leaves them uninitialised, and never reads them)."""
+        zones = self._posgrid.zones(1.0)
+        key = (zones.tobytes(), int(depth))
+        cached = getattr(self, "_mask_cache", None)
+        if cached is None or cached[0] != key:
+            side = self._posgrid.size
+            flat = np.zeros((side, side), np.uint8)
+            for x0, y0, x1, y1 in zones.reshape(-1, 4):
+                h, w = flat[x0:x1, y0:y1].shape
+                dy = np.arange(h)[:, None] - h / 2
+                dx = np.arange(w)[None, :] - w / 2
+                flat[x0:x1, y0:y1] = dx * dx + dy * dy <= min(h / 2, w / 2) ** 2
+            mask = flat if depth <= 1 else np.repeat(flat[:, :, None], depth, axis=2)
+            cached = self._mask_cache = (key, mask)
+        return cached[1]
+
     def _window_name(self):
         return "camkifu.stone.stonesfinder.StonesFinder"
 

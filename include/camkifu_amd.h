@@ -239,6 +239,25 @@ int ck_zone_counts(ck_ctx* ctx, const uint8_t* mask, int n, int in_space, int32_
 int ck_contour_stones(ck_ctx* ctx, const uint8_t* goban, const uint8_t* fg, int n, int side, int in_space, const int32_t* rects,
                       int rs, int re, int cs, int ce, uint8_t* stones, int16_t* zones, uint8_t* mask);
 
+/* ---- SfClustering.find_stones for m jobs in one call                               stone/sf_clustering.py:48-168
+ * A job is one region of one goban image: jobs = m x 5 int32 on the HOST (image index, rs, re, cs, ce), rows [rs, re) and
+ * columns [cs, ce) of the intersections.  Per job: cv2.kmeans(pixels of the region's view, 3, None, (EPS, 15, 3), 3,
+ * KMEANS_PP_CENTERS), the labels under the circle mask counted per zone, interpret_ratios, check_density.
+ * goban: n x side x side x 3 in `in_space`, uint8 (is_f32 = 0) or float32 (is_f32 = 1: what SfClustering._find accumulates).
+ * rects: HOST, the 19*19*4 getrect table as for ck_contour_stones; mask: HOST, side x side bytes, StonesFinder.getmask().
+ * Outputs on the HOST, one row per job: stones 361 (0 E, 1 B, 2 W; E outside the region), trusted 1 (check_density; 0 also
+ * where the compactness is 0 -- the reference fails there -- and the stones are then all E); nullable: ratios 361*3,
+ * centers 9 floats (winning attempt, cluster order), labels (the winning attempt's label per pixel of the view, job after
+ * job, labels_cap bytes available), passes 3 and compactness 3 (per attempt), winner 1 (the attempt kept).
+ * Random numbers: the context holds a cv::RNG state (initially 0xffffffff, the library's default seed); a job draws 21
+ * numbers, job j of a call starts 21 * j draws in, and the call leaves the state advanced by 21 * m.
+ * CK_ERR_ARG: empty or out-of-range region, a view outside the image, a zone outside its view, fewer than 3 pixels. */
+int ck_cluster_stones(ck_ctx* ctx, const void* goban, int n, int side, int is_f32, int in_space, const int32_t* rects,
+                      const uint8_t* mask, const int32_t* jobs, int m, uint8_t* stones, uint8_t* trusted, uint8_t* ratios,
+                      float* centers, uint8_t* labels, long long labels_cap, int32_t* passes, double* compactness, int32_t* winner);
+int ck_rng_get(ck_ctx* ctx, uint64_t* state);
+int ck_rng_set(ck_ctx* ctx, uint64_t state);
+
 /* ---- cv2.findContours(edges, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) as SfContours reads it   stone/sf_contours.py:82, 266
  * For n edge maps (h x w, non-zero = edge): counts[f] = contours of map f; table: one row of 4 int32 per contour, map after
  * map, each map's contours in the order cv2 returns them (last found first): x, y of the contour's first point, the

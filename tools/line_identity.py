@@ -18,6 +18,10 @@ PAIRS = [
     ("camkifu_amd/stone/stonesfinder.py", "stone/stonesfinder.py"),
     ("camkifu_amd/stone/sf_neural.py", "stone/sf_neural.py"),
     ("camkifu_amd/stone/sf_contours.py", "stone/sf_contours.py"),
+    ("camkifu_amd/stone/sf_clustering.py", "stone/sf_clustering.py"),
+    ("camkifu_amd/stone/sf_meta.py", "stone/sf_meta.py"),
+    ("camkifu_amd/core/imgutil.py", "core/imgutil.py"),
+    ("tests/cluster_ref.py", "stone/sf_clustering.py"),
     ("camkifu_amd/stone/nn_manager.py", "stone/nn_manager.py"),
     ("camkifu_amd/stone/nn_cache.py", "stone/nn_cache.py"),
     ("camkifu_amd/stone/policy.py", "stone/sf_neural.py"),

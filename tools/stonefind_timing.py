@@ -2,7 +2,11 @@
 """Timing of SURVEY 8f rank 3 on goban images resident in HBM: ck_contour_stones (SfContours.find_stones) and
 ck_find_intersections (StonesFinder.find_intersections) -- images/s at a few batch sizes, HIP-event time per stage,
 the CPU oracle beside them, and (CK_PROFILE_HOST=1) the host laps of ck_contour_stones on stderr.
-    python tools/stonefind_timing.py [--n 256] [--reps 5] [--cpu 2]"""
+    python tools/stonefind_timing.py [--n 256] [--reps 5] [--cpu 2]
+--leg cluster: ck_cluster_stones (SfClustering.find_stones) instead -- regions/s of a 9-job call (what SfMeta issues per frame)
+and of an n-image x 9-region call, the kernel's HIP-event time, passes per attempt, and the plain numpy reference
+(tests/cluster_ref.py) on the same jobs.
+    python tools/stonefind_timing.py --leg cluster [--n 256] [--reps 5] [--cpu 9]"""
 import argparse
 import json
 import os
@@ -14,12 +18,62 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def cluster_leg(args):
+    import torch
+    from camkifu_amd import capi, synth
+    from camkifu_amd.stone.stonesfinder import PosGrid
+    from tests import cluster_ref as cr
+    ctx = capi.Context(0)
+    n = args.n
+    dst = np.array([(0, 0), (380, 0), (380, 380), (0, 380)], np.float32)
+    rng = np.random.default_rng(synth.SEED)
+    gobans = torch.stack([synth.render(380, 380, synth.random_stones(rng, 0.15 + 0.5 * (f % 8) / 8), dst, seed=synth.SEED + f, device="cuda")
+                          for f in range(n)])
+    rects = np.ascontiguousarray(PosGrid(380).zones(1.0), np.int32)
+    mask = cr.circle_mask(rects, 380)
+    nine = [(a, b, c, d) for a, b in ((0, 6), (6, 12), (12, 19)) for c, d in ((0, 6), (6, 12), (12, 19))]
+    out = {}
+    for label, imgs in (("one_image_9_jobs", gobans[:1].contiguous()), ("batch_%d_x_9_jobs" % n, gobans)):
+        jobs = np.array([(f,) + reg for f in range(len(imgs)) for reg in nine], np.int32)
+        ctx.cluster_stones(imgs, rects, mask, jobs=jobs)
+        t = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            ctx.cluster_stones(imgs, rects, mask, jobs=jobs)
+            t.append(time.perf_counter() - t0)
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        ctx.rng_state = 0xffffffff
+        stones, trusted, extra = ctx.cluster_stones(imgs, rects, mask, jobs=jobs, want_all=True)
+        ms, launches = ctx.timing_get("cluster")
+        ctx.timing_enable(False)
+        out[label] = dict(regions_per_s=round(len(jobs) / float(np.median(t)), 1), ms_per_call=round(1e3 * float(np.median(t)), 3),
+                          kernel_ms=round(ms, 3), kernel_us_per_region=round(1e3 * ms / len(jobs), 2), launches=launches,
+                          passes_per_attempt=dict(mean=round(float(extra["passes"].mean()), 2), max=int(extra["passes"].max())),
+                          trusted=int(trusted.sum()))
+    if args.cpu:
+        k = min(args.cpu, 9 * n)
+        host = gobans[:(k + 8) // 9].cpu().numpy()
+        jobs = np.array([(f,) + reg for f in range(len(host)) for reg in nine], np.int32)[:k]
+        ctx.rng_state = 0xffffffff
+        stones, trusted = ctx.cluster_stones(host, rects, mask, jobs=jobs)
+        t0 = time.perf_counter()
+        ref = [cr.find_stones(host[f], rects, mask, a, b, c, d, rng=cr.RNG(cr.RNG().advanced(21 * j))) for j, (f, a, b, c, d) in enumerate(jobs)]
+        out["cpu_reference"] = dict(regions_per_s=round(k / (time.perf_counter() - t0), 1), kind="numpy restatement, one core",
+                                    equal=bool(all(np.array_equal(r["stones"], s) for r, s in zip(ref, stones))))
+    print(json.dumps({"cluster_stones": out}))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("contour", "cluster"), default="contour")
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu", type=int, default=2, help="images timed on the CPU oracle (0: skip)")
     args = ap.parse_args()
+    if args.leg == "cluster":
+        return cluster_leg(args)
     import torch
     from camkifu_amd import capi, synth
     from camkifu_amd.stone.stonesfinder import PosGrid

@@ -300,7 +300,10 @@ __attribute__((amdgpu_waves_per_eu(3))) __global__ __launch_bounds__(64) void me
     int lo_bound = 0, hi_bound = 255;       // lo_bound <= every median of the tile <= hi_bound (-> range)
     MED_COUNT(0, 1);
     {
-        // 4 samples per lane: rows 16 g + {1, 6, 9, 14} of columns n, 16 + n, 32 + n, 48 + n (inverted bytes)
+        // 4 samples per lane (inverted bytes).  In frame terms, relative to the tile's first input pixel (oy - K/2, ox - K/2):
+        // lane (n, g) takes input rows n, 16 + n, 32 + n, 48 + n at columns 16 g + 1, 16 g + 6, 16 g + 9, 16 g + 14 -- input row r
+        // is sampled at columns 16 g + {1, 6, 9, 14}[r / 16], g = 0..3: 256 pixels, 4 in each of the 64 rows, 16 in each of
+        // 16 columns.  (In the transposed tile the kernel works on, those are rows 16 g + {1, 6, 9, 14} of columns n, 16 + n, ..)
         const uint32_t s0 = ((uint32_t)nx[0][0] >> 8) & 0xFFu, s1 = ((uint32_t)nx[1][1] >> 16) & 0xFFu;
         const uint32_t s2 = ((uint32_t)nx[2][2] >> 8) & 0xFFu, s3 = ((uint32_t)nx[3][3] >> 16) & 0xFFu;
         uint32_t lo = s0 < s1 ? s0 : s1, hi = s0 < s1 ? s1 : s0;

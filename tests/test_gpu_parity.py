@@ -44,11 +44,16 @@ def test_median_random_shapes(ck, ora, shape):
 
 def test_median_interior_tiles_worst_case(ck, ora):
     """pure noise (up to 255 thresholds per tile) on a frame large enough to hold interior 48x48 tiles (the
-    scalar-base load / store path of the matrix-core kernel) next to border tiles, odd width"""
+    scalar-base load / store path of the matrix-core kernel) next to border tiles, odd width.  The 80 x 90 patch is smaller
+    than the 64 x 64 input of any tile at its place (tiles start at multiples of 48, 7 pixels early), so every tile's samples
+    still see noise and take the radix descent; the larger patch covers the whole input of tile (1, 1), rows and columns
+    41 .. 104, which then scans instead.  (tests/test_gpu_filters.py runs the scan's branches one by one.)"""
     rng = np.random.default_rng(4848)
     img = rng.integers(0, 256, (170, 203, 3), dtype=np.uint8)
     assert np.array_equal(ck.median15(img), ora.median(img, 15))
     img[40:120, 60:150] = rng.integers(100, 104, (80, 90, 3), dtype=np.uint8)      # a nearly flat patch inside
+    assert np.array_equal(ck.median15(img), ora.median(img, 15))
+    img[36:112, 36:112] = rng.integers(100, 104, (76, 76, 3), dtype=np.uint8)      # a flat interior tile inside noise
     assert np.array_equal(ck.median15(img), ora.median(img, 15))
 
 

@@ -25,7 +25,7 @@ EXPORTS = [
     "ck_ctx_create", "ck_ctx_create_prio", "ck_ctx_destroy", "ck_ctx_destroy2", "ck_stream_wait", "ck_last_error", "ck_backend", "ck_version", "ck_stream",
     "ck_timing_enable", "ck_timing_reset", "ck_timing_get",
     "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
-    "ck_i420_to_bgr", "ck_get_perspective_transform", "ck_warp_perspective",
+    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_get_perspective_transform", "ck_warp_perspective",
     "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
@@ -122,6 +122,19 @@ def lib():
 
 def _is_torch(a):
     return type(a).__module__.startswith("torch")
+
+
+def pyr_shape(h, w, levels):
+    """(h, w) of the frames after `levels` applications of pyrDown: each side becomes (side + 1) // 2.  CkError, as from the
+    library, for levels < 0 and for a level that would read an image with a side below 2."""
+    h, w, levels = int(h), int(w), int(levels)
+    if levels < 0:
+        raise CkError("pyramid levels %d: negative" % levels)
+    for l in range(levels):
+        if h < 2 or w < 2:
+            raise CkError("pyramid level %d would take a %dx%d image: sides below 2" % (l + 1, w, h))
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return h, w
 
 
 def _in(a, dtype=np.uint8):
@@ -341,16 +354,22 @@ class Context:
         return rec
 
     # ---- frame source ------------------------------------------------------------------------
-    def i420_to_bgr(self, i420, h, w, to_device=None, out=None):
+    def i420_to_bgr(self, i420, h, w, to_device=None, out=None, levels=0):
         """planar YUV 4:2:0 frames (n, h*w*3/2) or one flat frame -> BGR (n, h, w, 3) / (h, w, 3).
         `to_device`: a torch device to leave the BGR frames in HBM even when the I420 bytes come from host memory (the
-        fast-file path uploads 1.5 B/px and converts on the GPU); `out`: a preallocated BGR tensor / array to fill."""
+        fast-file path uploads 1.5 B/px and converts on the GPU); `out`: a preallocated BGR tensor / array to fill.
+        `levels` > 0: the frames come out pyrDown-ed that many times, of shape pyr_shape(h, w, levels) -- bit for bit
+        pyr_down(i420_to_bgr(..), levels), but the full-size BGR frames are never written (ck_i420_to_bgr_pyr)."""
         fsz = h * w * 3 // 2
         single = len(i420.shape) == 1
         n = 1 if single else int(i420.shape[0])
         assert int(i420.shape[-1]) == fsz, (tuple(i420.shape), fsz)
+        levels = int(levels)
+        if levels and ((h | w) & 1):
+            raise CkError("I420 needs even dimensions, got %dx%d" % (w, h))
+        oh, ow = pyr_shape(h, w, levels)
         p, sp, keep = self._in(i420)
-        oshape = (h, w, 3) if single else (n, h, w, 3)
+        oshape = (oh, ow, 3) if single else (n, oh, ow, 3)
         if out is not None:
             assert tuple(out.shape) == oshape
             op, osp, _ = self._in(out)
@@ -358,7 +377,28 @@ class Context:
             out, op, osp = self._out_on(to_device, oshape, np.uint8)
         else:
             out, op, osp = self._out(i420, oshape, np.uint8)
-        self._chk(lib().ck_i420_to_bgr(self._h, p, n, int(h), int(w), sp, op, osp))
+        if levels:
+            self._chk(lib().ck_i420_to_bgr_pyr(self._h, p, n, int(h), int(w), levels, sp, op, osp))
+        else:
+            self._chk(lib().ck_i420_to_bgr(self._h, p, n, int(h), int(w), sp, op, osp))
+        return out
+
+    def pyr_down(self, frames, levels=1, out=None):
+        """cv2.pyrDown of BGR frames (n, h, w, 3) or one frame (h, w, 3), applied `levels` (>= 1) times -> frames of
+        pyr_shape(h, w, levels) in the memory space of the input; `out`: a preallocated array / tensor to fill."""
+        n, h, w = self._shape(frames, 3)
+        levels = int(levels)
+        if levels < 1:
+            raise CkError("pyramid levels %d: at least 1" % levels)
+        oh, ow = pyr_shape(h, w, levels)
+        p, sp, keep = self._in(frames)
+        oshape = (oh, ow, 3) if len(frames.shape) == 3 else (n, oh, ow, 3)
+        if out is None:
+            out, op, osp = self._out(frames, oshape, np.uint8)
+        else:
+            assert tuple(out.shape) == oshape and (out.is_contiguous() if _is_torch(out) else out.flags.c_contiguous)
+            op, osp, _ = self._in(out)
+        self._chk(lib().ck_pyr_down(self._h, p, n, h, w, levels, sp, op, osp))
         return out
 
     # ---- K8 ---------------------------------------------------------------------------------

@@ -9,10 +9,15 @@ uncompressed containers:
 
   Y4MCapture   .y4m (YUV4MPEG2, 4:2:0 planar): frames stay I420 on the host (1.5 B/px) and are
                converted to BGR on the GPU (ck_i420_to_bgr) -- read() for one frame,
-               read_raw_batch() for the fast-file pipeline
+               read_raw_batch() for the fast-file pipeline; with `levels` set, read() converts and
+               downsamples in one kernel (ck_i420_to_bgr_pyr)
   ArrayCapture an (n, h, w, 3) uint8 array or .npy file of BGR frames (memory mapped)
 
 cv2 property ids are kept so CaptureReaderBase.skip reads like the reference's.
+
+CaptureReaderBase.downsample(ret, img) is the reference's extension point of the same name
+(core/vmanager.py:484-498, 527-533): every frame passes through it before a finder sees it.  Its one
+documented use, cv2.pyrDown(img), is what `cvconf.downsample = N` switches on here (N levels, on the GPU).
 """
 import os
 import threading
@@ -104,11 +109,14 @@ def write_y4m(path, frames_i420, h, w, fps=(30, 1)):
 class Y4MCapture:
     """cv2.VideoCapture look-alike over a YUV4MPEG2 4:2:0 file.  The file is memory mapped; frames are
     handed out as I420 (read_raw / read_raw_batch, zero copy) or as BGR through `convert`, a callable
-    (i420_flat, h, w) -> (h, w, 3) BGR -- by default the GPU conversion of a camkifu_amd Context."""
+    (i420_flat, h, w) -> (h, w, 3) BGR -- by default the GPU conversion of a camkifu_amd Context.
+    `levels` > 0: read() hands out frames pyrDown-ed that many times, `convert` being called with levels=... (the
+    Context's fused conversion); get(CAP_PROP_FRAME_WIDTH / HEIGHT) keep reporting the file's size, as cv2 would."""
 
-    def __init__(self, path, convert=None):
+    def __init__(self, path, convert=None, levels=0):
         self.path = path
         self.convert = convert
+        self.levels = int(levels)
         self.pos = 0
         self._mm = None
         self._offsets = []
@@ -195,7 +203,10 @@ class Y4MCapture:
             from .. import capi
             convert = capi.get_context().i420_to_bgr
             self.convert = convert
-        return True, np.asarray(convert(np.ascontiguousarray(raw), self.h, self.w))
+        raw = np.ascontiguousarray(raw)
+        if self.levels:
+            return True, np.asarray(convert(raw, self.h, self.w, levels=self.levels))
+        return True, np.asarray(convert(raw, self.h, self.w))
 
     def get(self, prop):
         if prop == CAP_PROP_POS_FRAMES:
@@ -256,11 +267,13 @@ def file_frame_indices(nframes, fps, rate=None, start=0):
 class CaptureReaderBase:
     """What a manager puts between its finders and the capture: `read(caller)` is taken over, every other
     attribute is the capture's.  A video FILE is thinned to `fps` analysed frames per second of footage with
-    the reference's arithmetic (core/vmanager.py:510-525; see file_frame_indices); other sources pass through."""
+    the reference's arithmetic (core/vmanager.py:510-525; see file_frame_indices); other sources pass through.
+    Every frame read goes through `downsample(ret, img)` before it is handed out.
+    `ctx`: the Context that downsamples (default: the process-wide one)."""
 
-    def __init__(self, capture, vmanager, fps=None):
+    def __init__(self, capture, vmanager, fps=None, ctx=None):
         self.__dict__.update(capture=capture, vmanager=vmanager,
-                             frame_rate=cvconf.file_fps if fps is None else fps)
+                             frame_rate=cvconf.file_fps if fps is None else fps, ctx=ctx)
 
     def __getattr__(self, attr):                       # only reached for names this object does not define
         return getattr(self.__dict__["capture"], attr)
@@ -277,10 +290,34 @@ class CaptureReaderBase:
 
     skip = advance
 
+    def read_capture(self):
+        """capture.read() through the downsample hook.  A capture that downsamples while it converts (Y4MCapture's
+        `levels`) is told the configured level first, and the hook then leaves its frames alone."""
+        cap = self.capture
+        if hasattr(cap, "levels"):
+            cap.levels = int(cvconf.downsample or 0)
+        return self.downsample(*cap.read())
+
+    def downsample(self, ret, img):
+        """The reference's extension point (core/vmanager.py:527-533), with its one documented use built in:
+        `cvconf.downsample` = N > 0 hands every good frame out as N levels of cv2.pyrDown (ctx.pyr_down); 0 is the
+        identity.  A failed read and the `unsynced` marker pass through untouched.  A subclass may override it (and then
+        leaves cvconf.downsample at 0)."""
+        levels = int(cvconf.downsample or 0)
+        if not levels or not ret or img is None or isinstance(img, str):
+            return ret, img
+        if getattr(self.capture, "levels", 0) == levels:
+            return ret, img                            # the capture has downsampled already
+        ctx = self.ctx
+        if ctx is None:
+            from .. import capi
+            ctx = capi.get_context()
+        return ret, np.asarray(ctx.pyr_down(img, levels))
+
     def read(self, caller=None):
         if self.is_file():
             self.advance()
-        return self.capture.read()
+        return self.read_capture()
 
 
 class CaptureReader(CaptureReaderBase):
@@ -293,8 +330,8 @@ class CaptureReader(CaptureReaderBase):
     A consumer therefore sees every frame exactly once -- the reference's reader lets the thread served last
     walk away with the following frame (and sometimes see it twice), a timing artefact that is not mirrored."""
 
-    def __init__(self, capture, vmanager, fps=None):
-        super().__init__(capture, vmanager, fps)
+    def __init__(self, capture, vmanager, fps=None, ctx=None):
+        super().__init__(capture, vmanager, fps, ctx)
         self.__dict__.update(_cv=threading.Condition(), _gen=0, _frame=None, _taken={}, unsync=False,
                              sleep_time=0.05)
 
@@ -309,10 +346,10 @@ class CaptureReader(CaptureReaderBase):
         return ready
 
     def _fetch(self, first):
-        """under the lock: load the next generation"""
+        """under the lock: load the next generation (downsampled once, whatever the number of consumers)"""
         if not first:
             self.advance()
-        self._frame = self.capture.read()
+        self._frame = self.read_capture()
         self._gen += 1
         if not first:
             self.vmanager.vid_progress(self.capture.get(CAP_PROP_POS_AVI_RATIO) * 100)
@@ -324,7 +361,7 @@ class CaptureReader(CaptureReaderBase):
 
     def read(self, caller=None):
         if not self.is_file():
-            return self.capture.read()
+            return self.read_capture()
         with self._cv:
             if self._gen == 0:
                 self._fetch(first=True)

@@ -240,7 +240,7 @@ int ck_ctx_destroy2(ck_ctx* ctx)
                        &ctx->labels2, &ctx->runs, &ctx->ghost, &ctx->misc, &ctx->bflag, &ctx->comp, &ctx->lists, &ctx->pts, &ctx->accum, &ctx->peaks,
                        &ctx->goban, &ctx->act0, &ctx->act1, &ctx->act2, &ctx->ybuf, &ctx->lblbuf, &ctx->confbuf,
                        &ctx->rlblbuf, &ctx->rconfbuf, &ctx->fgcbuf,
-                       &ctx->out_stage, &ctx->mats, &ctx->rec_stage,
+                       &ctx->out_stage, &ctx->mats, &ctx->rec_stage, &ctx->pyr0, &ctx->pyr1,
                        &ctx->cnn.c1w, &ctx->cnn.c1b, &ctx->cnn.c2w, &ctx->cnn.c2b, &ctx->cnn.c3w, &ctx->cnn.c3b,
                        &ctx->cnn.c4w, &ctx->cnn.c4b, &ctx->cnn.d1w, &ctx->cnn.d1b, &ctx->cnn.d2w, &ctx->cnn.d2b,
                        &ctx->cnn.c2w_bf, &ctx->cnn.c3w_bf, &ctx->cnn.c4w_bf, &ctx->cnn.d1w_bf, &ctx->cnn.c1w_f16, &ctx->cnn.d1w_bfp, &ctx->cnn.c1w_q8, &ctx->cnn.c2x_q8, &ctx->cnn.c3x_q8, &ctx->cnn.c4x_q8, &ctx->cnn.d1w_h2,
@@ -497,6 +497,80 @@ int ck_i420_to_bgr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int in
     uint8_t* d_out = bgr;
     if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
     CK_TRY(k_i420_to_bgr(ctx, (const uint8_t*)d_in, n, h, w, d_out));
+    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, bgr, d_out, obytes, CK_HOST));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+// the argument rules of both pyramid entry points, checked before any device work
+static int check_pyr(ck_ctx* ctx, int h, int w, int levels)
+{
+    if (levels < 1) return ck_fail(ctx, CK_ERR_ARG, "pyramid levels %d: at least 1", levels);
+    for (int l = 0; l < levels; l++, h = (h + 1) / 2, w = (w + 1) / 2)
+        if (h < 2 || w < 2) return ck_fail(ctx, CK_ERR_ARG, "pyramid level %d would take a %dx%d image: sides below 2", l + 1, w, h);
+    return CK_OK;
+}
+
+// levels `first` .. `levels` of the pyramid of n frames (h x w is the size level `first` reads), the last one into d_out;
+// the levels between go through the context's ping-pong scratch
+static int pyr_levels(ck_ctx* ctx, const uint8_t* d_in, int n, int h, int w, int first, int levels, uint8_t* d_out)
+{
+    for (int l = first; l <= levels; l++) {
+        const int oh = (h + 1) / 2, ow = (w + 1) / 2;
+        uint8_t* d_to = d_out;
+        if (l < levels) {
+            DevBuf& b = (l & 1) ? ctx->pyr1 : ctx->pyr0;
+            CK_TRY(ck_ensure(ctx, b, (size_t)n * oh * ow * 3));
+            d_to = (uint8_t*)b.p;
+        }
+        CK_TRY(k_pyr_down(ctx, d_in, n, h, w, d_to));
+        d_in = d_to; h = oh; w = ow;
+    }
+    return CK_OK;
+}
+
+int ck_pyr_down(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int levels, int in_space, uint8_t* out, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    if (!bgr || !out) return ck_fail(ctx, CK_ERR_ARG, "image pointer is NULL");
+    if (n <= 0 || h <= 0 || w <= 0) return ck_fail(ctx, CK_ERR_ARG, "bad shape n=%d h=%d w=%d", n, h, w);
+    CK_TRY(check_pyr(ctx, h, w, levels));
+    CK_TRY(check_img(ctx, bgr, n, h, w));
+    const void* d_in;
+    CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
+    int oh = h, ow = w;
+    for (int l = 0; l < levels; l++) { oh = (oh + 1) / 2; ow = (ow + 1) / 2; }
+    const size_t obytes = (size_t)n * oh * ow * 3;
+    uint8_t* d_out = out;
+    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
+    CK_TRY(pyr_levels(ctx, (const uint8_t*)d_in, n, h, w, 1, levels, d_out));
+    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, out, d_out, obytes, CK_HOST));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_i420_to_bgr_pyr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int levels, int in_space, uint8_t* bgr, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    if (!i420 || !bgr) return ck_fail(ctx, CK_ERR_ARG, "image pointer is NULL");
+    if (n <= 0 || h <= 0 || w <= 0) return ck_fail(ctx, CK_ERR_ARG, "bad shape n=%d h=%d w=%d", n, h, w);
+    if ((h & 1) || (w & 1)) return ck_fail(ctx, CK_ERR_ARG, "I420 needs even dimensions, got %dx%d", w, h);
+    CK_TRY(check_pyr(ctx, h, w, levels));
+    CK_TRY(check_img(ctx, i420, n, h, w));
+    const void* d_in;
+    CK_TRY(ck_to_device(ctx, i420, (size_t)n * h * w * 3 / 2, in_space, ctx->in_stage2, &d_in));
+    int oh = h, ow = w;
+    for (int l = 0; l < levels; l++) { oh = (oh + 1) / 2; ow = (ow + 1) / 2; }
+    const size_t obytes = (size_t)n * oh * ow * 3;
+    uint8_t* d_out = bgr;
+    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
+    uint8_t* d_first = d_out;                       // level 1, fused behind the conversion
+    if (levels > 1) {
+        CK_TRY(ck_ensure(ctx, ctx->pyr1, (size_t)n * (h / 2) * (w / 2) * 3));
+        d_first = (uint8_t*)ctx->pyr1.p;
+    }
+    CK_TRY(k_i420_pyr_down(ctx, (const uint8_t*)d_in, n, h, w, d_first));
+    if (levels > 1) CK_TRY(pyr_levels(ctx, d_first, n, h / 2, w / 2, 2, levels, d_out));
     if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, bgr, d_out, obytes, CK_HOST));
     return finish(ctx);
     CK_API_END(ctx)

@@ -100,6 +100,7 @@ struct ck_ctx {
     DevBuf ybuf, lblbuf, confbuf, rlblbuf, rconfbuf, fgcbuf;
     DevBuf out_stage;
     DevBuf mats;
+    DevBuf pyr0, pyr1;   // pyramid levels between the first and the last (ping-pong)
     void* host_pinned = nullptr;
     size_t host_pinned_cap = 0;
     void* host_pinned2 = nullptr;    // second arena (contour survey) so that a caller's data in the first one survives
@@ -221,6 +222,10 @@ int k_canny_planar(ck_ctx* ctx, const uint8_t* d_planes, int n, int h, int w, in
                    const int* d_thr = nullptr /* per-frame (low, high) pairs on the device, override low / high */,
                    const uint8_t* d_range = nullptr /* value bounds of the planes' tiles, from k_median_planar */);
 int k_i420_to_bgr(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uint8_t* d_bgr);
+// cv2.pyrDown, one level: n x h x w x 3 -> n x (h+1)/2 x (w+1)/2 x 3 (h, w >= 2); and the same behind the I420 conversion
+// (h, w even): bit for bit k_pyr_down of k_i420_to_bgr without the full-size BGR frames (k_pyramid.hip)
+int k_pyr_down(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, uint8_t* d_out);
+int k_i420_pyr_down(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uint8_t* d_out);
 int k_warp(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, const double* d_minv, int m_count,
            int dsize, uint8_t* d_out);
 int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,

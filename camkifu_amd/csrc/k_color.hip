@@ -7,12 +7,12 @@
 // HBM-bound: reads 1.5 B/px, writes 3 B/px.  One thread = 4x2 pixels (two Y dwords, one U and
 // one V ushort, two 12-byte stores); a wave covers 256 x 2 pixels with contiguous 768-byte rows.
 #include "ck_common.h"
+#include "ck_i420.h"       // the conversion arithmetic (shared with k_pyramid.hip)
 
 namespace {
 
-constexpr int CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527, SHIFT = 20;
-
-__device__ __forceinline__ uint32_t sat8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+using ck_i420::i420_chroma;
+using ck_i420::i420_pixel;
 
 // converts PX horizontally adjacent pixels of rows y and y+1 starting at even column x
 template <int PX>
@@ -43,15 +43,7 @@ __device__ __forceinline__ void convert_block(const uint8_t* __restrict__ Y, con
         uint8_t o[PX * 3];
 #pragma unroll
         for (int k = 0; k < PX; k++) {
-            const int u = (int)uv[k / 2] - 128, v = (int)vv[k / 2] - 128;
-            const int ruv = (1 << (SHIFT - 1)) + CVR * v;
-            const int guv = (1 << (SHIFT - 1)) + CVG * v + CUG * u;
-            const int buv = (1 << (SHIFT - 1)) + CUB * u;
-            int yy = (int)yv[r][k] - 16;
-            yy = (yy < 0 ? 0 : yy) * CY;
-            o[3 * k] = (uint8_t)sat8((yy + buv) >> SHIFT);
-            o[3 * k + 1] = (uint8_t)sat8((yy + guv) >> SHIFT);
-            o[3 * k + 2] = (uint8_t)sat8((yy + ruv) >> SHIFT);
+            i420_pixel(yv[r][k], i420_chroma(uv[k / 2], vv[k / 2]), o + 3 * k);
         }
         uint8_t* d = bgr + ((size_t)(y + r) * w + x) * 3;
         if constexpr (PX == 4) {

@@ -6,6 +6,7 @@ canonical_size = 20 * golib_shim.gsize      # 380: side of the straightened goba
 frame_period = 0.2                          # min seconds between two iterations (live input)
 unsynced = "unsynced"                       # marker returned by lock-step file readers
 file_fps = 5                                # target read rate for video files
+downsample = 0                              # levels of cv2.pyrDown every frame goes through before a finder sees it (0: none)
 
 # (module, class) pairs resolved by VManagerBase._reflect; first importable entry is the default
 bfinders = [

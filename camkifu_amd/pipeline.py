@@ -1349,13 +1349,20 @@ class FastFilePipeline:
             return [()] * len(full)
         return self.stones.run(None, None, counts, records=full)
 
-    def process_y4m(self, capture, batch=256, file_fps=None, torch_device=None):
+    def process_y4m(self, capture, batch=256, file_fps=None, torch_device=None, downsample=0):
         """Fast processing of a video file (README "Fast video file processing"; frame selection as the reference's
         file reader, core/vmanager.py:510-525).  The frames to analyse are dealt to the ranks batch by batch; each rank
         uploads ITS frames as I420 (1.5 B/px through a reused pinned buffer), converts them in HBM (ck_i420_to_bgr)
-        and the batch goes through process_batch.  Returns the concatenated request lists (rank 0)."""
+        and the batch goes through process_batch.  Returns the concatenated request lists (rank 0).
+        `downsample` = N > 0: the frames are analysed N pyrDown levels smaller (what cvconf.downsample is to the capture
+        readers).  Each rank converts its I420 frames straight to the downsampled BGR batch (ck_i420_to_bgr_pyr: the
+        full-size BGR frames are never written) and everything after that sees ordinary frames of capi.pyr_shape(h, w, N);
+        the pipeline must have been built for that size."""
         import torch
+        from . import capi
         from .core.capture import file_frame_indices
+        downsample = int(downsample)
+        fh, fw = capi.pyr_shape(capture.h, capture.w, downsample)
         idx = file_frame_indices(len(capture), capture.fps, file_fps)
         dev = torch_device if torch_device is not None else torch.device("cuda", getattr(self.ctx, "device", 0))
         pinned, emitted = None, []
@@ -1366,9 +1373,12 @@ class FastFilePipeline:
                 pinned = torch.empty((len(shard_indices(batch, 0, self.world)), capture.fsize), dtype=torch.uint8).pin_memory()
             raw = capture.read_raw_batch(mine, out=pinned.numpy())
             if len(mine):
-                frames = self.ctx.i420_to_bgr(raw, capture.h, capture.w, to_device=dev)
+                if downsample:
+                    frames = self.ctx.i420_to_bgr(raw, capture.h, capture.w, to_device=dev, levels=downsample)
+                else:
+                    frames = self.ctx.i420_to_bgr(raw, capture.h, capture.w, to_device=dev)
             else:
-                frames = torch.empty((0, capture.h, capture.w, 3), dtype=torch.uint8, device=dev)
+                frames = torch.empty((0, fh, fw, 3), dtype=torch.uint8, device=dev)
             out = self.process_batch(frames, len(chunk))
             if out is not None:
                 emitted.extend(out)

@@ -121,6 +121,18 @@ int ck_board_detect(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in
 int ck_i420_to_bgr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int in_space,
                    uint8_t* bgr, int out_space);
 
+/* ---- frame downsampling: CaptureReaderBase.downsample's cv2.pyrDown(img)   core/vmanager.py:484-498
+ * OpenCV 3.1.0 pyrDown of 8-bit 3-channel frames, BORDER_DEFAULT, applied `levels` times: per level h x w becomes
+ * (h+1)/2 x (w+1)/2 and dst[y,x] = (sum_{i,j=-2..2} k[i] k[j] src[r(2y+i), r(2x+j)] + 128) >> 8 with k = 1 4 6 4 1 and
+ * r = BORDER_REFLECT_101 -- integer and exact.  out: n frames of the last level.
+ * CK_ERR_ARG for levels < 1 and for a level that would read an image with a side below 2.
+ * The second form takes I420 frames (h, w even, else CK_ERR_ARG) and equals ck_pyr_down of ck_i420_to_bgr bit for
+ * bit; its first level converts and filters in one kernel, so the full-size BGR frames are never written. */
+int ck_pyr_down(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int levels,
+                int in_space, uint8_t* out, int out_space);
+int ck_i420_to_bgr_pyr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int levels /* >= 1 */,
+                       int in_space, uint8_t* bgr, int out_space);
+
 /* ---- K7  cv2.getPerspectiveTransform(src4, dst4)            board/boardfinder.py:43-45
  * host only; src/dst 4x2 float32, M 3x3 float64 row-major. */
 int ck_get_perspective_transform(const float* src4, const float* dst4, double* M9);

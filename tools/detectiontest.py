@@ -5,6 +5,7 @@ match ratio.  Runs the drop-in finders (BoardFinderAuto + SfNeural) on the HIP l
 
     python tools/detectiontest.py --synthetic 640x480 --frames 200
     python tools/detectiontest.py -v clip.npy --sgf game.sgf [--bf BoardFinderAuto --sf SfNeural]
+    python tools/detectiontest.py --synthetic 3840x2160 --frames 200 --downsample 1      (finders work on 1920x1080)
 """
 import argparse
 import os
@@ -14,7 +15,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from camkifu_amd import synth  # noqa: E402
+from camkifu_amd import cvconf, synth  # noqa: E402
 from camkifu_amd.controller import ControllerHeadless  # noqa: E402
 from camkifu_amd.core.vmanager import VManagerSeq  # noqa: E402
 from camkifu_amd.golib_shim import Kifu, Move, NP_TYPE  # noqa: E402
@@ -30,7 +31,10 @@ def main():
     ap.add_argument("--bf", default=None)
     ap.add_argument("--sf", default=None)
     ap.add_argument("--failfast", action="store_true")
+    ap.add_argument("--downsample", type=int, default=0, metavar="N",
+                    help="levels of cv2.pyrDown every frame goes through before the finders see it (cvconf.downsample)")
     args = ap.parse_args()
+    cvconf.downsample = args.downsample
     if args.synthetic:
         # a filmed game: a position, then a move every 30 frames with the player's hand over the point first
         # (synth.film); the reference game = that position in the order the first assessment reports it, then the moves

@@ -28,6 +28,8 @@ EXPORTS = [
     "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_get_perspective_transform", "ck_warp_perspective",
     "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
+    "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
+    "ck_train_get_adam_state", "ck_train_handover",
     "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
     "ck_board_detect_records", "ck_cnn_regions_records",
     "ck_contour_stones", "ck_cluster_stones", "ck_rng_get", "ck_rng_set", "ck_contours_external", "ck_find_intersections", "ck_update_grid",
@@ -115,6 +117,11 @@ def lib():
         L.ck_cluster_stones.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int] + [C.c_void_p] * 5 + [C.c_longlong] + [C.c_void_p] * 3)
         L.ck_rng_get.argtypes = [C.c_void_p, C.c_void_p]
+        L.ck_train_step.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
+                                    + [C.c_double, C.c_int, C.c_uint64, C.c_void_p])
+        L.ck_train_grads.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
+                                     + [C.c_int, C.c_uint64, C.c_longlong] + [C.c_void_p] * 5)
+        L.ck_train_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
         L.ck_rng_set.argtypes = [C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
@@ -492,6 +499,101 @@ class Context:
         p4 = np.empty((n, 100, 6, 6, 90), np.float32)
         self._chk(lib().ck_cnn_maps(self._h, p, n, sp, p2.ctypes.data_as(C.c_void_p), p4.ctypes.data_as(C.c_void_p)))
         return p2, p4
+
+    # ---- training of the classifier (k_cnn_train.hip) -----------------------------------------
+    def _weight_ptrs(self, arrays, what):
+        """12 float32 arrays under the WEIGHT_ORDER names -> (pointer table, memory space, keepalive)"""
+        ptrs, keep, space = (C.c_void_p * 12)(), [], None
+        for i, k in enumerate(WEIGHT_ORDER):
+            a = arrays[k]
+            if tuple(a.shape) != WEIGHT_SHAPES[k]:
+                raise ValueError("%s %s: shape %r, expected %r" % (what, k, tuple(a.shape), WEIGHT_SHAPES[k]))
+            if _is_torch(a) and "float32" not in str(a.dtype):
+                a = a.float()
+            p, sp, ka = self._in(a.contiguous() if _is_torch(a) else a, np.float32)
+            if space not in (None, sp):
+                raise ValueError("%s must live in one memory space" % what)
+            space, ptrs[i] = sp, p
+            keep.append(ka)
+        return ptrs, space, keep
+
+    @staticmethod
+    def _weight_outs():
+        out = {k: np.empty(WEIGHT_SHAPES[k], np.float32) for k in WEIGHT_ORDER}
+        return out, (C.c_void_p * 12)(*(out[k].ctypes.data_as(C.c_void_p) for k in WEIGHT_ORDER))
+
+    def train_create(self, weights):
+        """a trainer holding a copy of `weights` (dict of 12 float32 arrays, numpy or torch, host or device) -> handle"""
+        ptrs, space, keep = self._weight_ptrs(weights, "weights")
+        hd = C.c_int(-1)
+        self._chk(lib().ck_train_create(self._h, ptrs, space, C.byref(hd)))
+        return hd.value
+
+    def train_destroy(self, handle):
+        self._chk(lib().ck_train_destroy(self._h, int(handle)))
+
+    def _train_batch(self, x, labels):
+        """-> (pointer, space, n, h, w, c, labels pointer, keepalive); the library checks the shape and the labels"""
+        shp = tuple(int(v) for v in x.shape) + (0,) * 4
+        n, h, w, c = shp[:4] if len(x.shape) == 4 else (shp[0], 0, 0, 0)
+        if _is_torch(labels):
+            labels = labels.detach().cpu().numpy()
+        labels = np.asarray(labels)
+        if labels.ndim == 2:                         # one-hot rows
+            labels = labels.argmax(1)
+        if labels.shape != (n,):
+            raise ValueError("labels %r for %d patches" % (labels.shape, n))
+        lab = np.ascontiguousarray(np.where((labels < 0) | (labels > 255), 255, labels), np.uint8)      # out of range: the library says so
+        if _is_torch(x):
+            x = x.contiguous()
+        p, sp, keep = self._in(x)
+        return p, sp, n, h, w, c, lab.ctypes.data_as(C.c_void_p), (keep, lab)
+
+    def train_step(self, handle, x, labels, lr=0.001, dropout=True, seed=0):
+        """gradients of the batch and one Adam update -> the batch's mean loss (before the update).  x: uint8 (n, 40, 40, 3)
+        raw BGR patches, host or device; labels: n class indices 0..80 (or one-hot rows)"""
+        p, sp, n, h, w, c, lp, keep = self._train_batch(x, labels)
+        loss = C.c_float(0)
+        self._chk(lib().ck_train_step(self._h, int(handle), p, lp, n, h, w, c, sp, float(lr), int(bool(dropout)),
+                                      int(seed) & 0xffffffffffffffff, C.byref(loss)))
+        return float(loss.value)
+
+    def train_grads(self, handle, x, labels, dropout=False, seed=0, step=-1):
+        """the inspection call: (loss, dict of the 12 gradients, masks) with no update; masks = the three keep-masks
+        (n, 16, 16, 32), (n, 6, 6, 90), (n, 160) as uint8 with dropout, else None.  step < 0: the trainer's own count"""
+        p, sp, n, h, w, c, lp, keep = self._train_batch(x, labels)
+        grads, gp = self._weight_outs()
+        loss = C.c_float(0)
+        masks, mp = None, [None] * 3
+        if dropout:
+            masks = [np.empty((n,) + s, np.uint8) for s in ((16, 16, 32), (6, 6, 90), (160,))]
+            mp = [m.ctypes.data_as(C.c_void_p) for m in masks]
+        self._chk(lib().ck_train_grads(self._h, int(handle), p, lp, n, h, w, c, sp, int(bool(dropout)),
+                                       int(seed) & 0xffffffffffffffff, int(step), C.byref(loss), gp, *mp))
+        return float(loss.value), grads, masks
+
+    def train_apply(self, handle, grads, lr=0.001):
+        """one Adam update from 12 given gradient arrays (host)"""
+        host = {k: (grads[k].detach().cpu().numpy() if _is_torch(grads[k]) else grads[k]) for k in WEIGHT_ORDER}
+        ptrs, space, keep = self._weight_ptrs(host, "gradients")
+        self._chk(lib().ck_train_apply(self._h, int(handle), ptrs, float(lr)))
+
+    def train_weights(self, handle):
+        out, ptrs = self._weight_outs()
+        self._chk(lib().ck_train_get_weights(self._h, int(handle), ptrs))
+        return out
+
+    def train_adam_state(self, handle):
+        """-> (first moments, second moments, updates applied)"""
+        m, mp = self._weight_outs()
+        v, vp = self._weight_outs()
+        steps = C.c_longlong(0)
+        self._chk(lib().ck_train_get_adam_state(self._h, int(handle), mp, vp, C.byref(steps)))
+        return m, v, int(steps.value)
+
+    def train_handover(self, handle):
+        """the trainer's current weights become the context's classifier (no host round trip)"""
+        self._chk(lib().ck_train_handover(self._h, int(handle)))
 
     def stones_detect(self, bgr, M):
         n, h, w = self._shape(bgr, 3)

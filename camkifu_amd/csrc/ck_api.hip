@@ -254,6 +254,7 @@ int ck_ctx_destroy2(ck_ctx* ctx)
         if (m.rates_dev) (void)hipFree(m.rates_dev);
         if (m.rates_done) (void)hipEventDestroy(m.rates_done);
     }
+    for (auto& tr : ctx->trainers) k_train_free(tr);
     for (auto& pe : ctx->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->handover) (void)hipEventDestroy(ctx->handover);
@@ -1086,6 +1087,170 @@ int ck_mog2_destroy(ck_ctx* ctx, int handle)
     if (!ctx || handle < 0 || handle >= (int)ctx->mog2.size()) return CK_ERR_ARG;
     ctx->mog2[handle].alive = false;
     return CK_OK;
+    CK_API_END(ctx)
+}
+
+// ---- training of the stone classifier (k_cnn_train.hip) -----------------------------------------------------------------
+static int trainer_of(ck_ctx* ctx, int handle, CkTrainer** tr)
+{
+    if (handle < 0 || handle >= (int)ctx->trainers.size() || !ctx->trainers[handle].alive)
+        return ck_fail(ctx, CK_ERR_ARG, "bad trainer handle %d", handle);
+    *tr = &ctx->trainers[handle];
+    return CK_OK;
+}
+
+int ck_train_create(ck_ctx* ctx, const float* const weights[12], int space, int* handle)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx || !weights || !handle) return CK_ERR_ARG;
+    for (int i = 0; i < 12; i++) if (!weights[i]) return ck_fail(ctx, CK_ERR_ARG, "weights[%d] is NULL", i);
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    int idx = -1;
+    for (size_t i = 0; i < ctx->trainers.size(); i++) if (!ctx->trainers[i].alive) { idx = (int)i; break; }
+    if (idx < 0) { ctx->trainers.emplace_back(); idx = (int)ctx->trainers.size() - 1; }
+    CK_TRY(k_train_create(ctx, ctx->trainers[idx], weights, space));
+    *handle = idx;
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_train_destroy(ck_ctx* ctx, int handle)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    k_train_free(*tr);
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// checks, staging and the gradient pass shared by ck_train_step and ck_train_grads: leaves the gradients in tr->g and
+// the mean loss in *loss
+static int train_pass(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labels, int n, int h, int w, int c, int in_space,
+                      int dropout, uint64_t seed, long long step, bool want_masks, float* loss, CkTrainer** out)
+{
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    if (!x || !labels) return ck_fail(ctx, CK_ERR_ARG, "patches or labels NULL");
+    if (n < 1 || h != 40 || w != 40 || c != 3)
+        return ck_fail(ctx, CK_ERR_ARG, "patches of shape %d x %d x %d x %d: expected n x 40 x 40 x 3 with n >= 1", n, h, w, c);
+    for (int i = 0; i < n; i++)
+        if (labels[i] > 80) return ck_fail(ctx, CK_ERR_ARG, "label %d of patch %d: a class index is 0 .. 80", (int)labels[i], i);
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    const void* d_x;
+    CK_TRY(ck_to_device(ctx, x, (size_t)n * 4800, in_space, ctx->in_stage, &d_x));
+    CK_TRY(ck_ensure(ctx, tr->lab, (size_t)n));
+    CK_HIP(ctx, hipMemcpyAsync(tr->lab.p, labels, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    CK_TRY(k_train_grads(ctx, *tr, (const uint8_t*)d_x, (const uint8_t*)tr->lab.p, n, dropout ? 1 : 0, seed,
+                         (uint64_t)(step < 0 ? tr->steps : step), want_masks));
+    std::vector<float> per(n);
+    CK_HIP(ctx, hipMemcpyAsync(per.data(), tr->lossv.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CK_TRY(finish(ctx));
+    double sum = 0;                              // the mean over the batch, summed in patch order
+    for (int i = 0; i < n; i++) sum += per[i];
+    if (loss) *loss = (float)(sum / n);
+    *out = tr;
+    return CK_OK;
+}
+
+int ck_train_step(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labels, int n, int h, int w, int c, int in_space,
+                  double lr, int dropout, uint64_t seed, float* loss)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(train_pass(ctx, handle, x, labels, n, h, w, c, in_space, dropout, seed, -1, false, loss, &tr));
+    CK_TRY(k_train_adam(ctx, *tr, (const float*)tr->g.p, lr));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_train_grads(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labels, int n, int h, int w, int c, int in_space,
+                   int dropout, uint64_t seed, long long step, float* loss, float* const grads[12],
+                   uint8_t* mask1, uint8_t* mask2, uint8_t* mask3)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    const bool masks = dropout && (mask1 || mask2 || mask3);
+    CK_TRY(train_pass(ctx, handle, x, labels, n, h, w, c, in_space, dropout, seed, step, masks, loss, &tr));
+    if (grads)
+        for (int i = 0; i < 12; i++)
+            CK_TRY(ck_from_device(ctx, grads[i], (const float*)tr->g.p + ck_train_offset(i), CK_TRAIN_COUNTS[i] * sizeof(float), CK_HOST));
+    if (masks) {
+        CK_TRY(ck_from_device(ctx, mask1, tr->mask1.p, (size_t)n * 8192, CK_HOST));
+        CK_TRY(ck_from_device(ctx, mask2, tr->mask2.p, (size_t)n * 3240, CK_HOST));
+        CK_TRY(ck_from_device(ctx, mask3, tr->mask3.p, (size_t)n * 160, CK_HOST));
+    }
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_train_apply(ck_ctx* ctx, int handle, const float* const grads[12], double lr)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    if (!grads) return ck_fail(ctx, CK_ERR_ARG, "grads is NULL");
+    for (int i = 0; i < 12; i++) if (!grads[i]) return ck_fail(ctx, CK_ERR_ARG, "grads[%d] is NULL", i);
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < 12; i++)
+        CK_HIP(ctx, hipMemcpyAsync((float*)tr->g.p + ck_train_offset(i), grads[i], CK_TRAIN_COUNTS[i] * sizeof(float),
+                                   hipMemcpyHostToDevice, ctx->stream));
+    CK_TRY(k_train_adam(ctx, *tr, (const float*)tr->g.p, lr));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+static int train_get(ck_ctx* ctx, const DevBuf& src, float* const dst[12])
+{
+    if (!dst) return CK_OK;
+    for (int i = 0; i < 12; i++)
+        CK_TRY(ck_from_device(ctx, dst[i], (const float*)src.p + ck_train_offset(i), CK_TRAIN_COUNTS[i] * sizeof(float), CK_HOST));
+    return CK_OK;
+}
+
+int ck_train_get_weights(ck_ctx* ctx, int handle, float* const weights[12])
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    CK_TRY(train_get(ctx, tr->w, weights));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_train_get_adam_state(ck_ctx* ctx, int handle, float* const m[12], float* const v[12], long long* steps)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    CK_TRY(train_get(ctx, tr->m, m));
+    CK_TRY(train_get(ctx, tr->v, v));
+    if (steps) *steps = tr->steps;
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_train_handover(ck_ctx* ctx, int handle)
+{
+    CK_API_BEGIN(ctx)
+    if (!ctx) return CK_ERR_ARG;
+    CkTrainer* tr;
+    CK_TRY(trainer_of(ctx, handle, &tr));
+    CK_HIP(ctx, hipSetDevice(ctx->device));
+    CK_TRY(finish(ctx));
+    const float* w[12];
+    for (int i = 0; i < 12; i++) w[i] = (const float*)tr->w.p + ck_train_offset(i);
+    return ck_cnn_set_weights(ctx, w, CK_DEVICE);
     CK_API_END(ctx)
 }
 

@@ -45,6 +45,18 @@ struct Mog2State {
     bool rates_busy = false;
 };
 
+// A trainer of the stone classifier (k_cnn_train.hip): master weights, the last gradients and both Adam moments as flat f32
+// arrays in weight order (c1w c1b .. d2w d2b, CK_TRAIN_PARAMS floats), what one chunk keeps between forward and backward,
+// the partial sums of the weight gradients, and the number of Adam updates applied so far.
+#define CK_TRAIN_PARAMS 658665
+#define CK_TRAIN_CHUNK 256
+struct CkTrainer {
+    bool alive = false;
+    long long steps = 0;
+    DevBuf w, g, m, v;
+    DevBuf lab, a1, a2, p1, a3, a4, p2, h1, lg, dlg, dh1, dp2, dz4, dz3, dp1, dz2, dz1, part, lossv, mask1, mask2, mask3;
+};
+
 // the modes that carry f32 operands as split fp16 (and share the overflow flag and the f32 fallback)
 static inline bool ck_cnn_split(int mode) { return mode == CK_CNN_F16X2 || mode == CK_CNN_F16Q8; }
 
@@ -117,6 +129,7 @@ struct ck_ctx {
     int cnn_fallbacks = 0;           // batches the split-precision mode handed back to the f32 kernels
     int cnn_mode = CK_CNN_F16X2;     // f32-accurate and 2.3x faster than the k-ordered f32 chain (CK_CNN_FP32)
     std::vector<Mog2State> mog2;
+    std::vector<CkTrainer> trainers;
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 };
 
@@ -264,6 +277,14 @@ int k_cnn_bf16_fc1(ck_ctx* ctx, const uint16_t* q4, int np, float* h1);
 int k_cnn_q8_pack(ck_ctx* ctx, const float* k1, const float* k2, const float* k3, const float* k4);
 int k_cnn_q8_conv12(ck_ctx* ctx, const uint8_t* gob, int np, float* p2, int* overflow);
 int k_cnn_q8_conv34(ck_ctx* ctx, const float* p2, int np, float* p4, int* overflow);
+// the classifier's training step (k_cnn_train.hip); d_x n x 40 x 40 x 3 and d_lab n bytes on the device
+extern const size_t CK_TRAIN_COUNTS[12];
+size_t ck_train_offset(int i);
+int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int space);
+void k_train_free(CkTrainer& tr);
+int k_train_grads(ck_ctx* ctx, CkTrainer& tr, const uint8_t* d_x, const uint8_t* d_lab, int n, int drop, uint64_t seed,
+                  uint64_t step, bool want_masks);
+int k_train_adam(ck_ctx* ctx, CkTrainer& tr, const float* d_g, double lr);
 int k_mog2_apply(ck_ctx* ctx, Mog2State& st, const uint8_t* d_img, double lr, uint8_t* d_fg);
 int k_mog2_run(ck_ctx* ctx, Mog2State& st, const uint8_t* d_gobans, int n, const double* learning_rates,
                int32_t* d_fgcount, uint8_t* d_last_fg, int skip_row, int skip_col);

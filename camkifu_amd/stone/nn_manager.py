@@ -1,7 +1,8 @@
-"""NNManager: region geometry, the base-3 label codec and the classifier's weights -- the inference side of the
-reference's stone/nn_manager.py (29-131, 216-298, 360-382) under the same method names, built on small lookup
+"""NNManager: region geometry, the base-3 label codec, the classifier's weights and their training -- the reference's
+stone/nn_manager.py (29-131, 133-214, 216-298, 360-382) under the same method names, built on small lookup
 tables instead of per-call loops.  The Keras model is a dictionary of twelve float32 arrays handed to the HIP
-library (K10..K12, ck_cnn_set_weights); training and the labelling GUI are out of scope.
+library (K10..K12, ck_cnn_set_weights); train() fits them on the GPU (ck_train_*: forward, backward and Adam in
+csrc/k_cnn_train.hip) and writes checkpoints as .npz files of those twelve arrays.  The labelling GUI is out of scope.
 
 Tables (gsize 19, 10 x 10 regions of 2 x 2 intersections, the last region pulled back onto rows 17-18):
     REGION_START[i]  first row (or column) of region i            0, 2, ..., 16, 17
@@ -73,14 +74,34 @@ class NNManager:
         raise ModelMissing("stone classifier model not found: %s (set CAMKIFU_KERAS_MODEL)" % KERAS_MODEL_FILE)
 
     def load_model(path):
+        """the twelve arrays of a Keras-1 HDF5 model, or of an .npz checkpoint (save_model, tools/train_cnn.py)"""
+        if str(path).endswith(".npz"):
+            from ..capi import WEIGHT_ORDER, WEIGHT_SHAPES
+            with np.load(path) as z:
+                net = {k: np.ascontiguousarray(z[k], np.float32) for k in WEIGHT_ORDER}
+            for k, a in net.items():
+                if a.shape != WEIGHT_SHAPES[k]:
+                    raise ValueError("%s: %s has shape %r, expected %r" % (path, k, a.shape, WEIGHT_SHAPES[k]))
+            return net
         from . import keras1
         return keras1.load_model(path)
+
+    def save_model(net, path):
+        """the checkpoint format: an .npz of the twelve arrays under their WEIGHT_ORDER names"""
+        from ..capi import WEIGHT_ORDER
+        with open(path, "wb") as f:
+            np.savez(f, **{k: np.ascontiguousarray(net[k], np.float32) for k in WEIGHT_ORDER})
+
+    def get_nb_weights(net=None):
+        net = _seeded_weights() if net is None else net
+        return int(sum(int(np.prod(a.shape)) for a in net.values()))
 
     def create_net():
         """the architecture of nn_manager.py:277-298 with seeded He-normal weights (untrained)"""
         return _seeded_weights()
 
     init_net, load_model, create_net = staticmethod(init_net), staticmethod(load_model), staticmethod(create_net)
+    save_model, get_nb_weights = staticmethod(save_model), staticmethod(get_nb_weights)
 
     # ---- geometry --------------------------------------------------------------------------------
     def _subregion(self, ri, cj):
@@ -125,3 +146,108 @@ class NNManager:
             per_colour = [[np.flatnonzero(DIGITS[:, k] == col) for col in range(3)] for k in range(STEP * STEP)]
             table = self.c_indices = self._class_table = np.array(per_colour, np.uint8)
         return table
+
+    # ---- datasets (.npz: X uint8 N x 40 x 40 x 3, Y bool N x 81) ----------------------------------
+    def generate_xs(self, img):
+        """the 100 classifier windows of a canonical image, region (i, j) at i * 10 + j"""
+        if tuple(img.shape[:2]) != self.canonical_shape:
+            raise ValueError("canonical image expected, got %r" % (tuple(img.shape),))
+        rows = PATCH_ORIGIN[:, None] + np.arange(PATCH_SIDE)[None, :]
+        cut = np.asarray(img)[rows[:, None, :, None], rows[None, :, None, :]]
+        return np.ascontiguousarray(cut.reshape((SPLIT * SPLIT, PATCH_SIDE, PATCH_SIDE) + tuple(img.shape[2:])), np.uint8)
+
+    def generate_ys(self, stones):
+        """one-hot labels (100, 81) of the regions of a 19 x 19 grid of E / B / W"""
+        ys = np.zeros((SPLIT * SPLIT, NB_CLASSES), bool)
+        for i, r0 in enumerate(REGION_START):
+            for j, c0 in enumerate(REGION_START):
+                ys[i * SPLIT + j, NNManager.compute_label(r0, r0 + STEP, c0, c0 + STEP, stones)] = True
+        return ys
+
+    # ---- training ------------------------------------------------------------------------------------
+    def _context(self):
+        if getattr(self, "ctx", None) is None:
+            from .. import capi
+            self.ctx = capi.get_context()
+        return self.ctx
+
+    @staticmethod
+    def _class_index(y):
+        y = np.asarray(y)
+        return (y.argmax(1) if y.ndim == 2 else y).astype(np.uint8)
+
+    @staticmethod
+    def epoch_order(n, seed, epoch):
+        """the order in which epoch `epoch` visits the n samples: a function of (seed, epoch) alone"""
+        return np.random.default_rng([int(seed), int(epoch)]).permutation(n)
+
+    def train(self, x, y, vdata=None, batch_size=1000, nb_epoch=2, lr=0.001, seed=20161001, dropout=True, checkpoint=None,
+              net=None, verbose=True):
+        """Fit the classifier to patches x (N, 40, 40, 3) uint8 with labels y (one-hot (N, 81) or N class indices) on the
+        GPU, starting from `net` (default: the current network, see get_net).  Adam, categorical cross-entropy,
+        the samples reshuffled per epoch from `seed`.  Prints the loss per epoch (and the loss on vdata = (xv, yv)),
+        writes `checkpoint` (.npz) whenever the epoch's mean loss improves -- ModelCheckpoint(monitor='loss',
+        save_best_only=True) -- hands the trained weights to the context's classifier and makes them the current
+        network.  -> history dict(loss=[..], val_loss=[..])"""
+        ctx = self._context()
+        x, labels = np.ascontiguousarray(x, np.uint8), self._class_index(y)
+        start = NNManager.get_net() if net is None else net
+        handle = ctx.train_create(start)
+        history, best, step = dict(loss=[], val_loss=[]), None, 0
+        try:
+            for epoch in range(int(nb_epoch)):
+                order, total = self.epoch_order(len(x), seed, epoch), 0.0
+                for k in range(0, len(order), int(batch_size)):
+                    idx = order[k:k + int(batch_size)]
+                    total += ctx.train_step(handle, x[idx], labels[idx], lr=lr, dropout=dropout, seed=seed) * len(idx)
+                    step += 1
+                history["loss"].append(total / len(x))
+                line = "epoch %d/%d - loss: %.4f" % (epoch + 1, nb_epoch, history["loss"][-1])
+                if vdata is not None:
+                    xv, yv = np.ascontiguousarray(vdata[0], np.uint8), self._class_index(vdata[1])
+                    parts = [ctx.train_grads(handle, xv[k:k + 1000], yv[k:k + 1000])[0] * len(xv[k:k + 1000])
+                             for k in range(0, len(xv), 1000)]
+                    history["val_loss"].append(sum(parts) / len(xv))
+                    line += " - val_loss: %.4f" % history["val_loss"][-1]
+                if verbose:
+                    print(line, flush=True)
+                if best is None or history["loss"][-1] < best:
+                    best = history["loss"][-1]
+                    if checkpoint is not None:
+                        NNManager.save_model(ctx.train_weights(handle), checkpoint)
+            ctx.train_handover(handle)
+            with NNManager._guard:
+                NNManager._network = ctx.train_weights(handle)
+        finally:
+            ctx.train_destroy(handle)
+        return history
+
+    def predict_ys(self, x):
+        """argmax class index of each patch of x (N, 40, 40, 3), by the context's classifier as it stands (after train():
+        the trained weights).  The patches ride through the inference kernels 81 to a canonical image, in the regions
+        whose windows do not overlap (i, j < 9)."""
+        ctx = self._context()
+        x = np.ascontiguousarray(x, np.uint8)
+        per = (SPLIT - 1) ** 2
+        sheets = np.zeros((-(-len(x) // per),) + self.canonical_shape + (3,), np.uint8)
+        slot = np.arange(len(x))
+        f, i, j = slot // per, (slot % per) // (SPLIT - 1), slot % (SPLIT - 1)
+        for k in range(len(x)):
+            a, b = int(PATCH_ORIGIN[i[k]]), int(PATCH_ORIGIN[j[k]])
+            sheets[f[k], a:a + PATCH_SIDE, b:b + PATCH_SIDE] = x[k]
+        out = np.empty(len(x), np.int64)
+        for s in range(0, len(sheets), 64):
+            yy = ctx.cnn_predict(sheets[s:s + 64])[0]
+            sel = (f >= s) & (f < s + 64)
+            out[sel] = yy[f[sel] - s, i[sel] * SPLIT + j[sel]].argmax(1)
+        return out
+
+    def evaluate(self, x, y):
+        """the reference's two figures on (x, y): of the non-empty regions (label > 0) how many get exactly their label,
+        of the empty ones (label 0) how many are called empty.  Prints both lines -> (tp, ap, tn, an)"""
+        truth, pred = self._class_index(y).astype(np.int64), np.asarray(self.predict_ys(x))
+        hit, full = pred == truth, truth != 0
+        tp, ap, tn, an = int((hit & full).sum()), int(full.sum()), int((hit & ~full).sum()), int((~full).sum())
+        print("Non-empty: %.2f %% (%d/%d)" % (100.0 * tp / ap if ap else 0, tp, ap))
+        print("Empty    : %.2f %% (%d/%d)" % (100.0 * tn / an if an else 0, tn, an))
+        return tp, ap, tn, an

@@ -179,6 +179,38 @@ int ck_cnn_predict(ck_ctx* ctx, const uint8_t* goban, int n, int in_space,
  * Region order i*10+j as everywhere; either may be NULL; n <= 128 (one chunk of the classifier's frame loop). */
 int ck_cnn_maps(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, float* pool2, float* pool4);
 
+/* ---- training of the stone classifier: NNManager.train                       stone/nn_manager.py:133-214, 277-298
+ * A trainer is a handle on a context (like a MOG2 model): f32 master weights, both Adam moments and the number of updates
+ * applied.  One step = forward pass of the network of create_net on raw 0..255 BGR patches, softmax + categorical
+ * cross-entropy (mean over the batch), backward pass, Adam (lr per call, beta1 0.9, beta2 0.999, eps 1e-8, no decay, bias-corrected
+ * as Keras-1: lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), w -= lr_t m / (sqrt(v) + eps)).  The gradients' products run on the f32-input MFMA, the forward
+ * pass on the f64 MFMA rounded once to f32 (its ReLU and pool decisions are then those of exact arithmetic wherever f32 can tell
+ * the values apart), all with fixed summation orders: the same patches, labels, seed and step number give the same bits in every weight.
+ * x: n x h x w x c patches in `in_space` -- anything but n >= 1, h = w = 40, c = 3 is CK_ERR_ARG; labels: HOST, n class indices
+ * 0 .. 80 (above 80: CK_ERR_ARG); any n fits (the batch goes through in chunks of 256 patches).
+ * dropout != 0: 0.25 behind each pool and 0.5 behind dense 1, kept units divided by 1 - p; the keep-mask is a counter-based
+ * function of (seed, step, layer, unit index) with no state, step = the number of updates the trainer has applied.
+ * weights / grads / moments: 12 arrays in the order and layouts of ck_cnn_set_weights. */
+int ck_train_create(ck_ctx* ctx, const float* const weights[12], int space, int* handle);
+int ck_train_destroy(ck_ctx* ctx, int handle);
+/* gradients of the batch, then one Adam update; *loss: the mean loss before the update */
+int ck_train_step(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labels, int n, int h, int w, int c, int in_space,
+                  double lr, int dropout, uint64_t seed, float* loss);
+/* the inspection call (the counterpart of ck_cnn_maps): the same gradients, no update.  step < 0: the trainer's own count.
+ * Outputs on the HOST, each nullable: grads (12 arrays), and with dropout the keep-masks (1 kept, 0 dropped) behind pool 1
+ * (n x 16 x 16 x 32), pool 2 (n x 6 x 6 x 90) and dense 1 (n x 160). */
+int ck_train_grads(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labels, int n, int h, int w, int c, int in_space,
+                   int dropout, uint64_t seed, long long step, float* loss, float* const grads[12],
+                   uint8_t* mask1, uint8_t* mask2, uint8_t* mask3);
+/* one Adam update from 12 gradient arrays on the HOST */
+int ck_train_apply(ck_ctx* ctx, int handle, const float* const grads[12], double lr);
+int ck_train_get_weights(ck_ctx* ctx, int handle, float* const weights[12]);                 /* to the HOST */
+/* first moments m, second moments v (each nullable, 12 HOST arrays), *steps = updates applied */
+int ck_train_get_adam_state(ck_ctx* ctx, int handle, float* const m[12], float* const v[12], long long* steps);
+/* hand the trainer's current weights to the context's classifier (ck_cnn_set_weights from device memory): ck_cnn_predict
+ * and the other inference calls then run on them */
+int ck_train_handover(ck_ctx* ctx, int handle);
+
 /* ---- K8 + K10..K12: frame + M -> 19x19 labels   stonesfinder.py:140 + nn_cache.py:33-41 */
 int ck_stones_detect(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space,
                      const double* M, int m_count, uint8_t* labels, double* conf,

@@ -37,25 +37,25 @@ int ck_fail(ck_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
+// the allocator under DevBuf and PinBuf (ck_buf.h): the only calls of it in the library
+int ck_dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+int ck_dev_free(void* p) { return (int)hipFree(p); }
+int ck_pin_alloc(void** p, size_t bytes, unsigned flags) { return (int)hipHostMalloc(p, bytes, flags); }
+int ck_pin_free(void* p) { return (int)hipHostFree(p); }
+static_assert(CK_PIN_DEFAULT == hipHostMallocDefault && CK_PIN_MAPPED == hipHostMallocMapped, "ck_buf.h restates the flags");
+
 int ck_ensure(ck_ctx* ctx, DevBuf& b, size_t bytes)
 {
     if (bytes <= b.cap) return CK_OK;
-    if (b.p) { CK_HIP(ctx, hipStreamSynchronize(ctx->stream)); CK_HIP(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    CK_HIP(ctx, hipMalloc(&b.p, want));
-    b.cap = want;
+    if (b.p) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // queued work may still use the old block
+    CK_HIP(ctx, (hipError_t)b.reserve(bytes, bytes + bytes / 8 + 256));
     return CK_OK;
 }
 
-int ck_ensure_pinned(ck_ctx* ctx, size_t bytes, int which)
+int ck_ensure_pinned(ck_ctx* ctx, PinBuf& b, size_t bytes, size_t slack)
 {
-    void*& p = which ? ctx->host_pinned2 : ctx->host_pinned;
-    size_t& cap = which ? ctx->host_pinned2_cap : ctx->host_pinned_cap;
-    if (bytes <= cap) return CK_OK;
-    if (p) { CK_HIP(ctx, hipHostFree(p)); p = nullptr; cap = 0; }
-    bytes += bytes / 4;                       // a little headroom: the survey's point count changes from batch to batch
-    CK_HIP(ctx, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    cap = bytes;
+    // a little headroom: the survey's point count changes from batch to batch
+    CK_HIP(ctx, (hipError_t)b.reserve(bytes, bytes + bytes / 4 + slack));
     return CK_OK;
 }
 
@@ -79,6 +79,25 @@ int ck_from_device(ck_ctx* ctx, void* dst, const void* dev, size_t bytes, int sp
     }
     return CK_OK;
 }
+
+// The mirror of ck_to_device for a result of `bytes` that the caller wants at `user`: open() gives the device pointer the
+// kernels write -- `user` itself, or `stage` when the caller's memory is the host's -- and deliver() then copies it home.
+// A space other than CK_HOST is taken for device memory, unchecked, as it always was.  A NULL `user` stays NULL.
+template <class T>
+struct OutStage {
+    T* dev = nullptr;
+    T* user = nullptr;
+    size_t bytes = 0;
+    int open(ck_ctx* ctx, T* user_ptr, size_t nbytes, int space, DevBuf& stage)
+    {
+        dev = user_ptr;
+        if (!user_ptr || space != CK_HOST) return CK_OK;
+        CK_TRY(ck_ensure(ctx, stage, nbytes));
+        dev = (T*)stage.p; user = user_ptr; bytes = nbytes;
+        return CK_OK;
+    }
+    int deliver(ck_ctx* ctx) const { return user ? ck_from_device(ctx, user, dev, bytes, CK_HOST) : CK_OK; }
+};
 
 // ---- timing ---------------------------------------------------------------------------
 TimeScope::TimeScope(ck_ctx* c, const char* name) : ctx(c)
@@ -174,6 +193,32 @@ int ck_goban_canny_dev(ck_ctx* ctx, const uint8_t* d_in, int n, int h, int w, ui
                           (int32_t*)ctx->labels.p, d_edges, nullptr, nullptr, d_thr, (const uint8_t*)ctx->trange.p);
 }
 
+// ---- handles: an index into the context's models / trainers, valid while that slot is alive ----
+static int mog2_of(ck_ctx* ctx, int handle, Mog2State** st)
+{
+    if (handle < 0 || handle >= (int)ctx->mog2.size() || !ctx->mog2[handle].alive)
+        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", handle);
+    *st = &ctx->mog2[handle];
+    return CK_OK;
+}
+
+static int trainer_of(ck_ctx* ctx, int handle, CkTrainer** tr)
+{
+    if (handle < 0 || handle >= (int)ctx->trainers.size() || !ctx->trainers[handle].alive)
+        return ck_fail(ctx, CK_ERR_ARG, "bad trainer handle %d", handle);
+    *tr = &ctx->trainers[handle];
+    return CK_OK;
+}
+
+// the first slot that is not alive (a dead model keeps its memory for the next one), else a new one at the end
+template <class T>
+static int free_slot(std::vector<T>& slots)
+{
+    for (size_t i = 0; i < slots.size(); i++) if (!slots[i].alive) return (int)i;
+    slots.emplace_back();
+    return (int)slots.size() - 1;
+}
+
 extern "C" {
 
 int ck_version(void) { return 100; }
@@ -194,11 +239,11 @@ int ck_ctx_create_prio(int device, int priority, ck_ctx** out)
     ck_ctx* ctx = new ck_ctx();
     ctx->device = device;
     if (priority == 0)
-        e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+        e = hipStreamCreateWithFlags(&ctx->stream.s, hipStreamNonBlocking);
     else {
         int least = 0, greatest = 0;                     // (numerically: greatest priority = the smaller number)
         e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, priority > 0 ? greatest : least);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&ctx->stream.s, hipStreamNonBlocking, priority > 0 ? greatest : least);
     }
     if (e != hipSuccess) { delete ctx; return ck_fail(nullptr, CK_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     *out = ctx;
@@ -236,35 +281,22 @@ int ck_ctx_destroy2(ck_ctx* ctx)
     }
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* bufs[] = { &ctx->in_stage, &ctx->in_stage2, &ctx->planes, &ctx->trange, &ctx->edges, &ctx->map, &ctx->labels,
-                       &ctx->labels2, &ctx->runs, &ctx->ghost, &ctx->misc, &ctx->bflag, &ctx->comp, &ctx->lists, &ctx->pts, &ctx->accum, &ctx->peaks,
-                       &ctx->goban, &ctx->act0, &ctx->act1, &ctx->act2, &ctx->ybuf, &ctx->lblbuf, &ctx->confbuf,
-                       &ctx->rlblbuf, &ctx->rconfbuf, &ctx->fgcbuf,
-                       &ctx->out_stage, &ctx->mats, &ctx->rec_stage, &ctx->pyr0, &ctx->pyr1,
-                       &ctx->cnn.c1w, &ctx->cnn.c1b, &ctx->cnn.c2w, &ctx->cnn.c2b, &ctx->cnn.c3w, &ctx->cnn.c3b,
-                       &ctx->cnn.c4w, &ctx->cnn.c4b, &ctx->cnn.d1w, &ctx->cnn.d1b, &ctx->cnn.d2w, &ctx->cnn.d2b,
-                       &ctx->cnn.c2w_bf, &ctx->cnn.c3w_bf, &ctx->cnn.c4w_bf, &ctx->cnn.d1w_bf, &ctx->cnn.c1w_f16, &ctx->cnn.d1w_bfp, &ctx->cnn.c1w_q8, &ctx->cnn.c2x_q8, &ctx->cnn.c3x_q8, &ctx->cnn.c4x_q8, &ctx->cnn.d1w_h2,
-                       &ctx->cnn.c1w_h2, &ctx->cnn.c2w_h2, &ctx->cnn.c3w_h2, &ctx->cnn.c4w_h2 };
-    for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
-    if (ctx->cnn_flag_host) (void)hipHostFree(ctx->cnn_flag_host);
-    for (auto& m : ctx->mog2) {
-        DevBuf* mb[] = { &m.weight, &m.variance, &m.mean, &m.nmodes };
-        for (DevBuf* b : mb) if (b->p) (void)hipFree(b->p);
-        if (m.rates_host) (void)hipHostFree(m.rates_host);
-        if (m.rates_dev) (void)hipFree(m.rates_dev);
-        if (m.rates_done) (void)hipEventDestroy(m.rates_done);
-    }
-    for (auto& tr : ctx->trainers) k_train_free(tr);
-    for (auto& pe : ctx->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
-    for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-    if (ctx->handover) (void)hipEventDestroy(ctx->handover);
-    if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);
-    if (ctx->host_pinned2) (void)hipHostFree(ctx->host_pinned2);
-    if (ctx->rec_host) (void)hipHostFree(ctx->rec_host);
-    (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return CK_OK;
 }
+
+}  // extern "C"
+
+// after ck_ctx_destroy2 has synchronised the stream: the events go here, every buffer frees itself, the stream goes last
+ck_ctx::~ck_ctx()
+{
+    for (auto& m : mog2) if (m.rates_done) (void)hipEventDestroy(m.rates_done);
+    for (auto& pe : pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
+    for (auto e : event_pool) (void)hipEventDestroy(e);
+    if (handover) (void)hipEventDestroy(handover);
+}
+
+extern "C" {
 
 const char* ck_last_error(const ck_ctx* ctx)
 {
@@ -288,7 +320,6 @@ int ck_timing_enable(ck_ctx* ctx, int on)
 int ck_timing_reset(ck_ctx* ctx)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     ck_timing_collect(ctx);
     ctx->slots.clear();
     return CK_OK;
@@ -297,7 +328,7 @@ int ck_timing_reset(ck_ctx* ctx)
 int ck_timing_get(ck_ctx* ctx, const char* name, double* total_ms, int* launches)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx || !name) return CK_ERR_ARG;
+    if (!name) return CK_ERR_ARG;
     ck_timing_collect(ctx);
     auto it = ctx->slots.find(name);
     if (total_ms) *total_ms = it == ctx->slots.end() ? 0.0 : it->second.ms;
@@ -308,11 +339,9 @@ int ck_timing_get(ck_ctx* ctx, const char* name, double* total_ms, int* launches
 
 static int check_img(ck_ctx* ctx, const void* p, int n, int h, int w)
 {
-    if (!ctx) return CK_ERR_ARG;
     if (!p) return ck_fail(ctx, CK_ERR_ARG, "image pointer is NULL");
     if (n <= 0 || h <= 0 || w <= 0) return ck_fail(ctx, CK_ERR_ARG, "bad shape n=%d h=%d w=%d", n, h, w);
     if ((long long)h * w > (1LL << 28)) return ck_fail(ctx, CK_ERR_ARG, "image too large");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     return CK_OK;
 }
 
@@ -340,10 +369,10 @@ int ck_median(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int ksize, i
     CK_TRY(ck_to_device(ctx, bgr, bytes, in_space, ctx->in_stage, &d_in));
     CK_TRY(ck_ensure(ctx, ctx->planes, (size_t)n * 3 * h * pitch));
     CK_TRY(k_median_planar(ctx, (const uint8_t*)d_in, n, h, w, ksize, (uint8_t*)ctx->planes.p, pitch));
-    uint8_t* d_out = out;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, bytes)); d_out = (uint8_t*)ctx->out_stage.p; }
-    CK_TRY(k_planar_to_interleaved(ctx, (const uint8_t*)ctx->planes.p, n, h, w, pitch, d_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, out, d_out, bytes, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, out, bytes, out_space, ctx->out_stage));
+    CK_TRY(k_planar_to_interleaved(ctx, (const uint8_t*)ctx->planes.p, n, h, w, pitch, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -362,18 +391,13 @@ int ck_canny(ck_ctx* ctx, const uint8_t* img3, int n, int h, int w, int in_space
     CK_TRY(k_interleaved_to_planar(ctx, (const uint8_t*)d_in, n, h, w, pitch, (uint8_t*)ctx->planes.p));
     CK_TRY(ck_ensure(ctx, ctx->map, npx));
     CK_TRY(ck_ensure(ctx, ctx->labels, npx * 4));
-    uint8_t* d_edges = edges;
-    uint8_t* d_mapout = map_out;
-    if (out_space == CK_HOST) {
-        CK_TRY(ck_ensure(ctx, ctx->edges, npx)); d_edges = (uint8_t*)ctx->edges.p;
-        if (map_out) { CK_TRY(ck_ensure(ctx, ctx->out_stage, npx)); d_mapout = (uint8_t*)ctx->out_stage.p; }
-    }
+    OutStage<uint8_t> oe, om;
+    CK_TRY(oe.open(ctx, edges, npx, out_space, ctx->edges));
+    CK_TRY(om.open(ctx, map_out, npx, out_space, ctx->out_stage));
     CK_TRY(k_canny_planar(ctx, (const uint8_t*)ctx->planes.p, n, h, w, pitch, low, high,
-                          (uint8_t*)ctx->map.p, (int32_t*)ctx->labels.p, d_edges, d_mapout));
-    if (out_space == CK_HOST) {
-        CK_TRY(ck_from_device(ctx, edges, d_edges, npx, CK_HOST));
-        if (map_out) CK_TRY(ck_from_device(ctx, map_out, d_mapout, npx, CK_HOST));
-    }
+                          (uint8_t*)ctx->map.p, (int32_t*)ctx->labels.p, oe.dev, om.dev));
+    CK_TRY(oe.deliver(ctx));
+    CK_TRY(om.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -387,10 +411,10 @@ int ck_goban_canny(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
     const size_t npx = (size_t)n * h * w;
     const void* d_in;
     CK_TRY(ck_to_device(ctx, bgr, npx * 3, in_space, ctx->in_stage, &d_in));
-    uint8_t* d_edges = edges;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->edges, npx)); d_edges = (uint8_t*)ctx->edges.p; }
-    CK_TRY(ck_goban_canny_dev(ctx, (const uint8_t*)d_in, n, h, w, d_edges, otsu_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, edges, d_edges, npx, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, edges, npx, out_space, ctx->edges));
+    CK_TRY(ck_goban_canny_dev(ctx, (const uint8_t*)d_in, n, h, w, o.dev, otsu_out));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -419,10 +443,10 @@ int ck_board_edges(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
     const size_t npx = (size_t)n * h * w;
     const void* d_in;
     CK_TRY(ck_to_device(ctx, bgr, npx * 3, in_space, ctx->in_stage, &d_in));
-    uint8_t* d_edges = edges;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->edges, npx)); d_edges = (uint8_t*)ctx->edges.p; }
-    CK_TRY(board_edges_dev(ctx, (const uint8_t*)d_in, n, h, w, d_edges));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, edges, d_edges, npx, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, edges, npx, out_space, ctx->edges));
+    CK_TRY(board_edges_dev(ctx, (const uint8_t*)d_in, n, h, w, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -439,13 +463,10 @@ int ck_board_lines(ck_ctx* ctx, const uint8_t* edges, int n, int h, int w, int i
     const void* d_in;
     CK_TRY(ck_to_device(ctx, edges, npx, in_space, ctx->in_stage2, &d_in));
     if (hough_thresh < 0) hough_thresh = (int)((h < w ? h : w) / 5.0);
-    uint8_t* d_ghost = nullptr;
-    if (ghost_out) {
-        if (ghost_space == CK_DEVICE) d_ghost = ghost_out;
-        else { CK_TRY(ck_ensure(ctx, ctx->out_stage, npx)); d_ghost = (uint8_t*)ctx->out_stage.p; }
-    }
-    CK_TRY(k_board_lines(ctx, (const uint8_t*)d_in, n, h, w, hough_thresh, lines, cap, res, d_ghost));
-    if (ghost_out && ghost_space == CK_HOST) CK_TRY(ck_from_device(ctx, ghost_out, d_ghost, npx, CK_HOST));
+    OutStage<uint8_t> ghost;
+    CK_TRY(ghost.open(ctx, ghost_out, npx, ghost_space, ctx->out_stage));
+    CK_TRY(k_board_lines(ctx, (const uint8_t*)d_in, n, h, w, hough_thresh, lines, cap, res, ghost.dev));
+    CK_TRY(ghost.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -494,11 +515,10 @@ int ck_i420_to_bgr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int in
     if ((h & 1) || (w & 1)) return ck_fail(ctx, CK_ERR_ARG, "I420 needs even dimensions, got %dx%d", w, h);
     const void* d_in;
     CK_TRY(ck_to_device(ctx, i420, (size_t)n * h * w * 3 / 2, in_space, ctx->in_stage2, &d_in));
-    const size_t obytes = (size_t)n * h * w * 3;
-    uint8_t* d_out = bgr;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
-    CK_TRY(k_i420_to_bgr(ctx, (const uint8_t*)d_in, n, h, w, d_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, bgr, d_out, obytes, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, bgr, (size_t)n * h * w * 3, out_space, ctx->out_stage));
+    CK_TRY(k_i420_to_bgr(ctx, (const uint8_t*)d_in, n, h, w, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -510,6 +530,13 @@ static int check_pyr(ck_ctx* ctx, int h, int w, int levels)
     for (int l = 0; l < levels; l++, h = (h + 1) / 2, w = (w + 1) / 2)
         if (h < 2 || w < 2) return ck_fail(ctx, CK_ERR_ARG, "pyramid level %d would take a %dx%d image: sides below 2", l + 1, w, h);
     return CK_OK;
+}
+
+// bytes of n frames after `levels` halvings of h x w
+static size_t pyr_out_bytes(int n, int h, int w, int levels)
+{
+    for (int l = 0; l < levels; l++) { h = (h + 1) / 2; w = (w + 1) / 2; }
+    return (size_t)n * h * w * 3;
 }
 
 // levels `first` .. `levels` of the pyramid of n frames (h x w is the size level `first` reads), the last one into d_out;
@@ -539,13 +566,10 @@ int ck_pyr_down(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int levels
     CK_TRY(check_img(ctx, bgr, n, h, w));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
-    int oh = h, ow = w;
-    for (int l = 0; l < levels; l++) { oh = (oh + 1) / 2; ow = (ow + 1) / 2; }
-    const size_t obytes = (size_t)n * oh * ow * 3;
-    uint8_t* d_out = out;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
-    CK_TRY(pyr_levels(ctx, (const uint8_t*)d_in, n, h, w, 1, levels, d_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, out, d_out, obytes, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, out, pyr_out_bytes(n, h, w, levels), out_space, ctx->out_stage));
+    CK_TRY(pyr_levels(ctx, (const uint8_t*)d_in, n, h, w, 1, levels, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -560,19 +584,16 @@ int ck_i420_to_bgr_pyr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, in
     CK_TRY(check_img(ctx, i420, n, h, w));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, i420, (size_t)n * h * w * 3 / 2, in_space, ctx->in_stage2, &d_in));
-    int oh = h, ow = w;
-    for (int l = 0; l < levels; l++) { oh = (oh + 1) / 2; ow = (ow + 1) / 2; }
-    const size_t obytes = (size_t)n * oh * ow * 3;
-    uint8_t* d_out = bgr;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, obytes)); d_out = (uint8_t*)ctx->out_stage.p; }
-    uint8_t* d_first = d_out;                       // level 1, fused behind the conversion
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, bgr, pyr_out_bytes(n, h, w, levels), out_space, ctx->out_stage));
+    uint8_t* d_first = o.dev;                       // level 1, fused behind the conversion
     if (levels > 1) {
         CK_TRY(ck_ensure(ctx, ctx->pyr1, (size_t)n * (h / 2) * (w / 2) * 3));
         d_first = (uint8_t*)ctx->pyr1.p;
     }
     CK_TRY(k_i420_pyr_down(ctx, (const uint8_t*)d_in, n, h, w, d_first));
-    if (levels > 1) CK_TRY(pyr_levels(ctx, d_first, n, h / 2, w / 2, 2, levels, d_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, bgr, d_out, obytes, CK_HOST));
+    if (levels > 1) CK_TRY(pyr_levels(ctx, d_first, n, h / 2, w / 2, 2, levels, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -587,11 +608,10 @@ int ck_warp_perspective(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, in
     CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
     const double* d_minv;
     CK_TRY(upload_minv(ctx, M, m_count, n, &d_minv));
-    const size_t obytes = (size_t)n * dsize * dsize * 3;
-    uint8_t* d_out = out;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->goban, obytes)); d_out = (uint8_t*)ctx->goban.p; }
-    CK_TRY(k_warp(ctx, (const uint8_t*)d_in, n, h, w, d_minv, m_count, dsize, d_out));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, out, d_out, obytes, CK_HOST));
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, out, (size_t)n * dsize * dsize * 3, out_space, ctx->goban));
+    CK_TRY(k_warp(ctx, (const uint8_t*)d_in, n, h, w, d_minv, m_count, dsize, o.dev));
+    CK_TRY(o.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -599,9 +619,8 @@ int ck_warp_perspective(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, in
 int ck_cnn_set_weights(ck_ctx* ctx, const float* const weights[12], int space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx || !weights) return CK_ERR_ARG;
+    if (!weights) return CK_ERR_ARG;
     for (int i = 0; i < 12; i++) if (!weights[i]) return ck_fail(ctx, CK_ERR_ARG, "weights[%d] is NULL", i);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     CK_TRY(k_cnn_pack_weights(ctx, weights, space));
     return finish(ctx);
     CK_API_END(ctx)
@@ -610,28 +629,33 @@ int ck_cnn_set_weights(ck_ctx* ctx, const float* const weights[12], int space)
 int ck_cnn_set_mode(ck_ctx* ctx, int mode)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (mode != CK_CNN_FP32 && mode != CK_CNN_BF16 && mode != CK_CNN_F16X2 && mode != CK_CNN_F16Q8) return ck_fail(ctx, CK_ERR_ARG, "unknown cnn mode %d", mode);
     ctx->cnn_mode = mode;
     return CK_OK;
     CK_API_END(ctx)
 }
 
-// where the region outputs of a call go (all optional)
-struct RegionOut { uint8_t* label = nullptr; double* conf = nullptr; ck_frame_record* rec = nullptr; int rec_space = CK_HOST; };
+// where the classifier's answers of a call go (all optional): the softmax rows, labels and confidences per intersection
+// and the region answers in `space`, the stones half of records in `rec_space`
+struct CnnOut {
+    float* y = nullptr;
+    uint8_t* labels = nullptr;
+    double* conf = nullptr;
+    uint8_t* region_label = nullptr;
+    double* region_conf = nullptr;
+    int space = CK_HOST;
+    ck_frame_record* rec = nullptr;
+    int rec_space = CK_HOST;
+};
 
-static int ensure_rec_host(ck_ctx* ctx, size_t bytes)
+// did the split-precision kernels of the last batch flag a value outside the fp16 range? (after a synchronisation)
+static bool cnn_overflowed(const ck_ctx* ctx)
 {
-    if (bytes <= ctx->rec_host_cap) return CK_OK;
-    if (ctx->rec_host) { CK_HIP(ctx, hipHostFree(ctx->rec_host)); ctx->rec_host = nullptr; ctx->rec_host_cap = 0; }
-    bytes += bytes / 4 + 4096;
-    CK_HIP(ctx, hipHostMalloc(&ctx->rec_host, bytes, hipHostMallocDefault));
-    ctx->rec_host_cap = bytes;
-    return CK_OK;
+    return ck_cnn_split(ctx->cnn_mode) && ctx->cnn_flag.p && *(volatile int*)ctx->cnn_flag.p;
 }
 
-static int cnn_predict_dev(ck_ctx* ctx, const uint8_t* d_goban, int n, float* y, uint8_t* labels, double* conf, int out_space,
-                           RegionOut ro = RegionOut())
+// one pass of the kernels of the context's mode, the answers queued for delivery; no synchronisation, no fallback
+static int cnn_predict_dev(ck_ctx* ctx, const uint8_t* d_goban, int n, const CnnOut& o)
 {
     if (!ctx->cnn.set) return ck_fail(ctx, CK_ERR_STATE, "ck_cnn_set_weights has not been called");
     CK_TRY(ck_ensure(ctx, ctx->ybuf, (size_t)n * 8100 * sizeof(float)));
@@ -639,78 +663,72 @@ static int cnn_predict_dev(ck_ctx* ctx, const uint8_t* d_goban, int n, float* y,
     CK_TRY(ck_ensure(ctx, ctx->confbuf, (size_t)n * 361 * sizeof(double)));
     CK_TRY(ck_ensure(ctx, ctx->rlblbuf, (size_t)n * 100));
     CK_TRY(ck_ensure(ctx, ctx->rconfbuf, (size_t)n * 100 * sizeof(double)));
+    int* d_flag = nullptr;
     if (ck_cnn_split(ctx->cnn_mode)) {
         // Safety net of the split-precision mode: an activation beyond the fp16 range (|x| > 65000; never seen with
         // 8-bit images and sane weights) would turn into inf.  The kernels raise a flag in host-mapped memory, which
-        // cnn_finish() looks at after the one synchronisation the call needs anyway.
-        if (!ctx->cnn_flag_host) {
-            CK_HIP(ctx, hipHostMalloc((void**)&ctx->cnn_flag_host, 64, hipHostMallocMapped));
-            CK_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->cnn_flag_dev, ctx->cnn_flag_host, 0));
+        // cnn_run() looks at after the one synchronisation the call needs anyway.
+        if (!ctx->cnn_flag.p) {
+            CK_HIP(ctx, (hipError_t)ctx->cnn_flag.reserve(64, 64));
+            CK_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->cnn_flag_dev, ctx->cnn_flag.p, 0));
         }
-        *ctx->cnn_flag_host = 0;
-        CK_TRY(k_cnn_predict(ctx, d_goban, n, (float*)ctx->ybuf.p, (uint8_t*)ctx->lblbuf.p, (double*)ctx->confbuf.p, ctx->cnn_flag_dev,
-                             (uint8_t*)ctx->rlblbuf.p, (double*)ctx->rconfbuf.p));
-    } else {
-        CK_TRY(k_cnn_predict(ctx, d_goban, n, (float*)ctx->ybuf.p, (uint8_t*)ctx->lblbuf.p, (double*)ctx->confbuf.p, nullptr,
-                             (uint8_t*)ctx->rlblbuf.p, (double*)ctx->rconfbuf.p));
+        *(int*)ctx->cnn_flag.p = 0;
+        d_flag = ctx->cnn_flag_dev;
     }
-    if (ro.rec && ro.rec_space == CK_DEVICE)
-        CK_TRY(k_records_put_regions(ctx, (const uint8_t*)ctx->rlblbuf.p, (const double*)ctx->rconfbuf.p, n, ro.rec));
-    else if (ro.rec) {           // records in host memory: both region arrays to pinned staging, scattered after the call's sync
-        CK_TRY(ensure_rec_host(ctx, (size_t)n * 900));
-        CK_TRY(ck_from_device(ctx, ctx->rec_host, ctx->rconfbuf.p, (size_t)n * 800, CK_HOST));
-        CK_TRY(ck_from_device(ctx, (uint8_t*)ctx->rec_host + (size_t)n * 800, ctx->rlblbuf.p, (size_t)n * 100, CK_HOST));
+    CK_TRY(k_cnn_predict(ctx, d_goban, n, (float*)ctx->ybuf.p, (uint8_t*)ctx->lblbuf.p, (double*)ctx->confbuf.p, d_flag,
+                         (uint8_t*)ctx->rlblbuf.p, (double*)ctx->rconfbuf.p));
+    if (o.rec && o.rec_space == CK_DEVICE)
+        CK_TRY(k_records_put_regions(ctx, (const uint8_t*)ctx->rlblbuf.p, (const double*)ctx->rconfbuf.p, n, o.rec));
+    else if (o.rec) {            // records in host memory: both region arrays to pinned staging, scattered after the call's sync
+        CK_TRY(ck_ensure_pinned(ctx, ctx->rec_host, (size_t)n * 900, 4096));
+        CK_TRY(ck_from_device(ctx, ctx->rec_host.p, ctx->rconfbuf.p, (size_t)n * 800, CK_HOST));
+        CK_TRY(ck_from_device(ctx, (uint8_t*)ctx->rec_host.p + (size_t)n * 800, ctx->rlblbuf.p, (size_t)n * 100, CK_HOST));
     }
-    if (ro.label) CK_TRY(ck_from_device(ctx, ro.label, ctx->rlblbuf.p, (size_t)n * 100, out_space));
-    if (ro.conf) CK_TRY(ck_from_device(ctx, ro.conf, ctx->rconfbuf.p, (size_t)n * 100 * sizeof(double), out_space));
-    if (y) CK_TRY(ck_from_device(ctx, y, ctx->ybuf.p, (size_t)n * 8100 * sizeof(float), out_space));
-    if (labels) CK_TRY(ck_from_device(ctx, labels, ctx->lblbuf.p, (size_t)n * 361, out_space));
-    if (conf) CK_TRY(ck_from_device(ctx, conf, ctx->confbuf.p, (size_t)n * 361 * sizeof(double), out_space));
+    CK_TRY(ck_from_device(ctx, o.region_label, ctx->rlblbuf.p, (size_t)n * 100, o.space));
+    CK_TRY(ck_from_device(ctx, o.region_conf, ctx->rconfbuf.p, (size_t)n * 100 * sizeof(double), o.space));
+    CK_TRY(ck_from_device(ctx, o.y, ctx->ybuf.p, (size_t)n * 8100 * sizeof(float), o.space));
+    CK_TRY(ck_from_device(ctx, o.labels, ctx->lblbuf.p, (size_t)n * 361, o.space));
+    CK_TRY(ck_from_device(ctx, o.conf, ctx->confbuf.p, (size_t)n * 361 * sizeof(double), o.space));
     return CK_OK;
 }
 
-// synchronise; if the split-precision kernels flagged a value outside the fp16 range, recompute the batch with
-// the f32 kernels (the goban images are still in place) and deliver again
-static int cnn_finish(ck_ctx* ctx, const uint8_t* d_goban, int n, float* y, uint8_t* labels, double* conf, int out_space,
-                      RegionOut ro = RegionOut())
+// the classifier on n goban images in HBM, complete on return: predict and synchronise; if the split-precision kernels
+// flagged a value outside the fp16 range, the batch again with the f32 kernels (the images are still in place), delivered again
+static int cnn_run(ck_ctx* ctx, const uint8_t* d_goban, int n, const CnnOut& o)
 {
+    CK_TRY(cnn_predict_dev(ctx, d_goban, n, o));
     CK_TRY(finish(ctx));
-    if (ck_cnn_split(ctx->cnn_mode) && ctx->cnn_flag_host && *(volatile int*)ctx->cnn_flag_host) {
-        const int mode = ctx->cnn_mode;
-        ctx->cnn_mode = CK_CNN_FP32;
-        const int rc = cnn_predict_dev(ctx, d_goban, n, y, labels, conf, out_space, ro);
-        ctx->cnn_mode = mode;
-        ctx->cnn_fallbacks++;
-        if (rc) return rc;
-        return finish(ctx);
-    }
-    return CK_OK;
+    if (!cnn_overflowed(ctx)) return CK_OK;
+    const int mode = ctx->cnn_mode;
+    ctx->cnn_mode = CK_CNN_FP32;
+    const int rc = cnn_predict_dev(ctx, d_goban, n, o);
+    ctx->cnn_mode = mode;
+    ctx->cnn_fallbacks++;
+    if (rc) return rc;
+    return finish(ctx);
 }
 
 int ck_cnn_predict(ck_ctx* ctx, const uint8_t* goban, int n, int in_space,
                    float* y, uint8_t* labels, double* conf, int out_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "goban NULL or n <= 0");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_in));
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)d_in, n, y, labels, conf, out_space));
-    return cnn_finish(ctx, (const uint8_t*)d_in, n, y, labels, conf, out_space);
+    CnnOut o; o.y = y; o.labels = labels; o.conf = conf; o.space = out_space;
+    return cnn_run(ctx, (const uint8_t*)d_in, n, o);
     CK_API_END(ctx)
 }
 
 int ck_cnn_maps(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, float* pool2, float* pool4)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || n <= 0 || n > 128) return ck_fail(ctx, CK_ERR_ARG, "goban NULL or n outside 1 .. 128");
     const void* d_in;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_in));
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)d_in, n, nullptr, nullptr, nullptr, CK_HOST));
+    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)d_in, n, CnnOut()));     // (no cnn_run: these are the maps of this mode or none)
     CK_TRY(finish(ctx));
-    if (ck_cnn_split(ctx->cnn_mode) && ctx->cnn_flag_host && *(volatile int*)ctx->cnn_flag_host)
+    if (cnn_overflowed(ctx))
         return ck_fail(ctx, CK_ERR_STATE, "an activation left the fp16 range: the maps of this batch are the f32 chain's (set CK_CNN_FP32)");
     // after one chunk the pooled conv2 output is still in act1 and the pooled conv4 output in act2 (k_cnn_predict)
     const size_t np = (size_t)n * 100;
@@ -749,8 +767,8 @@ int ck_stones_detect(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int i
     CK_TRY(upload_minv(ctx, M, m_count, n, &d_minv));
     CK_TRY(ck_ensure(ctx, ctx->goban, (size_t)n * 380 * 380 * 3));
     CK_TRY(k_warp(ctx, (const uint8_t*)d_in, n, h, w, d_minv, m_count, 380, (uint8_t*)ctx->goban.p));
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)ctx->goban.p, n, nullptr, labels, conf, out_space));
-    return cnn_finish(ctx, (const uint8_t*)ctx->goban.p, n, nullptr, labels, conf, out_space);
+    CnnOut o; o.labels = labels; o.conf = conf; o.space = out_space;
+    return cnn_run(ctx, (const uint8_t*)ctx->goban.p, n, o);
     CK_API_END(ctx)
 }
 
@@ -758,32 +776,26 @@ int ck_cnn_regions(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, uint8
                    int out_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || n <= 0 || !region_label || !region_conf) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_in));
-    RegionOut ro; ro.label = region_label; ro.conf = region_conf;
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)d_in, n, nullptr, nullptr, nullptr, out_space, ro));
-    return cnn_finish(ctx, (const uint8_t*)d_in, n, nullptr, nullptr, nullptr, out_space, ro);
+    CnnOut o; o.region_label = region_label; o.region_conf = region_conf; o.space = out_space;
+    return cnn_run(ctx, (const uint8_t*)d_in, n, o);
     CK_API_END(ctx)
 }
 
 int ck_cnn_regions_records(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, ck_frame_record* rec, int rec_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || n <= 0 || !rec) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
     if (rec_space != CK_HOST && rec_space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", rec_space);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_in));
-    RegionOut ro; ro.rec = rec; ro.rec_space = rec_space;
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)d_in, n, nullptr, nullptr, nullptr, CK_HOST, ro));
-    CK_TRY(cnn_finish(ctx, (const uint8_t*)d_in, n, nullptr, nullptr, nullptr, CK_HOST, ro));
+    CnnOut o; o.rec = rec; o.rec_space = rec_space;
+    CK_TRY(cnn_run(ctx, (const uint8_t*)d_in, n, o));
     if (rec_space == CK_HOST) {
-        const double* conf = (const double*)ctx->rec_host;
-        const uint8_t* lab = (const uint8_t*)ctx->rec_host + (size_t)n * 800;
+        const double* conf = (const double*)ctx->rec_host.p;
+        const uint8_t* lab = (const uint8_t*)ctx->rec_host.p + (size_t)n * 800;
         for (int f = 0; f < n; f++) {
             memcpy(rec[f].region_conf, conf + (size_t)f * 100, 800);
             memcpy(rec[f].region_label, lab + (size_t)f * 100, 100);
@@ -804,8 +816,8 @@ int ck_board_detect_records(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w
     // then into the records -- a memcpy per record on the host, one upload + one small kernel for records in HBM
     const size_t part = offsetof(ck_frame_record, region_conf);
     const size_t lines_bytes = (size_t)n * CK_REC_LMAX * 2 * sizeof(float), res_bytes = (size_t)n * sizeof(ck_board_result);
-    CK_TRY(ensure_rec_host(ctx, (size_t)n * part + lines_bytes + res_bytes));
-    uint8_t* parts = (uint8_t*)ctx->rec_host;
+    CK_TRY(ck_ensure_pinned(ctx, ctx->rec_host, (size_t)n * part + lines_bytes + res_bytes, 4096));
+    uint8_t* parts = (uint8_t*)ctx->rec_host.p;
     float* lines = (float*)(parts + (size_t)n * part);
     ck_board_result* res = (ck_board_result*)((uint8_t*)lines + lines_bytes);
     CK_TRY(ck_board_detect(ctx, bgr, n, h, w, in_space, hough_thresh, lines, CK_REC_LMAX, res));
@@ -837,11 +849,10 @@ int ck_stones_run(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
     CK_TRY(check_img(ctx, bgr, n, h, w));
     if (!region_label || !region_conf) return ck_fail(ctx, CK_ERR_ARG, "region outputs are NULL");
     const bool bg = mog2_handle >= 0;
-    if (bg && (mog2_handle >= (int)ctx->mog2.size() || !ctx->mog2[mog2_handle].alive))
-        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", mog2_handle);
+    Mog2State* st = nullptr;
+    if (bg) CK_TRY(mog2_of(ctx, mog2_handle, &st));
     if (bg && (!learning_rates || !fgcount)) return ck_fail(ctx, CK_ERR_ARG, "a background model needs learning_rates and fgcount");
-    if (bg && (ctx->mog2[mog2_handle].h != 380 || ctx->mog2[mog2_handle].w != 380))
-        return ck_fail(ctx, CK_ERR_ARG, "the background model of a stones run is 380x380");
+    if (bg && (st->h != 380 || st->w != 380)) return ck_fail(ctx, CK_ERR_ARG, "the background model of a stones run is 380x380");
     const void* d_in;
     CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
     const double* d_minv;
@@ -849,14 +860,13 @@ int ck_stones_run(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
     CK_TRY(ck_ensure(ctx, ctx->goban, (size_t)n * 380 * 380 * 3));
     CK_TRY(k_warp(ctx, (const uint8_t*)d_in, n, h, w, d_minv, m_count, 380, (uint8_t*)ctx->goban.p));
     if (bg) {
-        int32_t* d_cnt = fgcount;
-        if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->fgcbuf, (size_t)n * 361 * sizeof(int32_t))); d_cnt = (int32_t*)ctx->fgcbuf.p; }
-        CK_TRY(k_mog2_run(ctx, ctx->mog2[mog2_handle], (const uint8_t*)ctx->goban.p, n, learning_rates, d_cnt, nullptr, 379, 379));
-        if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, fgcount, d_cnt, (size_t)n * 361 * sizeof(int32_t), CK_HOST));
+        OutStage<int32_t> cnt;
+        CK_TRY(cnt.open(ctx, fgcount, (size_t)n * 361 * sizeof(int32_t), out_space, ctx->fgcbuf));
+        CK_TRY(k_mog2_run(ctx, *st, (const uint8_t*)ctx->goban.p, n, learning_rates, cnt.dev, nullptr, 379, 379));
+        CK_TRY(cnt.deliver(ctx));
     }
-    RegionOut ro; ro.label = region_label; ro.conf = region_conf;
-    CK_TRY(cnn_predict_dev(ctx, (const uint8_t*)ctx->goban.p, n, nullptr, labels, conf, out_space, ro));
-    return cnn_finish(ctx, (const uint8_t*)ctx->goban.p, n, nullptr, labels, conf, out_space, ro);
+    CnnOut o; o.region_label = region_label; o.region_conf = region_conf; o.labels = labels; o.conf = conf; o.space = out_space;
+    return cnn_run(ctx, (const uint8_t*)ctx->goban.p, n, o);
     CK_API_END(ctx)
 }
 
@@ -864,19 +874,17 @@ int ck_mog2_band_run(ck_ctx* ctx, int handle, const uint8_t* band, int n, int in
                      int last_band, int32_t* counts, int out_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
-    if (handle < 0 || handle >= (int)ctx->mog2.size() || !ctx->mog2[handle].alive)
-        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", handle);
+    Mog2State* stp;
+    CK_TRY(mog2_of(ctx, handle, &stp));
     if (!band || !learning_rates || !counts || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
-    Mog2State& st = ctx->mog2[handle];
+    Mog2State& st = *stp;
     const size_t zones = (size_t)((st.h + 19) / 20) * ((st.w + 19) / 20);
     const void* d_in;
     CK_TRY(ck_to_device(ctx, band, (size_t)n * st.h * st.w * 3, in_space, ctx->in_stage, &d_in));
-    int32_t* d_cnt = counts;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->fgcbuf, (size_t)n * zones * sizeof(int32_t))); d_cnt = (int32_t*)ctx->fgcbuf.p; }
-    CK_TRY(k_mog2_run(ctx, st, (const uint8_t*)d_in, n, learning_rates, d_cnt, nullptr, last_band ? st.h - 1 : -1, st.w - 1));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, counts, d_cnt, (size_t)n * zones * sizeof(int32_t), CK_HOST));
+    OutStage<int32_t> cnt;
+    CK_TRY(cnt.open(ctx, counts, (size_t)n * zones * sizeof(int32_t), out_space, ctx->fgcbuf));
+    CK_TRY(k_mog2_run(ctx, st, (const uint8_t*)d_in, n, learning_rates, cnt.dev, nullptr, last_band ? st.h - 1 : -1, st.w - 1));
+    CK_TRY(cnt.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -884,15 +892,13 @@ int ck_mog2_band_run(ck_ctx* ctx, int handle, const uint8_t* band, int n, int in
 int ck_zone_counts(ck_ctx* ctx, const uint8_t* mask, int n, int in_space, int32_t* counts, int out_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!mask || !counts || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_in;
     CK_TRY(ck_to_device(ctx, mask, (size_t)n * 380 * 380, in_space, ctx->in_stage2, &d_in));
-    int32_t* d_cnt = counts;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->fgcbuf, (size_t)n * 361 * sizeof(int32_t))); d_cnt = (int32_t*)ctx->fgcbuf.p; }
-    CK_TRY(k_zone_counts(ctx, (const uint8_t*)d_in, n, 380, d_cnt));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, counts, d_cnt, (size_t)n * 361 * sizeof(int32_t), CK_HOST));
+    OutStage<int32_t> cnt;
+    CK_TRY(cnt.open(ctx, counts, (size_t)n * 361 * sizeof(int32_t), out_space, ctx->fgcbuf));
+    CK_TRY(k_zone_counts(ctx, (const uint8_t*)d_in, n, 380, cnt.dev));
+    CK_TRY(cnt.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -901,12 +907,10 @@ int ck_contour_stones(ck_ctx* ctx, const uint8_t* goban, const uint8_t* fg, int 
                       int rs, int re, int cs, int ce, uint8_t* stones, int16_t* zones, uint8_t* mask)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || !fg || !rects || !stones || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
     if (side < 19 * 4 || side > 4096) return ck_fail(ctx, CK_ERR_ARG, "goban image side %d", side);
     if (rs < 0 || cs < 0 || re > 19 || ce > 19 || re <= rs || ce <= cs)
         return ck_fail(ctx, CK_ERR_ARG, "intersection range rows [%d, %d) columns [%d, %d)", rs, re, cs, ce);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)n * side * side;
     const void *d_img, *d_fg;
     CK_TRY(ck_to_device(ctx, goban, px * 3, in_space, ctx->in_stage, &d_img));
@@ -921,11 +925,9 @@ int ck_cluster_stones(ck_ctx* ctx, const void* goban, int n, int side, int is_f3
                       float* centers, uint8_t* labels, long long labels_cap, int32_t* passes, double* compactness, int32_t* winner)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || !rects || !mask || !jobs || !stones || !trusted || n <= 0 || m <= 0)
         return ck_fail(ctx, CK_ERR_ARG, "NULL argument, n <= 0 or no job");
     if (side < 19 * 4 || side > 4096) return ck_fail(ctx, CK_ERR_ARG, "goban image side %d", side);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_img;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * side * side * 3 * (is_f32 ? 4 : 1), in_space, ctx->in_stage, &d_img));
     CK_TRY(k_cluster_stones(ctx, d_img, n, side, is_f32 != 0, rects, mask, jobs, m, stones, trusted, ratios, centers, labels,
@@ -984,10 +986,8 @@ int ck_find_intersections(ck_ctx* ctx, const uint8_t* goban, int n, int side, in
                           int16_t* grid, int16_t* lines, int32_t* nlines, uint8_t* edges)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     if (!goban || !mtx || !rects || !grid || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL argument or n <= 0");
     if (side < 19 * 4 || side > 4096) return ck_fail(ctx, CK_ERR_ARG, "goban image side %d", side);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_img;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * side * side * 3, in_space, ctx->in_stage, &d_img));
     const int16_t* found;
@@ -1025,11 +1025,8 @@ int ck_update_grid(const int32_t* lines, int k, const int32_t* box, int16_t* slo
 int ck_mog2_create(ck_ctx* ctx, int h, int w, int* handle)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx || !handle || h <= 0 || w <= 0) return CK_ERR_ARG;
-    CK_HIP(ctx, hipSetDevice(ctx->device));
-    int idx = -1;
-    for (size_t i = 0; i < ctx->mog2.size(); i++) if (!ctx->mog2[i].alive) { idx = (int)i; break; }
-    if (idx < 0) { ctx->mog2.emplace_back(); idx = (int)ctx->mog2.size() - 1; }
+    if (!handle || h <= 0 || w <= 0) return CK_ERR_ARG;
+    const int idx = free_slot(ctx->mog2);
     Mog2State& st = ctx->mog2[idx];
     st.h = h; st.w = w; st.nframes = 0; st.alive = true;
     const size_t npx = (size_t)h * w;
@@ -1047,19 +1044,17 @@ int ck_mog2_apply(ck_ctx* ctx, int handle, const uint8_t* img3, int in_space,
                   double learning_rate, uint8_t* fgmask, int out_space)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
-    if (handle < 0 || handle >= (int)ctx->mog2.size() || !ctx->mog2[handle].alive)
-        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", handle);
+    Mog2State* stp;
+    CK_TRY(mog2_of(ctx, handle, &stp));
     if (!img3 || !fgmask) return ck_fail(ctx, CK_ERR_ARG, "NULL image or mask");
-    CK_HIP(ctx, hipSetDevice(ctx->device));
-    Mog2State& st = ctx->mog2[handle];
+    Mog2State& st = *stp;
     const size_t npx = (size_t)st.h * st.w;
     const void* d_in;
     CK_TRY(ck_to_device(ctx, img3, npx * 3, in_space, ctx->in_stage, &d_in));
-    uint8_t* d_fg = fgmask;
-    if (out_space == CK_HOST) { CK_TRY(ck_ensure(ctx, ctx->out_stage, npx)); d_fg = (uint8_t*)ctx->out_stage.p; }
-    CK_TRY(k_mog2_apply(ctx, st, (const uint8_t*)d_in, learning_rate, d_fg));
-    if (out_space == CK_HOST) CK_TRY(ck_from_device(ctx, fgmask, d_fg, npx, CK_HOST));
+    OutStage<uint8_t> fg;
+    CK_TRY(fg.open(ctx, fgmask, npx, out_space, ctx->out_stage));
+    CK_TRY(k_mog2_apply(ctx, st, (const uint8_t*)d_in, learning_rate, fg.dev));
+    CK_TRY(fg.deliver(ctx));
     return finish(ctx);
     CK_API_END(ctx)
 }
@@ -1067,11 +1062,9 @@ int ck_mog2_apply(ck_ctx* ctx, int handle, const uint8_t* img3, int in_space,
 int ck_mog2_get_state(ck_ctx* ctx, int handle, float* weight, float* variance, float* mean, uint8_t* nmodes)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
-    if (handle < 0 || handle >= (int)ctx->mog2.size() || !ctx->mog2[handle].alive)
-        return ck_fail(ctx, CK_ERR_ARG, "bad mog2 handle %d", handle);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
-    const Mog2State& st = ctx->mog2[handle];
+    Mog2State* stp;
+    CK_TRY(mog2_of(ctx, handle, &stp));
+    const Mog2State& st = *stp;
     const size_t npx = (size_t)st.h * st.w;
     CK_TRY(ck_from_device(ctx, weight, st.weight.p, npx * 5 * sizeof(float), CK_HOST));
     CK_TRY(ck_from_device(ctx, variance, st.variance.p, npx * 5 * sizeof(float), CK_HOST));
@@ -1084,30 +1077,20 @@ int ck_mog2_get_state(ck_ctx* ctx, int handle, float* weight, float* variance, f
 int ck_mog2_destroy(ck_ctx* ctx, int handle)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx || handle < 0 || handle >= (int)ctx->mog2.size()) return CK_ERR_ARG;
+    if (handle < 0 || handle >= (int)ctx->mog2.size()) return CK_ERR_ARG;
     ctx->mog2[handle].alive = false;
     return CK_OK;
     CK_API_END(ctx)
 }
 
 // ---- training of the stone classifier (k_cnn_train.hip) -----------------------------------------------------------------
-static int trainer_of(ck_ctx* ctx, int handle, CkTrainer** tr)
-{
-    if (handle < 0 || handle >= (int)ctx->trainers.size() || !ctx->trainers[handle].alive)
-        return ck_fail(ctx, CK_ERR_ARG, "bad trainer handle %d", handle);
-    *tr = &ctx->trainers[handle];
-    return CK_OK;
-}
 
 int ck_train_create(ck_ctx* ctx, const float* const weights[12], int space, int* handle)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx || !weights || !handle) return CK_ERR_ARG;
+    if (!weights || !handle) return CK_ERR_ARG;
     for (int i = 0; i < 12; i++) if (!weights[i]) return ck_fail(ctx, CK_ERR_ARG, "weights[%d] is NULL", i);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
-    int idx = -1;
-    for (size_t i = 0; i < ctx->trainers.size(); i++) if (!ctx->trainers[i].alive) { idx = (int)i; break; }
-    if (idx < 0) { ctx->trainers.emplace_back(); idx = (int)ctx->trainers.size() - 1; }
+    const int idx = free_slot(ctx->trainers);
     CK_TRY(k_train_create(ctx, ctx->trainers[idx], weights, space));
     *handle = idx;
     return finish(ctx);
@@ -1117,12 +1100,10 @@ int ck_train_create(ck_ctx* ctx, const float* const weights[12], int space, int*
 int ck_train_destroy(ck_ctx* ctx, int handle)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(trainer_of(ctx, handle, &tr));
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    k_train_free(*tr);
+    *tr = CkTrainer();                              // dead, and its buffers freed
     return CK_OK;
     CK_API_END(ctx)
 }
@@ -1139,7 +1120,6 @@ static int train_pass(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* 
         return ck_fail(ctx, CK_ERR_ARG, "patches of shape %d x %d x %d x %d: expected n x 40 x 40 x 3 with n >= 1", n, h, w, c);
     for (int i = 0; i < n; i++)
         if (labels[i] > 80) return ck_fail(ctx, CK_ERR_ARG, "label %d of patch %d: a class index is 0 .. 80", (int)labels[i], i);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     const void* d_x;
     CK_TRY(ck_to_device(ctx, x, (size_t)n * 4800, in_space, ctx->in_stage, &d_x));
     CK_TRY(ck_ensure(ctx, tr->lab, (size_t)n));
@@ -1160,7 +1140,6 @@ int ck_train_step(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* labe
                   double lr, int dropout, uint64_t seed, float* loss)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(train_pass(ctx, handle, x, labels, n, h, w, c, in_space, dropout, seed, -1, false, loss, &tr));
     CK_TRY(k_train_adam(ctx, *tr, (const float*)tr->g.p, lr));
@@ -1173,7 +1152,6 @@ int ck_train_grads(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* lab
                    uint8_t* mask1, uint8_t* mask2, uint8_t* mask3)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     const bool masks = dropout && (mask1 || mask2 || mask3);
     CK_TRY(train_pass(ctx, handle, x, labels, n, h, w, c, in_space, dropout, seed, step, masks, loss, &tr));
@@ -1192,12 +1170,10 @@ int ck_train_grads(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* lab
 int ck_train_apply(ck_ctx* ctx, int handle, const float* const grads[12], double lr)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(trainer_of(ctx, handle, &tr));
     if (!grads) return ck_fail(ctx, CK_ERR_ARG, "grads is NULL");
     for (int i = 0; i < 12; i++) if (!grads[i]) return ck_fail(ctx, CK_ERR_ARG, "grads[%d] is NULL", i);
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < 12; i++)
         CK_HIP(ctx, hipMemcpyAsync((float*)tr->g.p + ck_train_offset(i), grads[i], CK_TRAIN_COUNTS[i] * sizeof(float),
                                    hipMemcpyHostToDevice, ctx->stream));
@@ -1217,10 +1193,8 @@ static int train_get(ck_ctx* ctx, const DevBuf& src, float* const dst[12])
 int ck_train_get_weights(ck_ctx* ctx, int handle, float* const weights[12])
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(trainer_of(ctx, handle, &tr));
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     CK_TRY(train_get(ctx, tr->w, weights));
     return finish(ctx);
     CK_API_END(ctx)
@@ -1229,10 +1203,8 @@ int ck_train_get_weights(ck_ctx* ctx, int handle, float* const weights[12])
 int ck_train_get_adam_state(ck_ctx* ctx, int handle, float* const m[12], float* const v[12], long long* steps)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(trainer_of(ctx, handle, &tr));
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     CK_TRY(train_get(ctx, tr->m, m));
     CK_TRY(train_get(ctx, tr->v, v));
     if (steps) *steps = tr->steps;
@@ -1243,10 +1215,8 @@ int ck_train_get_adam_state(ck_ctx* ctx, int handle, float* const m[12], float* 
 int ck_train_handover(ck_ctx* ctx, int handle)
 {
     CK_API_BEGIN(ctx)
-    if (!ctx) return CK_ERR_ARG;
     CkTrainer* tr;
     CK_TRY(trainer_of(ctx, handle, &tr));
-    CK_HIP(ctx, hipSetDevice(ctx->device));
     CK_TRY(finish(ctx));
     const float* w[12];
     for (int i = 0; i < 12; i++) w[i] = (const float*)tr->w.p + ck_train_offset(i);

@@ -17,10 +17,16 @@
 #include <vector>
 
 #include "../../include/camkifu_amd.h"
+#include "ck_buf.h"        // DevBuf, PinBuf: buffers that free themselves
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
+// the context's stream, destroyed with it
+struct CkStream {
+    hipStream_t s = nullptr;
+    CkStream() = default;
+    CkStream(const CkStream&) = delete;
+    CkStream& operator=(const CkStream&) = delete;
+    ~CkStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
 struct TimingSlot {
@@ -38,10 +44,9 @@ struct Mog2State {
     DevBuf weight, variance, mean, nmodes;
     bool alive = false;
     // learning rates of an ordered run: the model's own pinned staging + device copy (k_mog2_run)
-    float* rates_host = nullptr;
-    float* rates_dev = nullptr;
-    size_t rates_cap = 0;
-    hipEvent_t rates_done = nullptr;
+    PinBuf rates_host;
+    DevBuf rates_dev;
+    hipEvent_t rates_done = nullptr;     // (events stay plain handles: ~ck_ctx destroys them)
     bool rates_busy = false;
 };
 
@@ -75,19 +80,24 @@ struct CnnWeights {
     bool q8_ok = false;  // every weight inside the e4m3 range of its block scale (else the mode runs the three-MFMA kernels)
 };
 
+// Members are destroyed last to first: the stream is declared before every buffer, so it outlives them all.
 struct ck_ctx {
     // One thread at a time (include/camkifu_amd.h): `owner` is the token of the thread inside an entry point, 0 when
     // nobody is; a second thread gets CK_ERR_STATE instead of a silent race on the stream and the scratch buffers.
     std::atomic<unsigned long long> owner{0};
     int depth = 0;                   // entry points calling entry points on the owner's thread
     int device = 0;
-    hipStream_t stream = nullptr;
+    CkStream stream;
     std::string err;
     bool timing = false;
     std::map<std::string, TimingSlot> slots;
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     hipEvent_t handover = nullptr;   // ck_stream_wait: recorded on the host framework's stream, waited for on ours
+    // pinned host memory: two arenas (the contour survey has the second, so that a caller's data in the first survives),
+    // and the staging of per-frame result records (ck_board_detect_records / ck_cnn_regions_records): one half of n records
+    PinBuf host_pinned, host_pinned2, rec_host;
+    PinBuf cnn_flag{CK_PIN_MAPPED};  // host-mapped flag: the split-precision kernels met a value outside the fp16 range
 
     // scratch (grown on demand, never shrunk)
     DevBuf in_stage;     // staged host input
@@ -113,31 +123,24 @@ struct ck_ctx {
     DevBuf out_stage;
     DevBuf mats;
     DevBuf pyr0, pyr1;   // pyramid levels between the first and the last (ping-pong)
-    void* host_pinned = nullptr;
-    size_t host_pinned_cap = 0;
-    void* host_pinned2 = nullptr;    // second arena (contour survey) so that a caller's data in the first one survives
-    size_t host_pinned2_cap = 0;
-    // per-frame result records (ck_board_detect_records / ck_cnn_regions_records): pinned staging of one half of n records,
-    // and its device twin for records that live in HBM
-    void* rec_host = nullptr;
-    size_t rec_host_cap = 0;
-    DevBuf rec_stage;
+    DevBuf rec_stage;    // the device twin of rec_host, for records that live in HBM
 
     CnnWeights cnn;
-    int* cnn_flag_host = nullptr;    // host-mapped flag: the split-precision kernels met a value outside the fp16 range
-    int* cnn_flag_dev = nullptr;
+    int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
     int cnn_fallbacks = 0;           // batches the split-precision mode handed back to the f32 kernels
     int cnn_mode = CK_CNN_F16X2;     // f32-accurate and 2.3x faster than the k-ordered f32 chain (CK_CNN_FP32)
     std::vector<Mog2State> mog2;
     std::vector<CkTrainer> trainers;
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
+
+    ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
 };
 
 extern thread_local std::string g_ck_create_error;
 
 int ck_fail(ck_ctx* ctx, int code, const char* fmt, ...);
 int ck_ensure(ck_ctx* ctx, DevBuf& b, size_t bytes);
-int ck_ensure_pinned(ck_ctx* ctx, size_t bytes, int which = 0);
+int ck_ensure_pinned(ck_ctx* ctx, PinBuf& b, size_t bytes, size_t slack = 0);     // grows to bytes + bytes / 4 + slack
 
 #define CK_HIP(ctx, call)                                                                 \
     do {                                                                                  \
@@ -180,6 +183,8 @@ struct CtxCall {
         if (ctx && --ctx->depth == 0) ctx->owner.store(0, std::memory_order_release);
     }
 };
+// From CK_API_BEGIN on, ctx is not NULL, this thread owns it, and the HIP device of this thread is ctx->device: an entry
+// point neither checks the first nor sets the second again.
 #define CK_API_BEGIN(ctx)                         \
     CtxCall call__(ctx);                          \
     if (call__.code != CK_OK) return call__.code; \
@@ -281,7 +286,6 @@ int k_cnn_q8_conv34(ck_ctx* ctx, const float* p2, int np, float* p4, int* overfl
 extern const size_t CK_TRAIN_COUNTS[12];
 size_t ck_train_offset(int i);
 int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int space);
-void k_train_free(CkTrainer& tr);
 int k_train_grads(ck_ctx* ctx, CkTrainer& tr, const uint8_t* d_x, const uint8_t* d_lab, int n, int drop, uint64_t seed,
                   uint64_t step, bool want_masks);
 int k_train_adam(ck_ctx* ctx, CkTrainer& tr, const float* d_g, double lr);

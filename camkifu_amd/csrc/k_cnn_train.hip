@@ -420,18 +420,6 @@ int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int spa
     return CK_OK;
 }
 
-void k_train_free(CkTrainer& tr)
-{
-    DevBuf* bufs[] = { &tr.w, &tr.g, &tr.m, &tr.v, &tr.lab, &tr.a1, &tr.a2, &tr.p1, &tr.a3, &tr.a4, &tr.p2, &tr.h1, &tr.lg, &tr.dlg,
-                       &tr.dh1, &tr.dp2, &tr.dz4, &tr.dz3, &tr.dp1, &tr.dz2, &tr.dz1, &tr.part, &tr.lossv, &tr.mask1, &tr.mask2, &tr.mask3 };
-    for (DevBuf* b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    tr.alive = false;
-}
-
 // Gradients of the mean loss over the n patches d_x (device, n x 40 x 40 x 3) with labels d_lab (device, n bytes, 0..80) into
 // tr.g, the per-patch losses into tr.lossv; with want_masks (and dropout) the keep-masks into tr.mask1 .. mask3.
 // The batch goes through in chunks of CK_TRAIN_CHUNK patches; the chunks' gradient sums are added in chunk order.

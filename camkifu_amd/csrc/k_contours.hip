@@ -1592,8 +1592,8 @@ int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, s
     CK_TRY(ck_ensure(ctx, ctx->pts, npts * 8 + (size_t)(n + 1) * 4 + 64));
     int32_t* d_pts = (int32_t*)ctx->pts.p;
     int32_t* d_base = d_pts + npts * 2;
-    CK_TRY(ck_ensure_pinned(ctx, npts * 8 + 64, 1));
-    int32_t* hp = (int32_t*)ctx->host_pinned2;
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, npts * 8 + 64));
+    int32_t* hp = (int32_t*)ctx->host_pinned2.p;
     {
         TimeScope ts(ctx, "survey_gather");
         CK_HIP(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -261,9 +261,9 @@ int k_grid_lines(ck_ctx* ctx, const uint8_t* d_goban, int n, int side, const int
         CK_HIP(ctx, hipGetLastError());
     }
     int over = 0;
-    CK_TRY(ck_ensure_pinned(ctx, line_bytes + cnt_bytes + 64));       // the tables are mostly empty: a pinned landing area, read in place
-    int16_t* lines = (int16_t*)ctx->host_pinned;
-    int32_t* nlines = (int32_t*)((char*)ctx->host_pinned + line_bytes);
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, line_bytes + cnt_bytes + 64));       // the tables are mostly empty: a pinned landing area, read in place
+    int16_t* lines = (int16_t*)ctx->host_pinned.p;
+    int32_t* nlines = (int32_t*)((char*)ctx->host_pinned.p + line_bytes);
     *lines_out = lines;
     *nlines_out = nlines;
     CK_HIP(ctx, hipMemcpyAsync(lines, d_lines, line_bytes + cnt_bytes, hipMemcpyDeviceToHost, ctx->stream));

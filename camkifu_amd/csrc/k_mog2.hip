@@ -293,28 +293,25 @@ int k_mog2_run(ck_ctx* ctx, Mog2State& st, const uint8_t* d_gobans, int n, const
         if (learning_rates[f] >= 1) return ck_fail(ctx, CK_ERR_ARG, "mog2 run: learning rate >= 1 (model reset) inside a run");
     // the rates travel through the model's OWN pinned + device buffers (not the context's shared scratch)
     const size_t rbytes = (size_t)n * 2 * sizeof(float);
-    if (st.rates_cap < rbytes) {
-        if (st.rates_host) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // a queued run may still read the old ones
-        if (st.rates_host) (void)hipHostFree(st.rates_host);
-        if (st.rates_dev) (void)hipFree(st.rates_dev);
-        st.rates_host = nullptr; st.rates_dev = nullptr; st.rates_cap = 0;
+    if (st.rates_host.cap < rbytes || st.rates_dev.cap < rbytes) {
+        if (st.rates_host.p) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));    // a queued run may still read the old ones
         const size_t cap = rbytes < 4096 ? 4096 : rbytes * 2;
-        CK_HIP(ctx, hipHostMalloc((void**)&st.rates_host, cap, hipHostMallocDefault));
-        CK_HIP(ctx, hipMalloc((void**)&st.rates_dev, cap));
-        st.rates_cap = cap;
+        CK_HIP(ctx, (hipError_t)st.rates_host.reserve(rbytes, cap));
+        CK_HIP(ctx, (hipError_t)st.rates_dev.reserve(rbytes, cap));
     } else if (st.rates_busy) {
         CK_HIP(ctx, hipEventSynchronize(st.rates_done));                        // previous upload has left the host buffer
     }
     if (!st.rates_done) CK_HIP(ctx, hipEventCreateWithFlags(&st.rates_done, hipEventDisableTiming));
-    for (int f = 0; f < n; f++) mog2_rate(st, learning_rates[f], &st.rates_host[2 * (size_t)f], &st.rates_host[2 * (size_t)f + 1]);
-    CK_HIP(ctx, hipMemcpyAsync(st.rates_dev, st.rates_host, rbytes, hipMemcpyHostToDevice, ctx->stream));
+    float* rates = (float*)st.rates_host.p;
+    for (int f = 0; f < n; f++) mog2_rate(st, learning_rates[f], &rates[2 * (size_t)f], &rates[2 * (size_t)f + 1]);
+    CK_HIP(ctx, hipMemcpyAsync(st.rates_dev.p, rates, rbytes, hipMemcpyHostToDevice, ctx->stream));
     CK_HIP(ctx, hipEventRecord(st.rates_done, ctx->stream));
     st.rates_busy = true;
     const int zrows = (st.h + ZONE - 1) / ZONE, zcols = (st.w + ZONE - 1) / ZONE;
     const int blocks = 8 * ((zrows + 7) / 8) * zcols;               // XCD k <- zone rows k, k + 8, ... (see the kernel)
     hipLaunchKernelGGL(mog2_run_kernel, dim3(blocks), dim3(ZTHREADS), (size_t)n * sizeof(int), ctx->stream,
                        d_gobans, n, st.h, st.w, skip_row, skip_col, (float*)st.weight.p, (float*)st.variance.p, (float*)st.mean.p,
-                       (uint8_t*)st.nmodes.p, (const float2*)st.rates_dev, d_fgcount, d_last_fg);
+                       (uint8_t*)st.nmodes.p, (const float2*)st.rates_dev.p, d_fgcount, d_last_fg);
     CK_HIP(ctx, hipGetLastError());
     return CK_OK;
 }

@@ -210,9 +210,9 @@ int k_contour_stones(ck_ctx* ctx, const uint8_t* d_goban, const uint8_t* d_fg, i
         hipLaunchKernelGGL(crop_bgr_kernel, dim3((ws * 3 + 255) / 256, hs, n), dim3(256), 0, ctx->stream, d_goban, side, x0, y0, hs, ws, d_sub);
         CK_HIP(ctx, hipGetLastError());
     }
-    CK_TRY(ck_ensure_pinned(ctx, npx));
-    const uint8_t* h_fg = (const uint8_t*)ctx->host_pinned;
-    CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, d_subfg, npx, hipMemcpyDeviceToHost, ctx->stream));
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, npx));
+    const uint8_t* h_fg = (const uint8_t*)ctx->host_pinned.p;
+    CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, d_subfg, npx, hipMemcpyDeviceToHost, ctx->stream));
     CK_TRY(k_canny_planar(ctx, (const uint8_t*)ctx->planes.p, n, hs, ws, pitch, 25, 75, (uint8_t*)ctx->map.p,
                           (int32_t*)ctx->labels.p, d_edges, nullptr));
     lap("open + fg canny");

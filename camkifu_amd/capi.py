@@ -14,7 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("CK_HIP_LIB") or os.path.join(_HERE, "libck_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
+CK_OK, CK_ERR_ARG, CK_ERR_HIP, CK_ERR_CAPACITY, CK_ERR_STATE, CK_ERR_DATA = 0, 1, 2, 3, 4, 5
 CK_HOST, CK_DEVICE = 0, 1
+CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
@@ -25,7 +27,7 @@ EXPORTS = [
     "ck_ctx_create", "ck_ctx_create_prio", "ck_ctx_destroy", "ck_ctx_destroy2", "ck_stream_wait", "ck_last_error", "ck_backend", "ck_version", "ck_stream",
     "ck_timing_enable", "ck_timing_reset", "ck_timing_get",
     "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
-    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_get_perspective_transform", "ck_warp_perspective",
+    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_jpeg_probe", "ck_jpeg_coefficients", "ck_jpeg_reconstruct", "ck_jpeg_decode", "ck_jpeg_bad_frame", "ck_get_perspective_transform", "ck_warp_perspective",
     "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
@@ -63,7 +65,15 @@ assert REC_BYTES == 1440
 
 
 class CkError(RuntimeError):
-    pass
+    """`code`: the CK_ERR_* status of the call that failed (None where Python refused before calling); `bad_frame`: for a
+    JPEG batch the decoder refused, the index of the stream it is about (else None)"""
+    code = None
+    bad_frame = None
+
+
+class JpegInfo(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("sampling", C.c_int32), ("restart_interval", C.c_int32),
+                ("blocks", C.c_int32)]                     # ck_jpeg_info
 
 
 def build(force=False):
@@ -123,6 +133,11 @@ def lib():
                                      + [C.c_int, C.c_uint64, C.c_longlong] + [C.c_void_p] * 5)
         L.ck_train_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
         L.ck_rng_set.argtypes = [C.c_void_p, C.c_uint64]
+        L.ck_jpeg_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ck_jpeg_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.ck_jpeg_reconstruct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
+        L.ck_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.ck_jpeg_bad_frame.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -185,7 +200,9 @@ class Context:
 
     def _chk(self, rc):
         if rc != 0:
-            raise CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(self._h) or b"").decode()))
+            err = CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(self._h) or b"").decode()))
+            err.code = rc
+            raise err
 
     # ---- timing -------------------------------------------------------------------------
     def timing_enable(self, on=True):
@@ -388,6 +405,57 @@ class Context:
             self._chk(lib().ck_i420_to_bgr_pyr(self._h, p, n, int(h), int(w), levels, sp, op, osp))
         else:
             self._chk(lib().ck_i420_to_bgr(self._h, p, n, int(h), int(w), sp, op, osp))
+        return out
+
+    def jpeg_decode(self, streams, to_device=None, out=None):
+        """baseline JPEG streams (a list of bytes-like objects or uint8 arrays in host memory, all of the first one's size
+        and sampling) -> BGR frames (n, h, w, 3), bit for bit what cv2.imread gives.  Huffman decoding runs on the host (the
+        frames of a batch in parallel), everything after it in one kernel.  `to_device`: a torch device to leave the frames
+        in HBM; `out`: a preallocated (n, h, w, 3) array / tensor to fill.  CkError with code CK_ERR_DATA and a message
+        that names the frame and the cause for a stream the decoder refuses or that is damaged."""
+        ptrs, lens, keep = _jpeg_streams(streams)
+        n = len(keep)
+        rc, info, why = _jpeg_probe(keep[0])          # (the size of the output comes from the first stream's headers)
+        if rc != 0:
+            err = CkError("libck_hip error %d: frame 0: %s" % (rc, why))
+            err.code, err.bad_frame = rc, 0
+            raise err
+        oshape = (n, info["h"], info["w"], 3)
+        if out is not None:
+            _check_array(out, oshape, np.uint8, "out")
+            op, osp, _ = self._in(out)
+        elif to_device is not None:
+            out, op, osp = self._out_on(to_device, oshape, np.uint8)
+        else:
+            out, op, osp = self._out(None, oshape, np.uint8)
+        rc = lib().ck_jpeg_decode(self._h, ptrs, lens, n, op, osp)
+        if rc == CK_ERR_DATA:
+            bad = C.c_int32(-1)
+            err = CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(self._h) or b"").decode()))
+            err.code = rc
+            if lib().ck_jpeg_bad_frame(self._h, C.byref(bad)) == 0 and bad.value >= 0:
+                err.bad_frame = bad.value
+            raise err
+        self._chk(rc)
+        return out
+
+    def jpeg_reconstruct(self, coef, quant, h, w, sampling, out=None):
+        """the GPU half alone: coefficients (n, blocks * 64) int16 and quant tables (n, 3, 64) uint16 as jpeg_coefficients
+        gives them (numpy arrays, or torch tensors in HBM) -> BGR (n, h, w, 3) in the memory space of the input"""
+        n, h, w, sampling = int(coef.shape[0]), int(h), int(w), int(sampling)
+        # the library cannot know how much memory lies behind its pointers: sizes and element types are held here
+        _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
+        _check_array(quant, (n, 3, 64), (np.uint16, np.int16), "quant")          # (torch below 2.3 has no uint16: the bits count)
+        cp, sp, keep = self._in(coef, np.int16)
+        qp, qsp, keep2 = self._in(quant, np.asarray(quant).dtype if not _is_torch(quant) else np.uint16)
+        if sp != qsp:
+            raise CkError("coef and quant must lie in the same memory space")
+        if out is None:
+            out, op, osp = self._out(coef, (n, h, w, 3), np.uint8)
+        else:
+            _check_array(out, (n, h, w, 3), np.uint8, "out")
+            op, osp, _ = self._in(out)
+        self._chk(lib().ck_jpeg_reconstruct(self._h, cp, qp, n, int(h), int(w), int(sampling), sp, op, osp))
         return out
 
     def pyr_down(self, frames, levels=1, out=None):
@@ -803,6 +871,86 @@ class Context:
         found = [{divmod(z, 19): [tuple(int(v) for v in lines[f, z, k]) for k in range(counts[f, z])]
                   for z in np.nonzero(counts[f])[0]} for f in range(n)]
         return (grid[0], found[0], edges[0]) if single else (grid, found, edges)
+
+
+def _host_error(rc):
+    err = CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(None) or b"").decode()))
+    err.code = rc
+    return err
+
+
+def jpeg_blocks(h, w, sampling):
+    """8x8 blocks of one frame, all components, on the MCU-padded grid (ck_jpeg_info.blocks)"""
+    if sampling not in (CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420) or h <= 0 or w <= 0:
+        raise CkError("bad JPEG geometry %dx%d sampling %r" % (w, h, sampling))
+    hs, vs = (2 if sampling >= CK_JPEG_422 else 1), (2 if sampling == CK_JPEG_420 else 1)
+    return -(-w // (8 * hs)) * -(-h // (8 * vs)) * (hs * vs + (0 if sampling == CK_JPEG_GREY else 2))
+
+
+def _check_array(a, shape, dtypes, what):
+    """a numpy array or torch tensor the library reads or writes in place: shape, element type, contiguity -- else CkError"""
+    dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+    if _is_torch(a):
+        name, contiguous = str(a.dtype).replace("torch.", ""), a.is_contiguous()
+    elif isinstance(a, np.ndarray):
+        name, contiguous = a.dtype.name, a.flags.c_contiguous
+    else:
+        raise CkError("%s: a numpy array or a torch tensor is needed, got %s" % (what, type(a).__name__))
+    if tuple(a.shape) != tuple(shape) or name not in [np.dtype(d).name for d in dtypes] or not contiguous:
+        raise CkError("%s: a contiguous %s array of shape %r is needed, got %s %r" % (
+            what, "/".join(np.dtype(d).name for d in dtypes), tuple(shape), name, tuple(a.shape)))
+
+
+def _jpeg_streams(streams):
+    """-> (array of pointers, array of lengths, the uint8 arrays that own the bytes)"""
+    keep = [np.ascontiguousarray(np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview)) else s, np.uint8).reshape(-1)
+            for s in streams]
+    if not keep:
+        raise CkError("no JPEG stream given")
+    ptrs = (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+    lens = (C.c_size_t * len(keep))(*[a.size for a in keep])
+    return ptrs, lens, keep
+
+
+def _jpeg_probe(stream):
+    """-> (status, dict or None, the library's message)"""
+    ptrs, lens, keep = _jpeg_streams([stream])
+    info = JpegInfo()
+    rc = lib().ck_jpeg_probe(C.c_void_p(keep[0].ctypes.data), keep[0].size, C.byref(info))
+    if rc != 0:
+        return rc, None, (lib().ck_last_error(None) or b"").decode()
+    return 0, dict(h=info.h, w=info.w, sampling=info.sampling, restart_interval=info.restart_interval, blocks=info.blocks), ""
+
+
+def jpeg_probe(stream):
+    """the headers of one baseline JPEG stream -> dict(h, w, sampling (CK_JPEG_*), restart_interval, blocks); host only.
+    CkError (code CK_ERR_DATA) for a stream the decoder refuses, with the cause."""
+    rc, info, why = _jpeg_probe(stream)
+    if rc != 0:
+        err = CkError("libck_hip error %d: %s" % (rc, why))
+        err.code = rc
+        raise err
+    return info
+
+
+def jpeg_coefficients(streams):
+    """the Huffman stage alone (host only): streams of one geometry -> (info of the first, coef (n, blocks * 64) int16,
+    quant (n, 3, 64) uint16) in the layout of ck_jpeg_coefficients.  CkError (CK_ERR_DATA) names the frame that failed;
+    its index is the error's `bad_frame`."""
+    ptrs, lens, keep = _jpeg_streams(streams)
+    n = len(keep)
+    info = jpeg_probe(keep[0])
+    geom = JpegInfo(info["h"], info["w"], info["sampling"], info["restart_interval"], info["blocks"])
+    coef = np.empty((n, info["blocks"] * 64), np.int16)
+    quant = np.empty((n, 3, 64), np.uint16)
+    bad = C.c_int32(-1)
+    rc = lib().ck_jpeg_coefficients(ptrs, lens, n, C.byref(geom), coef.ctypes.data_as(C.c_void_p),
+                                    quant.ctypes.data_as(C.c_void_p), C.byref(bad))
+    if rc != 0:
+        err = _host_error(rc)
+        err.bad_frame = bad.value
+        raise err
+    return info, coef, quant
 
 
 def get_perspective_transform(src4, dst4):

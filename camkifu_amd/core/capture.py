@@ -5,13 +5,16 @@ CaptureReader (core/vmanager.py:461-635): when the input is a file, frames are s
 only `cvconf.file_fps` frames per second of video are analysed, and every active VidProcessor
 receives the same sequence of frames (lock-step).  Video decoding itself is a third-party
 library there and is not rebuilt here; the captures below quack like cv2.VideoCapture over
-uncompressed containers:
+uncompressed containers and over the one compressed format that decodes exactly, frame by frame: baseline JPEG
+(ck_jpeg_decode: Huffman decoding on the host, everything after it in one GPU kernel, bit for bit cv2.imread's numbers):
 
   Y4MCapture   .y4m (YUV4MPEG2, 4:2:0 planar): frames stay I420 on the host (1.5 B/px) and are
                converted to BGR on the GPU (ck_i420_to_bgr) -- read() for one frame,
                read_raw_batch() for the fast-file pipeline; with `levels` set, read() converts and
                downsamples in one kernel (ck_i420_to_bgr_pyr)
   ArrayCapture an (n, h, w, 3) uint8 array or .npy file of BGR frames (memory mapped)
+  AviMjpegCapture  .avi holding Motion-JPEG: the file is memory mapped, the frames' JPEG bytes go to the decoder as they lie
+  ImageCapture     a .jpg / .jpeg still, served over and over (the reference's CaptureReaderImg)
 
 cv2 property ids are kept so CaptureReaderBase.skip reads like the reference's.
 
@@ -20,6 +23,7 @@ CaptureReaderBase.downsample(ret, img) is the reference's extension point of the
 documented use, cv2.pyrDown(img), is what `cvconf.downsample = N` switches on here (N levels, on the GPU).
 """
 import os
+import struct
 import threading
 import time
 
@@ -242,10 +246,246 @@ class Y4MCapture:
         self._mm = None
 
 
+class AviError(ValueError):
+    pass
+
+
+def write_mjpeg_avi(path, jpeg_frames, h, w, fps=(30, 1)):
+    """a RIFF 'AVI ' container around JPEG byte strings (one '00dc' chunk each; an empty string gives the zero-length
+    chunk that stands for "repeat the previous frame").  Container only: nothing is encoded here.  fps: (rate, scale)."""
+    frames = [bytes(f) for f in jpeg_frames]
+    rate, scale = (int(fps[0]), int(fps[1])) if isinstance(fps, (tuple, list)) else (int(round(float(fps) * 1000)), 1000)
+
+    def chunk(cc, body):
+        return cc + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+
+    def lst(kind, body):
+        return b"LIST" + struct.pack("<I", len(body) + 4) + kind + body
+
+    biggest = max([len(f) for f in frames] or [0])
+    avih = struct.pack("<14I", int(1e6 * scale / max(1, rate)), 0, 0, 0, len(frames), 0, 1, biggest, w, h, 0, 0, 0, 0)
+    strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIIIhhhh", 0, 0, 0, 0, scale, rate, 0, len(frames), biggest, 0xFFFFFFFF, 0,
+                                          0, 0, w, h)
+    strf = struct.pack("<IiiHH", 40, w, h, 1, 24) + b"MJPG" + struct.pack("<IiiII", w * h * 3, 0, 0, 0, 0)
+    hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
+    movi = lst(b"movi", b"".join(chunk(b"00dc", f) for f in frames))
+    body = b"AVI " + hdrl + movi
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
+class AviMjpegCapture:
+    """cv2.VideoCapture look-alike over Motion-JPEG in an AVI container.  The file is memory mapped and walked once:
+    hdrl/avih, the first 'vids' stream's strh (fps = dwRate / dwScale) and strf (biCompression or the stream handler must
+    be MJPG), then the ##dc / ##db chunks of movi in file order; an idx1 chunk is ignored.  Frames are handed out as their
+    JPEG bytes (read_raw_batch, views of the mapping) or as BGR through `decode`, a callable (list of byte strings) ->
+    (n, h, w, 3) BGR -- by default jpeg_decode of the process-wide Context.
+
+    An empty chunk, or one whose headers the decoder refuses (capi.jpeg_probe), stands for a repeat of the previous good
+    frame, as players take it; such chunks are counted in `.damaged`.  Before any good frame it is a failed read.
+    Only the first video stream is read: chunks of other streams (a second video stream, audio) are passed over.
+    OpenDML ('AVIX') extensions are not read: frames beyond the first RIFF chunk (files above 1 GiB or so) are ignored."""
+
+    def __init__(self, path, decode=None):
+        self.path = path
+        self.decode = decode
+        self.pos = 0
+        self.damaged = 0
+        self.error = None
+        self._mm = None
+        self._chunks = []                       # (offset, length) of every video chunk
+        self._good = None                       # per chunk: index of the chunk whose picture it shows (-1: none yet)
+        try:
+            self._open(path)
+        except (OSError, AviError, struct.error) as exc:
+            self.error = exc
+            self._mm = None
+
+    def _open(self, path):
+        mm = np.memmap(path, dtype=np.uint8, mode="r")
+        if len(mm) < 12 or bytes(mm[:4]) != b"RIFF" or bytes(mm[8:12]) != b"AVI ":
+            raise AviError("not a RIFF AVI file: " + path)
+        end = min(len(mm), 8 + struct.unpack("<I", bytes(mm[4:8]))[0])
+        st = dict(w=0, h=0, fps=0.0, handler=b"", comp=b"", vids=False, done=False, streams=0, tag=b"")
+        chunks = []
+        # the RIFF tree, walked with a stack of our own (no recursion: a file decides how deep its lists nest).  An entry
+        # is (next byte, end, inside movi); 'rec ' lists inside movi group chunks and are walked like movi itself.
+        stack = [(12, end, False)]
+        while stack:
+            p, stop, in_movi = stack.pop()
+            if p + 8 > stop:
+                continue
+            cc = bytes(mm[p:p + 4])
+            ln = struct.unpack("<I", bytes(mm[p + 4:p + 8]))[0]
+            body = p + 8
+            stack.append((body + ln + (ln & 1), stop, in_movi))              # the sibling after this chunk
+            if cc == b"LIST":
+                if len(stack) > 64:
+                    raise AviError("lists nested more than 64 deep")
+                if body + 4 <= stop:
+                    kind = bytes(mm[body:body + 4])
+                    stack.append((body + 4, min(stop, body + ln), kind == b"movi" or (in_movi and kind == b"rec ")))
+            elif cc == b"strh":
+                hd = bytes(mm[body:min(stop, body + ln)])
+                if not st["done"]:
+                    st["vids"] = hd[:4] == b"vids"
+                    if st["vids"] and len(hd) >= 28:
+                        st["handler"] = hd[4:8]
+                        scale, rate = struct.unpack("<II", hd[20:28])
+                        st["fps"] = rate / scale if scale else 0.0
+                        st["tag"] = b"%02d" % st["streams"]                # its chunks are '##dc' / '##db', ## its number
+                st["streams"] += 1
+            elif cc == b"strf" and st["vids"] and not st["done"]:
+                bi = bytes(mm[body:min(stop, body + ln)])
+                if len(bi) < 20:
+                    raise AviError("short stream format")
+                st["w"], st["h"] = struct.unpack("<ii", bi[4:12])
+                st["h"] = abs(st["h"])
+                st["comp"] = bi[16:20]
+                st["done"] = True
+            elif in_movi and st["done"] and cc[:2] == st["tag"] and cc[2:4] in (b"dc", b"db"):
+                chunks.append((body, max(0, min(ln, stop - body))))
+        if not st["done"]:
+            raise AviError("no video stream")
+        if b"MJPG" not in (st["comp"].upper(), st["handler"].upper()):
+            raise AviError("the video stream is %r / %r, only MJPG is read" % (st["comp"], st["handler"]))
+        if st["w"] <= 0 or st["h"] <= 0:
+            raise AviError("bad frame size")
+        self.w, self.h, self.fps = st["w"], st["h"], st["fps"] or 30.0
+        # which picture every chunk shows: itself when its headers are a baseline JPEG of the stream's size, else the
+        # last chunk that was
+        from .. import capi
+        good, last = [], -1
+        for k, (o, ln) in enumerate(chunks):
+            ok = False
+            if ln:
+                try:
+                    info = capi.jpeg_probe(mm[o:o + ln])
+                    ok = info["h"] == self.h and info["w"] == self.w
+                except capi.CkError:
+                    ok = False
+            if ok:
+                last = k
+            else:
+                self.damaged += 1
+            good.append(last)
+        self._mm, self._chunks, self._good = mm, chunks, good
+
+    def isOpened(self):
+        return self._mm is not None
+
+    def __len__(self):
+        return len(self._chunks)
+
+    def read_raw_batch(self, indices):
+        """the JPEG bytes of frames `indices` as views of the mapping (no copy); a repeat frame gives the bytes of the
+        frame it repeats, None where there is no good frame yet.  Does not move the read position."""
+        out = []
+        for i in indices:
+            g = self._good[i]
+            out.append(None if g < 0 else self._mm[self._chunks[g][0]:self._chunks[g][0] + self._chunks[g][1]])
+        return out
+
+    def read(self, caller=None):
+        if self._mm is None or self.pos >= len(self._chunks):
+            return False, None
+        raw = self.read_raw_batch([self.pos])[0]
+        self.pos += 1
+        if raw is None:
+            return False, None
+        decode = self.decode
+        if decode is None:
+            from .. import capi
+            decode = capi.get_context().jpeg_decode
+            self.decode = decode
+        return True, np.asarray(decode([raw]))[0]
+
+    def get(self, prop):
+        if prop == CAP_PROP_POS_FRAMES:
+            return float(self.pos)
+        if prop == CAP_PROP_FRAME_COUNT:
+            return float(len(self._chunks))
+        if prop == CAP_PROP_FPS:
+            return self.fps
+        if prop == CAP_PROP_POS_AVI_RATIO:
+            return self.progress()
+        if prop == CAP_PROP_FRAME_WIDTH:
+            return float(self.w)
+        if prop == CAP_PROP_FRAME_HEIGHT:
+            return float(self.h)
+        return 0.0
+
+    def set(self, prop, value):
+        if prop == CAP_PROP_POS_FRAMES:
+            self.pos = int(value)
+            return True
+        if prop == CAP_PROP_POS_AVI_RATIO:
+            self.seek(value)
+            return True
+        return False
+
+    def progress(self):
+        return self.pos / max(1, len(self._chunks))
+
+    def seek(self, ratio):
+        self.pos = int(ratio * len(self._chunks))
+
+    def release(self):
+        self._mm = None
+
+
+class ImageCapture:
+    """The reference's CaptureReaderImg (core/vmanager.py:638-660) for a .jpg / .jpeg still: the image is decoded once
+    (`decode` as for AviMjpegCapture) and every read() returns a copy of it; get() returns 0 whatever is asked, and
+    nothing sleeps."""
+
+    def __init__(self, path, decode=None):
+        self.path = path
+        self.img = None
+        self.error = None
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+            if decode is None:
+                from .. import capi
+                decode = capi.get_context().jpeg_decode
+            self.img = np.asarray(decode([data]))[0]
+        except (OSError, RuntimeError) as exc:
+            self.error = exc
+
+    def isOpened(self):
+        return self.img is not None
+
+    def read(self, caller=None):
+        if self.img is None:
+            return False, None
+        return True, self.img.copy()
+
+    def get(self, prop):
+        return 0
+
+    def set(self, prop, value):            # (the reference's reader ignores every other call)
+        return False
+
+    def seek(self, ratio):
+        pass
+
+    def progress(self):
+        return 0
+
+    def release(self):
+        pass
+
+
 def open_capture(video, convert=None):
-    """the capture for a controller's `video` attribute: an array, a .npy path or a .y4m path"""
+    """the capture for a controller's `video` attribute: an array, a .npy path, a .y4m path, an MJPEG .avi path or a
+    .jpg / .jpeg still"""
     if isinstance(video, str) and video.lower().endswith(".y4m"):
         return Y4MCapture(video, convert=convert)
+    if isinstance(video, str) and video.lower().endswith(".avi"):
+        return AviMjpegCapture(video)
+    if isinstance(video, str) and video.lower().endswith((".jpg", ".jpeg")):
+        return ImageCapture(video)
     return ArrayCapture(video)
 
 

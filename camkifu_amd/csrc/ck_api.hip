@@ -3,6 +3,7 @@
 // which the stage kernels are launched on the context's stream.
 #include <stdarg.h>
 #include <stddef.h>
+#include <stdlib.h>
 
 #include <cfloat>
 #include <cmath>
@@ -13,6 +14,7 @@
 
 #include "ck_common.h"
 #include "ck_stonegeom.h"
+#include "ck_jpeg.h"
 
 thread_local std::string g_ck_create_error;
 static thread_local const ck_ctx* g_ck_busy_ctx = nullptr;     // the context that refused this thread's last call
@@ -595,6 +597,164 @@ int ck_i420_to_bgr_pyr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, in
     if (levels > 1) CK_TRY(pyr_levels(ctx, d_first, n, h / 2, w / 2, 2, levels, o.dev));
     CK_TRY(o.deliver(ctx));
     return finish(ctx);
+    CK_API_END(ctx)
+}
+
+// ---- baseline JPEG: host half (ck_jpeg.cpp) behind the ABI, and the two calls that reach the GPU ----
+int ck_jpeg_probe(const uint8_t* data, size_t len, ck_jpeg_info* info)
+{
+    if (!info) return ck_fail(nullptr, CK_ERR_ARG, "info is NULL");
+    try {
+        auto f = std::make_unique<CkJpegFrame>();
+        char msg[CK_JPEG_MSG];
+        const int rc = ck_jpeg_parse(data, len, f.get(), msg);
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "%s", msg);
+        *info = f->info;
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+// the Huffman stage of n frames, in parallel: coef n * geom.blocks * 64, quant n * 192.  On failure *bad is the first
+// frame that failed and `why` its message.
+static int jpeg_entropy_batch(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info& geom, int16_t* coef,
+                              uint16_t* quant, int* bad, std::string& why)
+{
+    std::vector<int> rcs((size_t)n, CK_OK);
+    std::vector<std::string> msgs((size_t)n);
+    ck_parallel_for(n, 16, [&](int f) {
+        auto fr = std::make_unique<CkJpegFrame>();
+        char msg[CK_JPEG_MSG];
+        int rc = ck_jpeg_parse(data[f], len[f], fr.get(), msg);
+        if (rc == CK_OK && (fr->info.h != geom.h || fr->info.w != geom.w || fr->info.sampling != geom.sampling)) {
+            snprintf(msg, sizeof msg, "%dx%d sampling %d where the batch is %dx%d sampling %d", fr->info.w, fr->info.h,
+                     fr->info.sampling, geom.w, geom.h, geom.sampling);
+            rc = CK_ERR_DATA;
+        }
+        if (rc == CK_OK) rc = ck_jpeg_entropy(data[f], len[f], *fr, coef + (size_t)f * geom.blocks * 64, msg);
+        if (rc == CK_OK) memcpy(quant + (size_t)f * 192, fr->quant, 192 * sizeof(uint16_t));
+        rcs[f] = rc;
+        if (rc != CK_OK) msgs[f] = msg;
+    });
+    for (int f = 0; f < n; f++)
+        if (rcs[f] != CK_OK) { *bad = f; why = msgs[f]; return rcs[f]; }
+    return CK_OK;
+}
+
+static int check_jpeg_geom(ck_ctx* ctx, int h, int w, int sampling, long long blocks)
+{
+    if (h <= 0 || w <= 0 || h > 65535 || w > 65535) return ck_fail(ctx, CK_ERR_ARG, "bad JPEG frame size %dx%d", w, h);
+    if (sampling < CK_JPEG_GREY || sampling > CK_JPEG_420) return ck_fail(ctx, CK_ERR_ARG, "bad JPEG sampling %d", sampling);
+    if (blocks >= 0 && blocks != ck_jpeg_blocks(h, w, sampling))
+        return ck_fail(ctx, CK_ERR_ARG, "%lld blocks where a %dx%d frame of sampling %d has %lld", blocks, w, h, sampling,
+                       ck_jpeg_blocks(h, w, sampling));
+    if ((long long)h * w > (1LL << 28)) return ck_fail(ctx, CK_ERR_ARG, "image too large");
+    return CK_OK;
+}
+
+int ck_jpeg_coefficients(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                         int16_t* coef, uint16_t* quant, int32_t* bad_frame)
+{
+    if (bad_frame) *bad_frame = -1;
+    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
+    try {
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_entropy_batch(data, len, n, *geom, coef, quant, &bad, why);
+        if (rc != CK_OK) {
+            if (bad_frame) *bad_frame = bad;
+            return ck_fail(nullptr, rc, "frame %d: %s", bad, why.c_str());
+        }
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_jpeg_reconstruct(ck_ctx* ctx, const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling,
+                        int in_space, uint8_t* bgr, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    if (!coef || !quant || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
+    const size_t cbytes = (size_t)n * (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
+    const void *d_coef, *d_quant;
+    CK_TRY(ck_to_device(ctx, coef, cbytes, in_space, ctx->in_stage, &d_coef));
+    CK_TRY(ck_to_device(ctx, quant, (size_t)n * 192 * sizeof(uint16_t), in_space, ctx->in_stage2, &d_quant));
+    if (((uintptr_t)d_coef | (uintptr_t)d_quant) & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients and quant tables must lie on 16 bytes");
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, bgr, (size_t)n * h * w * 3, out_space, ctx->out_stage));
+    CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)d_coef, (const uint16_t*)d_quant, n, h, w, sampling, o.dev));
+    CK_TRY(o.deliver(ctx));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+// frames per pass of ck_jpeg_decode: the pinned block and its device twin hold the coefficients of one pass, not of the
+// whole batch (a 1080p 4:2:0 frame is 6.2 MB of coefficients, a batch of 256 would pin 1.6 GB) -- 256 MB, or what
+// CK_JPEG_PASS_BYTES says (a developer knob: the tests set it to a few KB to run several passes on small frames)
+static int jpeg_pass_frames(int n, size_t frame_bytes)
+{
+    size_t budget = (size_t)256 << 20;
+    if (const char* e = getenv("CK_JPEG_PASS_BYTES")) {
+        const long long v = atoll(e);
+        if (v > 0) budget = (size_t)v;
+    }
+    const size_t fit = budget / (frame_bytes ? frame_bytes : 1);
+    return fit < 1 ? 1 : (fit < (size_t)n ? (int)fit : n);
+}
+
+int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    ctx->jpeg_bad_frame = -1;
+    if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    auto first = std::make_unique<CkJpegFrame>();
+    char msg[CK_JPEG_MSG];
+    const int rc0 = ck_jpeg_parse(data[0], len[0], first.get(), msg);
+    if (rc0 != CK_OK) { ctx->jpeg_bad_frame = 0; return ck_fail(ctx, rc0, "frame 0: %s", msg); }
+    const ck_jpeg_info geom = first->info;
+    CK_TRY(check_jpeg_geom(ctx, geom.h, geom.w, geom.sampling, geom.blocks));
+    const size_t cframe = (size_t)geom.blocks * 64 * sizeof(int16_t), qframe = 192 * sizeof(uint16_t);
+    const size_t oframe = (size_t)geom.h * geom.w * 3;
+    const int pass = jpeg_pass_frames(n, cframe + qframe);
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
+    // per pass: coefficients, then quant tables, in one pinned block -> one upload -> the kernel.  The stream is waited
+    // for before the next pass decodes into the same block.
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, (size_t)pass * (cframe + qframe)));
+    for (int f0 = 0; f0 < n; f0 += pass) {
+        const int m = n - f0 < pass ? n - f0 : pass;
+        const size_t cbytes = (size_t)m * cframe, qbytes = (size_t)m * qframe;
+        int16_t* coef = (int16_t*)ctx->host_pinned.p;
+        uint16_t* quant = (uint16_t*)((uint8_t*)ctx->host_pinned.p + cbytes);
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_entropy_batch(data + f0, len + f0, m, geom, coef, quant, &bad, why);
+        if (rc != CK_OK) {
+            ctx->jpeg_bad_frame = f0 + bad;
+            (void)hipStreamSynchronize(ctx->stream);
+            return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+        }
+        const void* d_in;
+        CK_TRY(ck_to_device(ctx, coef, cbytes + qbytes, CK_HOST, ctx->in_stage, &d_in));
+        CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)d_in, (const uint16_t*)((const uint8_t*)d_in + cbytes), m, geom.h, geom.w,
+                                  geom.sampling, o.dev + (size_t)f0 * oframe));
+        if (f0 + pass < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    CK_TRY(o.deliver(ctx));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame)
+{
+    CK_API_BEGIN(ctx)
+    if (!frame) return ck_fail(ctx, CK_ERR_ARG, "frame is NULL");
+    *frame = ctx->jpeg_bad_frame;
+    return CK_OK;
     CK_API_END(ctx)
 }
 

@@ -131,6 +131,7 @@ struct ck_ctx {
     int cnn_mode = CK_CNN_F16X2;     // f32-accurate and 2.3x faster than the k-ordered f32 chain (CK_CNN_FP32)
     std::vector<Mog2State> mog2;
     std::vector<CkTrainer> trainers;
+    int jpeg_bad_frame = -1;         // ck_jpeg_decode: the frame its last CK_ERR_DATA is about (-1: none)
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
@@ -244,6 +245,8 @@ int k_i420_to_bgr(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uint8
 // (h, w even): bit for bit k_pyr_down of k_i420_to_bgr without the full-size BGR frames (k_pyramid.hip)
 int k_pyr_down(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, uint8_t* d_out);
 int k_i420_pyr_down(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uint8_t* d_out);
+// baseline JPEG behind the Huffman decoder (k_jpeg.hip): coefficients + quant tables of n frames on the device -> BGR
+int k_jpeg_reconstruct(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* d_quant, int n, int h, int w, int sampling, uint8_t* d_bgr);
 int k_warp(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, const double* d_minv, int m_count,
            int dsize, uint8_t* d_out);
 int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,

@@ -1383,3 +1383,51 @@ class FastFilePipeline:
             if out is not None:
                 emitted.extend(out)
         return emitted
+
+    def process_mjpeg(self, capture, batch=256, file_fps=None, torch_device=None, downsample=0):
+        """process_y4m for a Motion-JPEG file (core.capture.AviMjpegCapture): the same frame selection and the same deal of
+        the frames to the ranks; each rank decodes ITS frames straight into HBM (ck_jpeg_decode: the Huffman stage on the
+        host's worker threads, the coefficients uploaded in passes of about 256 MB, one kernel per pass) and the batch goes
+        through process_batch.
+        `downsample` = N > 0: the decoded frames go through N levels of pyrDown on the device first (no fusion with the
+        decoder); the pipeline must have been built for capi.pyr_shape(h, w, N).
+        A frame whose entropy-coded data is damaged, or that has no good frame before it, raises CkError naming the frame's
+        number in the file -- on EVERY rank (the ranks exchange one word per batch before any of them enters the batch's
+        collectives), with the cause on the rank that owns the frame.  Returns the concatenated request lists (rank 0)."""
+        import torch
+        from . import capi
+        from .core.capture import file_frame_indices
+        downsample = int(downsample)
+        fh, fw = capi.pyr_shape(capture.h, capture.w, downsample)
+        idx = file_frame_indices(len(capture), capture.fps, file_fps)
+        dev = torch_device if torch_device is not None else torch.device("cuda", getattr(self.ctx, "device", 0))
+        emitted = []
+        for b0 in range(0, len(idx), batch):
+            chunk = idx[b0:b0 + batch]
+            mine = [chunk[k] for k in shard_indices(len(chunk), self.rank, self.world)]
+            frames, bad, why, code = None, -1, None, capi.CK_ERR_DATA    # bad: the file's number of the frame that cannot be decoded
+            raw = capture.read_raw_batch(mine)
+            missing = [i for i, r in zip(mine, raw) if r is None]
+            if missing:
+                bad, why = missing[0], "no good frame before it"
+            elif len(mine):
+                try:
+                    frames = self.ctx.jpeg_decode(raw, to_device=dev)
+                    if downsample:
+                        frames = self.ctx.pyr_down(frames, downsample)
+                except capi.CkError as exc:                     # (any other failure of the decode: charged to the shard's first frame)
+                    bad, why, code = mine[exc.bad_frame or 0], str(exc), exc.code
+            else:
+                frames = torch.empty((0, fh, fw, 3), dtype=torch.uint8, device=dev)
+            worst = bad + 1
+            if self.world > 1:
+                worst = self.group.max_flag(worst)              # nobody goes into the batch alone
+            if worst > 0:
+                err = capi.CkError("frame %d of %s: %s" % (worst - 1, capture.path,
+                                                           why if bad == worst - 1 else "refused on another rank"))
+                err.code, err.bad_frame = code, worst - 1
+                raise err
+            out = self.process_batch(frames, len(chunk))
+            if out is not None:
+                emitted.extend(out)
+        return emitted

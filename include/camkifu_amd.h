@@ -21,13 +21,15 @@
 #ifndef CAMKIFU_AMD_H
 #define CAMKIFU_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { CK_OK = 0, CK_ERR_ARG = 1, CK_ERR_HIP = 2, CK_ERR_CAPACITY = 3, CK_ERR_STATE = 4 };
+enum { CK_OK = 0, CK_ERR_ARG = 1, CK_ERR_HIP = 2, CK_ERR_CAPACITY = 3, CK_ERR_STATE = 4,
+       CK_ERR_DATA = 5 /* the input bytes are not what the call can read: a JPEG stream it refuses or that is damaged */ };
 enum { CK_HOST = 0, CK_DEVICE = 1 };
 enum { CK_BACKEND_HIP = 1 };
 enum { CK_CNN_FP32 = 0, CK_CNN_BF16 = 1, CK_CNN_F16X2 = 2, CK_CNN_F16Q8 = 3 };
@@ -120,6 +122,40 @@ int ck_board_detect(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in
  * i420: n frames of h*w*3/2 bytes; bgr: n x h x w x 3.  h and w must be even. */
 int ck_i420_to_bgr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, int in_space,
                    uint8_t* bgr, int out_space);
+
+/* ---- frame source, compressed: baseline JPEG (Motion-JPEG frames of an .avi, .jpg stills)   core/vmanager.py:638-660 (cv2.imread),
+ * stone/nn_manager.py:134.  The numbers are libjpeg's default decode path (slow-integer IDCT, "fancy" chroma upsampling,
+ * fixed-point YCbCr -> RGB): what cv2.imread and Pillow give, bit for bit.  Two halves:
+ *   host: marker parser + Huffman decoder -> per frame int16 coefficient blocks (component-planar: Y, then Cb, then Cr;
+ *         blocks in raster order over the MCU-padded block grid; 64 values per block in natural, de-zigzagged order; not
+ *         dequantised) and uint16 quant[3][64] (natural order, by component, table selectors resolved);
+ *   GPU:  one kernel: dequantise, inverse DCT, upsample, convert, interleaved BGR (n x h x w x 3) out.
+ * Accepted: SOF0, 8-bit, one component (grey: Y is written three times) or three taken as Y Cb Cr with luma sampling 1x1,
+ * 2x1 or 2x2 and chroma 1x1, one interleaved scan, with or without restart intervals; a frame without DHT is decoded with the
+ * tables of Annex K.3.  Everything else -- other frame types, other samplings, an Adobe APP14 segment with transform 0, several
+ * scans, damaged entropy-coded data -- is CK_ERR_DATA with a message that names the cause (host-only calls: ck_last_error(NULL)). */
+enum { CK_JPEG_GREY = 0, CK_JPEG_444 = 1, CK_JPEG_422 = 2, CK_JPEG_420 = 3 };
+typedef struct ck_jpeg_info {
+    int32_t h, w;
+    int32_t sampling;          /* CK_JPEG_*                                                   */
+    int32_t restart_interval;  /* MCUs between restart markers, 0: none                       */
+    int32_t blocks;            /* 8x8 blocks per frame, all components, on the MCU-padded grid */
+} ck_jpeg_info;
+/* the headers of one stream (host only) */
+int ck_jpeg_probe(const uint8_t* data, size_t len, ck_jpeg_info* info);
+/* n streams that all have the geometry *geom (h, w, sampling; else CK_ERR_DATA) -> coef n * geom->blocks * 64 int16 and
+ * quant n * 3 * 64 uint16 (host only; frames decode in parallel on the library's worker threads).  On CK_ERR_DATA *bad_frame
+ * (nullable) is the first frame that failed. */
+int ck_jpeg_coefficients(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                         int16_t* coef, uint16_t* quant, int32_t* bad_frame);
+/* coefficients + quant tables of n frames of h x w (in `in_space`, both) -> bgr */
+int ck_jpeg_reconstruct(ck_ctx* ctx, const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling,
+                        int in_space, uint8_t* bgr, int out_space);
+/* the three steps in one call: n streams in HOST memory, all of the first one's geometry -> bgr.  The coefficients are
+ * decoded into pinned memory of the context and go up in one copy (a large batch in passes of about 256 MB each). */
+int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space);
+/* the frame the context's last ck_jpeg_decode refused with CK_ERR_DATA, -1 when it refused none */
+int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame);
 
 /* ---- frame downsampling: CaptureReaderBase.downsample's cv2.pyrDown(img)   core/vmanager.py:484-498
  * OpenCV 3.1.0 pyrDown of 8-bit 3-channel frames, BORDER_DEFAULT, applied `levels` times: per level h x w becomes

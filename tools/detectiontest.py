@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Headless DetectionTest (mirror of the reference's test/mains/detectiontest.py / benchmark.py):
-a video (frames saved with np.save, or a synthetic clip) + a reference SGF -> move-sequence
+a video (frames saved with np.save, a .y4m or Motion-JPEG .avi file, or a synthetic clip) + a reference SGF -> move-sequence
 match ratio.  Runs the drop-in finders (BoardFinderAuto + SfNeural) on the HIP library.
 
     python tools/detectiontest.py --synthetic 640x480 --frames 200
     python tools/detectiontest.py -v clip.npy --sgf game.sgf [--bf BoardFinderAuto --sf SfNeural]
+    python tools/detectiontest.py -v film.avi --sgf film.sgf          (a file on disk is thinned to cvconf.file_fps, as the reference does)
     python tools/detectiontest.py --synthetic 3840x2160 --frames 200 --downsample 1      (finders work on 1920x1080)
 """
 import argparse
@@ -24,7 +25,7 @@ from camkifu_amd.kifu_checker import KifuChecker, report  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("-v", "--video", help=".npy file holding (n,h,w,3) uint8 BGR frames")
+    ap.add_argument("-v", "--video", help=".npy file holding (n,h,w,3) uint8 BGR frames, or a .y4m / Motion-JPEG .avi file")
     ap.add_argument("--sgf", help="reference SGF")
     ap.add_argument("--synthetic", default=None, help="WxH: render a clip and its reference game instead")
     ap.add_argument("--frames", type=int, default=200)
@@ -52,7 +53,9 @@ def main():
                 ref.append(Move(NP_TYPE, ("EBW"[col], r, c)))
         name = "synthetic-%dx%d" % (w, h)
     else:
-        frames, ref, name = np.load(args.video, mmap_mode="r"), Kifu(sgffile=args.sgf), os.path.basename(args.video)
+        ref, name = Kifu(sgffile=args.sgf), os.path.basename(args.video)
+        # containers go to the manager by path (core.capture.open_capture picks the reader); arrays are loaded here
+        frames = args.video if args.video.lower().endswith((".y4m", ".avi")) else np.load(args.video, mmap_mode="r")
     ctrl = ControllerHeadless(video=frames)
     vm = VManagerSeq(ctrl, bf=args.bf, sf=args.sf)
     t0 = time.time()

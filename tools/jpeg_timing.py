@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Timing of the Motion-JPEG frame source, in ONE process on one GPU -> profiles/jpeg_timing.json
+
+A filmed game (synth.film) at 1920x1080 is encoded with Pillow as baseline JPEG, 4:2:0, quality 90, and held in host memory.
+1. host: the Huffman stage alone (capi.jpeg_coefficients), ms per frame -- one frame per call (one thread) and the whole
+   batch per call (the library's worker threads, at most 16); warmed up, `--reps` alternating rounds, median / min / max.
+2. kernel: ck_jpeg_reconstruct on a batch of coefficients resident in HBM, output preallocated, HIP-event time
+   (ck_timing_get("jpeg")) per frame, and the achieved bytes/s against the compulsory 6 * W * H bytes of a 4:2:0 frame
+   (int16 coefficients in, BGR out) and the HBM peak.
+3. end to end: FastFilePipeline.process_mjpeg on the JPEG film against process_y4m on the same film held as I420 (the path
+   that existed before), frames/s in alternating rounds, and the game record of each against the film's moves.
+
+    python tools/jpeg_timing.py [--size 1920x1080] [--film 128] [--n 32] [--reps 7] [--inner 8] [--e2e-reps 5]
+
+Needs Pillow (to encode).  There is no CPU fallback: without a GPU the first device call raises."""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ingest_timing import HBM_PEAK, I420Clip, game_quality, i420_of, spread_of  # noqa: E402
+
+
+class MjpegClip:
+    """what process_mjpeg asks of a capture, over JPEG byte strings in host memory; file frame k is clip frame k // 2 (see
+    ingest_timing.I420Clip)"""
+    path = "<memory>"
+
+    def __init__(self, jpegs, h, w, fps=5.0):
+        self.jpegs, self.h, self.w, self.fps = jpegs, h, w, float(fps)
+
+    def __len__(self):
+        return 2 * len(self.jpegs)
+
+    def read_raw_batch(self, indices):
+        return [self.jpegs[i // 2] for i in indices]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--film", type=int, default=128, help="frames of the filmed game")
+    ap.add_argument("--n", type=int, default=32, help="frames per batch of the host and kernel legs")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=8, help="kernel calls per round")
+    ap.add_argument("--batch", type=int, default=32, help="frames per pipeline batch")
+    ap.add_argument("--e2e-reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_timing.json"))
+    args = ap.parse_args(argv)
+    if args.reps < 5 or args.e2e_reps < 5:
+        raise SystemExit("at least 5 alternating rounds per leg")
+    from PIL import Image
+    import torch
+    from camkifu_amd import capi, pipeline, synth
+    from camkifu_amd.controller import ControllerHeadless
+    from camkifu_amd.stone.nn_manager import NNManager
+    w, h = (int(v) for v in args.size.lower().split("x"))
+    ctx = capi.Context(0)
+    dev = torch.device("cuda", 0)
+    F, n = args.film, min(args.n, args.film)
+    out = dict(tool="tools/jpeg_timing.py", device=torch.cuda.get_device_name(0),
+               plan=dict(height=h, width=w, sampling="4:2:0", quality=args.quality, film_frames=F, batch=n, rounds=args.reps,
+                         kernel_calls_per_round=args.inner, e2e_rounds=args.e2e_reps, pipeline_batch=args.batch))
+    film, corners, truth, moves, hands = synth.film(F, h, w, seed=synth.SEED, device=dev, quiet=52, move_every=32, hand_frames=12)
+    i420 = torch.empty((F, h * w * 3 // 2), dtype=torch.uint8).pin_memory()
+    jpegs = []
+    for b0 in range(0, F, 8):
+        part = film[b0:b0 + 8]
+        i420[b0:b0 + 8].copy_(i420_of(part))
+        for fr in part.cpu().numpy():
+            buf = io.BytesIO()
+            Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1]), "RGB").save(buf, "JPEG", quality=args.quality, subsampling=2)
+            jpegs.append(np.frombuffer(buf.getvalue(), np.uint8))
+    del film
+    torch.cuda.empty_cache()
+    out["plan"]["jpeg_bytes_per_frame"] = int(np.mean([j.size for j in jpegs]))
+    try:
+        # 1. host
+        batch = jpegs[:n]
+        capi.jpeg_coefficients(batch)
+        capi.jpeg_coefficients(batch[:1])
+        one, many = [], []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            for j in batch:
+                capi.jpeg_coefficients([j])
+            one.append((time.perf_counter() - t0) * 1e3 / n)
+            t0 = time.perf_counter()
+            capi.jpeg_coefficients(batch)
+            many.append((time.perf_counter() - t0) * 1e3 / n)
+        out["host_entropy_decode"] = dict(one_thread_ms_per_frame=spread_of(one), sixteen_threads_ms_per_frame=spread_of(many),
+                                          cpus_seen=os.cpu_count(),
+                                          note="includes the allocation of the coefficient array of each call")
+        # 2. kernel
+        info, coef, quant = capi.jpeg_coefficients(batch)
+        d_coef, d_quant = torch.from_numpy(coef).to(dev), torch.from_numpy(quant.view(np.int16)).to(dev)
+        bgr = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        for _ in range(3):
+            ctx.jpeg_reconstruct(d_coef, d_quant, h, w, info["sampling"], out=bgr)
+        same = bool(np.array_equal(bgr[:2].cpu().numpy(), ctx.jpeg_decode(batch[:2])))
+        ctx.timing_enable(True)
+        ms = []
+        for _ in range(args.reps):
+            ctx.timing_reset()
+            for _ in range(args.inner):
+                ctx.jpeg_reconstruct(d_coef, d_quant, h, w, info["sampling"], out=bgr)
+            ms.append(ctx.timing_get("jpeg")[0] / (args.inner * n))
+        ctx.timing_enable(False)
+        s = spread_of(ms)
+        floor = 6 * w * h
+        moved = info["blocks"] * 128 + h * w * 3
+        out["kernel"] = dict(per_frame=s, floor_bytes_per_frame=floor, bytes_per_frame_with_mcu_padding=moved,
+                             gb_per_s_against_floor=round(floor / (s["median_ms"] * 1e-3) / 1e9, 1),
+                             share_of_hbm_peak=round(floor / (s["median_ms"] * 1e-3) / HBM_PEAK, 4), two_halves_equal_decode=same)
+        del d_coef, d_quant, bgr
+        torch.cuda.empty_cache()
+        # 3. end to end
+        ctx.cnn_set_weights(NNManager.init_net())
+        clips = dict(mjpeg=MjpegClip(jpegs, h, w), y4m=I420Clip(i420.numpy(), h, w))
+
+        def run(kind):
+            p = pipeline.FastFilePipeline(h, w, ControllerHeadless(), ctx=ctx)
+            try:
+                t0 = time.perf_counter()
+                reqs = (p.process_mjpeg if kind == "mjpeg" else p.process_y4m)(clips[kind], batch=args.batch)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, reqs, p.mtx is not None
+            finally:
+                p.close()
+        first = {k: run(k) for k in clips}
+        secs = {k: [] for k in clips}
+        for _ in range(args.e2e_reps):
+            for k in clips:
+                secs[k].append(run(k)[0])
+        res = {}
+        for k in clips:
+            fps = sorted(F / t for t in secs[k])
+            res[k] = dict(frames_per_s=dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1),
+                                            spread=round((fps[-1] - fps[0]) / float(np.median(fps)), 4), rounds=len(fps)),
+                          board_found=bool(first[k][2]), game_record=game_quality(first[k][1], truth, moves, F))
+        res["mjpeg_over_y4m"] = round(res["mjpeg"]["frames_per_s"]["median"] / res["y4m"]["frames_per_s"]["median"], 3)
+        host_fps = 1e3 / out["host_entropy_decode"]["sixteen_threads_ms_per_frame"]["median_ms"]
+        res["host_entropy_frames_per_s"] = round(host_fps, 1)
+        res["host_entropy_bounds_the_rate"] = bool(host_fps < 1.5 * res["mjpeg"]["frames_per_s"]["median"])
+        out["end_to_end"] = res
+    finally:
+        ctx.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1317,7 +1317,7 @@ int ck_train_grads(ck_ctx* ctx, int handle, const uint8_t* x, const uint8_t* lab
     CK_TRY(train_pass(ctx, handle, x, labels, n, h, w, c, in_space, dropout, seed, step, masks, loss, &tr));
     if (grads)
         for (int i = 0; i < 12; i++)
-            CK_TRY(ck_from_device(ctx, grads[i], (const float*)tr->g.p + ck_train_offset(i), CK_TRAIN_COUNTS[i] * sizeof(float), CK_HOST));
+            CK_TRY(ck_from_device(ctx, grads[i], (const float*)tr->g.p + ck_cnn_offset(i), CK_CNN_COUNTS[i] * sizeof(float), CK_HOST));
     if (masks) {
         CK_TRY(ck_from_device(ctx, mask1, tr->mask1.p, (size_t)n * 8192, CK_HOST));
         CK_TRY(ck_from_device(ctx, mask2, tr->mask2.p, (size_t)n * 3240, CK_HOST));
@@ -1335,7 +1335,7 @@ int ck_train_apply(ck_ctx* ctx, int handle, const float* const grads[12], double
     if (!grads) return ck_fail(ctx, CK_ERR_ARG, "grads is NULL");
     for (int i = 0; i < 12; i++) if (!grads[i]) return ck_fail(ctx, CK_ERR_ARG, "grads[%d] is NULL", i);
     for (int i = 0; i < 12; i++)
-        CK_HIP(ctx, hipMemcpyAsync((float*)tr->g.p + ck_train_offset(i), grads[i], CK_TRAIN_COUNTS[i] * sizeof(float),
+        CK_HIP(ctx, hipMemcpyAsync((float*)tr->g.p + ck_cnn_offset(i), grads[i], CK_CNN_COUNTS[i] * sizeof(float),
                                    hipMemcpyHostToDevice, ctx->stream));
     CK_TRY(k_train_adam(ctx, *tr, (const float*)tr->g.p, lr));
     return finish(ctx);
@@ -1346,7 +1346,7 @@ static int train_get(ck_ctx* ctx, const DevBuf& src, float* const dst[12])
 {
     if (!dst) return CK_OK;
     for (int i = 0; i < 12; i++)
-        CK_TRY(ck_from_device(ctx, dst[i], (const float*)src.p + ck_train_offset(i), CK_TRAIN_COUNTS[i] * sizeof(float), CK_HOST));
+        CK_TRY(ck_from_device(ctx, dst[i], (const float*)src.p + ck_cnn_offset(i), CK_CNN_COUNTS[i] * sizeof(float), CK_HOST));
     return CK_OK;
 }
 
@@ -1379,7 +1379,7 @@ int ck_train_handover(ck_ctx* ctx, int handle)
     CK_TRY(trainer_of(ctx, handle, &tr));
     CK_TRY(finish(ctx));
     const float* w[12];
-    for (int i = 0; i < 12; i++) w[i] = (const float*)tr->w.p + ck_train_offset(i);
+    for (int i = 0; i < 12; i++) w[i] = (const float*)tr->w.p + ck_cnn_offset(i);
     return ck_cnn_set_weights(ctx, w, CK_DEVICE);
     CK_API_END(ctx)
 }

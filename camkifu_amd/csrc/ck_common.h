@@ -18,6 +18,7 @@
 
 #include "../../include/camkifu_amd.h"
 #include "ck_buf.h"        // DevBuf, PinBuf: buffers that free themselves
+#include "ck_cnn_pack.h"   // the classifier's weight arrays and their packs (host only)
 
 // the context's stream, destroyed with it
 struct CkStream {
@@ -51,9 +52,10 @@ struct Mog2State {
 };
 
 // A trainer of the stone classifier (k_cnn_train.hip): master weights, the last gradients and both Adam moments as flat f32
-// arrays in weight order (c1w c1b .. d2w d2b, CK_TRAIN_PARAMS floats), what one chunk keeps between forward and backward,
+// arrays in weight order (c1w c1b .. d2w d2b, CK_TRAIN_PARAMS floats; array i at ck_cnn_offset(i)), what one chunk keeps between forward and backward,
 // the partial sums of the weight gradients, and the number of Adam updates applied so far.
 #define CK_TRAIN_PARAMS 658665
+static_assert(ck_cnn_offset(12) == CK_TRAIN_PARAMS, "the twelve arrays of ck_cnn_pack.h end to end");
 #define CK_TRAIN_CHUNK 256
 struct CkTrainer {
     bool alive = false;
@@ -65,12 +67,13 @@ struct CkTrainer {
 // the modes that carry f32 operands as split fp16 (and share the overflow flag and the f32 fallback)
 static inline bool ck_cnn_split(int mode) { return mode == CK_CNN_F16X2 || mode == CK_CNN_F16Q8; }
 
+// every buffer is a member of CnnPacks (ck_cnn_pack.h) under the same name: packed on the host, uploaded by k_cnn_pack_weights
 struct CnnWeights {
     bool set = false;
     // repacked fp32 (correlation layout, [kh][kw][cin][cout] with the flip applied)
     DevBuf c1w, c1b, c2w, c2b, c3w, c3b, c4w, c4b, d1w, d1b, d2w, d2b;
     // bf16 packs for the MFMA path
-    DevBuf c2w_bf, c3w_bf, c4w_bf, d1w_bf;
+    DevBuf c2w_bf, c3w_bf, c4w_bf;
     DevBuf c1w_f16;      // conv1 for the fused bf16 kernels: fp16 fragments (k_cnn_bf16.hip)
     DevBuf d1w_bfp;      // dense 1 for fc1_bf16_kernel: bf16 fragments over the padded maps
     // hi / lo fp16 planes for the split-precision mode
@@ -277,17 +280,12 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int n, float* d_y, uint8_
                   int* d_nonfinite = nullptr, uint8_t* d_rlabel = nullptr, double* d_rconf = nullptr);
 int k_cnn_pack_weights(ck_ctx* ctx, const float* const w[12], int space);
 // CK_CNN_BF16 (k_cnn_bf16.hip): conv1 + conv2 and conv3 + conv4 of np patches, pooled maps out as bf16
-int k_cnn_bf16_pack_conv1(ck_ctx* ctx, const float* k1, DevBuf& dst);
 int k_cnn_bf16_convs(ck_ctx* ctx, const uint8_t* gob, int np, uint16_t* p2, uint16_t* q4);
-int k_cnn_bf16_pack_fc1(ck_ctx* ctx, const float* w, DevBuf& dst);
 int k_cnn_bf16_fc1(ck_ctx* ctx, const uint16_t* q4, int np, float* h1);
 // CK_CNN_F16Q8 (k_cnn_q8.hip): the same two fused kernels with f32 maps in and out (drop-ins for the split-precision pair of k_cnn.hip)
-int k_cnn_q8_pack(ck_ctx* ctx, const float* k1, const float* k2, const float* k3, const float* k4);
 int k_cnn_q8_conv12(ck_ctx* ctx, const uint8_t* gob, int np, float* p2, int* overflow);
 int k_cnn_q8_conv34(ck_ctx* ctx, const float* p2, int np, float* p4, int* overflow);
 // the classifier's training step (k_cnn_train.hip); d_x n x 40 x 40 x 3 and d_lab n bytes on the device
-extern const size_t CK_TRAIN_COUNTS[12];
-size_t ck_train_offset(int i);
 int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int space);
 int k_train_grads(ck_ctx* ctx, CkTrainer& tr, const uint8_t* d_x, const uint8_t* d_lab, int n, int drop, uint64_t seed,
                   uint64_t step, bool want_masks);

@@ -24,7 +24,7 @@
 #include <math.h>
 
 #include <algorithm>
-
+#include <map>
 #include <type_traits>
 
 #include "ck_common.h"
@@ -53,7 +53,7 @@
 #ifndef H2C34_PF
 #define H2C34_PF 2
 #endif
-constexpr float H2_WSCALE = 256.f;      // split-precision mode: weights are stored x 2^8 (their lo halves stay normal fp16)
+constexpr float H2_WSCALE = CK_CNN_WSCALE;      // split-precision mode: weights are stored x 2^8 (their lo halves stay normal fp16)
 #ifndef C1_R
 #define C1_R 3
 #endif
@@ -91,6 +91,72 @@ constexpr int H2_LOG_CAP = 1 << 18;
 __device__ unsigned long long g_h2_log[3 * H2_LOG_CAP];
 #define H34_STAMP(K) do { if (NXT_W > 0 && threadIdx.x == 0) { const unsigned long long now__ = wall_clock64(); atomicAdd(&g_h34_prof[K], now__ - t_prev__); t_prev__ = now__; } } while (0)
 #define H2_STAMP(K) do { if (FUSE1 && threadIdx.x == 0) { const unsigned long long now__ = wall_clock64(); atomicAdd(&g_h2_prof[K], now__ - t_prev__); t_prev__ = now__; } } while (0)
+// what the host prints after the fused conv1 + conv2 kernel ran on np patches: the phases, then the residency per CU from the per-wave log
+static void h2_conv2_report(ck_ctx* ctx, int np)
+{
+    unsigned long long hp[8];
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_h2_prof), sizeof hp);
+    if (hp[7]) fprintf(stderr, "[conv2 phases, us per workgroup over %llu workgroups] stage %.2f  conv1 tiles (wave 0) %.2f  wait for the others %.2f  k-loop %.2f  epilogue %.2f\n", hp[7],
+                       hp[0] * 0.01 / hp[7], hp[4] * 0.01 / hp[7], hp[1] * 0.01 / hp[7], hp[2] * 0.01 / hp[7], hp[3] * 0.01 / hp[7]);
+    memset(hp, 0, sizeof hp);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h2_prof), hp, sizeof hp);
+    const int nw = std::min(np * 3 * 8, H2_LOG_CAP);
+    std::vector<unsigned long long> lg((size_t)3 * nw);
+    (void)hipMemcpyFromSymbol(lg.data(), HIP_SYMBOL(g_h2_log), lg.size() * 8);
+    struct Wg { unsigned long long a, b, wsum; int n; };
+    std::map<unsigned, std::map<unsigned, Wg>> cus;          // CU key -> workgroup id -> its interval
+    unsigned long long t_lo = ~0ull, t_hi = 0;
+    for (int i = 0; i < nw; i++) {
+        const unsigned long long key = lg[3 * i], a = lg[3 * i + 1], b = lg[3 * i + 2];
+        if (!b) continue;
+        Wg& g = cus[(unsigned)(key & 0xFFFF)][(unsigned)(key >> 16)];
+        if (!g.n) { g.a = a; g.b = b; } else { g.a = std::min(g.a, a); g.b = std::max(g.b, b); }
+        g.wsum += b - a; g.n++;
+        t_lo = std::min(t_lo, a); t_hi = std::max(t_hi, b);
+    }
+    double life = 0, wlife = 0, gap = 0, resid = 0; size_t nwg = 0, ngap = 0, nwave = 0;
+    std::vector<double> gaps;
+    for (auto& cu : cus) {
+        std::vector<std::pair<unsigned long long, int>> ev;
+        double busy = 0;
+        for (auto& w : cu.second) {
+            life += (double)(w.second.b - w.second.a); wlife += (double)w.second.wsum; nwave += w.second.n; nwg++;
+            busy += (double)(w.second.b - w.second.a);
+            ev.push_back({w.second.a, +1}); ev.push_back({w.second.b, -1});
+        }
+        resid += busy;
+        std::sort(ev.begin(), ev.end());
+        // a slot falls empty at every end; the next start on this CU fills it
+        std::vector<unsigned long long> ends;
+        for (auto& e : ev) {
+            if (e.second < 0) ends.push_back(e.first);
+            else if (!ends.empty()) { gaps.push_back((double)(e.first - ends.front())); ends.erase(ends.begin()); }
+        }
+    }
+    std::sort(gaps.begin(), gaps.end());
+    for (double g : gaps) gap += g;
+    ngap = gaps.size();
+    fprintf(stderr, "[conv2 residency] %zu CUs, %zu workgroups: workgroup lifetime %.2f us (its waves %.2f), %.2f workgroups resident per CU over the kernel's %.0f us; "
+                    "slot empty between two workgroups: mean %.2f us, median %.2f, p90 %.2f (%zu refills)\n",
+            cus.size(), nwg, 0.01 * life / std::max<size_t>(nwg, 1), 0.01 * wlife / std::max<size_t>(nwave, 1),
+            resid / ((double)(t_hi - t_lo) * std::max<size_t>(cus.size(), 1)), 0.01 * (double)(t_hi - t_lo),
+            0.01 * gap / std::max<size_t>(ngap, 1), ngap ? 0.01 * gaps[ngap / 2] : 0.0, ngap ? 0.01 * gaps[ngap * 9 / 10] : 0.0, ngap);
+    std::fill(lg.begin(), lg.end(), 0ull);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h2_log), lg.data(), lg.size() * 8);
+}
+
+// ... and after the fused conv3 + conv4 kernel: its phases
+static void h2_conv34_report(ck_ctx* ctx)
+{
+    unsigned long long hp[8];
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_h34_prof), sizeof hp);
+    if (hp[3]) fprintf(stderr, "[conv3+4 phases, us per workgroup over %llu workgroups] stage + conv3 + relayout (wave 0) %.2f (stage %.2f, k-loop %.2f, relayout %.2f)  barrier %.2f  conv4 + epilogue %.2f\n",
+                       hp[3], hp[0] * 0.01 / hp[3], hp[4] * 0.01 / hp[3], hp[5] * 0.01 / hp[3], hp[6] * 0.01 / hp[3], hp[1] * 0.01 / hp[3], hp[2] * 0.01 / hp[3]);
+    memset(hp, 0, sizeof hp);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h34_prof), hp, sizeof hp);
+}
 #else
 #define H2_STAMP(K) do { } while (0)
 #define H34_STAMP(K) do { } while (0)
@@ -114,20 +180,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// float -> bf16, round to nearest even (activations are finite)
-__host__ __device__ __forceinline__ uint16_t f2bf(float f)
-{
-    union { float f; uint32_t u; } x;
-    x.f = f;
-    return (uint16_t)((x.u + 0x7FFFu + ((x.u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float bf2f(uint16_t h)
-{
-    union { float f; uint32_t u; } x;
-    x.u = (uint32_t)h << 16;
-    return x.f;
-}
-
 // region index -> first pixel row/col of its 40x40 patch (nn_manager.py:92-126, 256-275)
 __device__ __forceinline__ int region_origin(int i) { return i == 9 ? 340 : 40 * i; }
 
@@ -136,7 +188,7 @@ __device__ __forceinline__ int region_origin(int i) { return i == 9 ? 340 : 40 *
 // 16-pixel x 16-channel tiles.  blockIdx.x = patch, blockIdx.y = group of TB pixel tiles;
 // wave (wm, wn) owns R = TB / WAVES_M pixel tiles x RN channel tiles.
 //   in : [patch][H][W][CIN] f32
-//   wc : [channel tile][group of 4 k-steps][lane][4] f32 (pack_mfma16: the B fragment lane (k-slot, column)
+//   wc : [channel tile][group of 4 k-steps][lane][4] f32 (conv_f32 of ck_cnn_pack.cpp: the B fragment lane (k-slot, column)
 //        needs for k-step 4g+e is element e; K = (kh, kw, cin padded to 4), zero padded)
 //   out: POOL ? [patch][OH/2*OW/2][COUT] : [patch][OH*OW][COUT]
 // With POOL a tile is a 4x4 block of output pixels = four 2x2 pooling windows (tile row 4q+e =
@@ -330,7 +382,7 @@ __global__ __launch_bounds__(64 * WAVES_M * (cdiv(COUT, 16) / RN)) void conv_mfm
 // conv_mfma16_f32_kernel (A = weights, B = pixels), so a lane's four accumulators are four
 // consecutive channels of one pixel and the result leaves as 16-byte stores.
 //   work unit = 12 output rows of one patch = 27 pixel tiles, WAVES waves x R tiles
-//   wf : [2 channel tiles][19 steps][64 lanes] f32 (pack_conv1)
+//   wf : [2 channel tiles][19 steps][64 lanes] f32 (conv1_f32 of ck_cnn_pack.cpp)
 //   out: [patch][36*36][32] f32
 template <int R>
 __global__ __launch_bounds__(64 * (27 / R)) void conv1_mfma16_kernel(
@@ -447,7 +499,7 @@ __host__ __device__ constexpr int lds_stride_b(int n, int rem, int mod) { return
 // Weights are pre-scaled by 2^8 so that their lo halves stay normal fp16 numbers (undone on the accumulator,
 // exact).  Results agree with the f32 kernels to ~1e-6 (tests), not bit for bit: the k-ordered f32 chain
 // is what CK_CNN_FP32 keeps.
-//   in : [patch][H][W][CIN] f32       wt : [16-channel tile][k-step][hi|lo][lane][8] fp16 (pack_mfma16_h2)
+//   in : [patch][H][W][CIN] f32       wt : [16-channel tile][k-step][hi|lo][lane][8] fp16 (conv_k32 of ck_cnn_pack.cpp)
 //   out: as conv_mfma16_f32_kernel
 // LDS: per pixel [hi CINP][lo CINP][8 pad] halves (pixel stride = 16 mod 128 bytes), row stride chosen as in
 // the bf16 kernel; one k-step = 32 channels of one kernel tap.
@@ -455,12 +507,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // swizzled conv2 tile: chunk c of the pixel at column x of tile row y sits in slot c ^ h2_swz(x, y)
 __device__ __forceinline__ int h2_swz(int x, int y) { return ((x & 6) ^ (x & 1) ^ (y << 2)) & 7; }
-
-__device__ __forceinline__ void split_h2(float x, _Float16& hi, _Float16& lo)
-{
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
 
 // Two values at once, in four instructions instead of ten (round 4): hi = the fp16 TOWARDS ZERO of x (one
 // v_cvt_pkrtz_f16_f32 for both), residual x - hi by v_fma_mix_f32 (the fp16 operand is widened inside the instruction),
@@ -1032,7 +1078,7 @@ __global__ __launch_bounds__(64 * 2 * (6 / H2C34_RN), H2C34_MINW) void conv34_h2
 // Workgroup = 64 patches x all 160 outputs: wave w owns patches 16w..16w+15 and the ten 16-output
 // tiles.  The activations are staged through LDS in chunks of 120 values per patch (coalesced
 // float4 loads, pixel stride 130 dwords = 2 mod 32: conflict-free fragment reads); the weights
-// stream from L2 as packed dwordx2 fragments ([tile][pair of k-steps][lane][2], pack_fc1) through
+// stream from L2 as packed dwordx2 fragments ([tile][pair of k-steps][lane][2], fc1_f32 of ck_cnn_pack.cpp) through
 // a 3-deep register ring.  Operands are swapped (A = weights, B = activations) so a lane ends up
 // with four consecutive outputs of one patch: 16-byte stores.
 __global__ __launch_bounds__(256) void fc1_mfma16_kernel(const float* __restrict__ x, const float* __restrict__ wq_,
@@ -1339,170 +1385,38 @@ __global__ __launch_bounds__(128) void decode_kernel(const float* __restrict__ y
 }
 }  // namespace
 
-// B operand pack of conv_mfma16_f32_kernel: [channel tile of 16][group of 4 k-steps][lane = kslot*16 + col][4]
-// with K = (kh, kw, cin padded to a multiple of 4) and k = 4*step + kslot; flip applied, padding zero
-static void pack_mfma16(const float* k, int KH, int KW, int CIN, int COUT, std::vector<float>& dst)
+static int upload(ck_ctx* ctx, DevBuf& b, const CkBytes& v)
 {
-    const int CINP = (CIN + 3) / 4 * 4, KS = KH * KW * CINP / 4, SG = (KS + 3) / 4, NT = (COUT + 15) / 16;
-    dst.assign((size_t)NT * SG * 64 * 4, 0.f);
-    for (int nt = 0; nt < NT; nt++)
-        for (int step = 0; step < KS; step++)
-            for (int lane = 0; lane < 64; lane++) {
-                const int kidx = 4 * step + lane / 16, ij = kidx / CINP, c = kidx % CINP, o = nt * 16 + lane % 16;
-                if (c >= CIN || o >= COUT) continue;
-                const int i = ij / KW, j = ij % KW;
-                dst[(((size_t)nt * SG + step / 4) * 64 + lane) * 4 + step % 4] =
-                    k[(((size_t)(KH - 1 - i) * KW + (KW - 1 - j)) * CIN + c) * COUT + o];
-            }
+    CK_TRY(ck_ensure(ctx, b, v.size()));
+    CK_HIP(ctx, hipMemcpy(b.p, v.data(), v.size(), hipMemcpyHostToDevice));
+    return CK_OK;
 }
 
-// A operand pack of conv1_mfma16_kernel: [channel tile][step][lane = kslot*16 + channel], K = 75 dense
-// in (kh, kw, cin) order, k = 4*step + kslot, flip applied, k = 75 zero
-static void pack_conv1(const float* k, std::vector<float>& dst)
-{
-    dst.assign((size_t)2 * 19 * 64, 0.f);
-    for (int n = 0; n < 2; n++)
-        for (int s = 0; s < 19; s++)
-            for (int lane = 0; lane < 64; lane++) {
-                const int kk = 4 * s + lane / 16, o = n * 16 + lane % 16;
-                if (kk >= 75) continue;
-                const int i = kk / 15, j = (kk % 15) / 3, c = kk % 3;
-                dst[((size_t)n * 19 + s) * 64 + lane] = k[(((size_t)(4 - i) * 5 + (4 - j)) * 3 + c) * 32 + o];
-            }
-}
-
-// A operand pack of fc1_mfma16_kernel: [output tile of 16][pair of k-steps][lane = kslot*16 + output][2],
-// k = 4*step + kslot ascending
-static void pack_fc1(const float* w, std::vector<float>& dst)
-{
-    const int KIN = 3240, NOUT = 160, SG2 = KIN / 8;
-    dst.assign((size_t)(NOUT / 16) * SG2 * 64 * 2, 0.f);
-    for (int nt = 0; nt < NOUT / 16; nt++)
-        for (int step = 0; step < KIN / 4; step++)
-            for (int lane = 0; lane < 64; lane++)
-                dst[(((size_t)nt * SG2 + step / 2) * 64 + lane) * 2 + step % 2] =
-                    w[(size_t)(4 * step + lane / 16) * NOUT + nt * 16 + lane % 16];
-}
-
+// fetch the twelve Keras arrays, pack them on the host (ck_cnn_pack.cpp), upload every pack
 int k_cnn_pack_weights(ck_ctx* ctx, const float* const w[12], int space)
 {
-    static const size_t counts[12] = { 5 * 5 * 3 * 32, 32, 5 * 5 * 32 * 32, 32, 3 * 3 * 32 * 90, 90,
-                                       3 * 3 * 90 * 90, 90, 3240 * 160, 160, 160 * 81, 81 };
-    std::vector<std::vector<float>> host(12);
+    std::vector<float> host(CK_TRAIN_PARAMS);
+    const float* arrays[12];
     for (int i = 0; i < 12; i++) {
-        host[i].resize(counts[i]);
-        if (space == CK_DEVICE) CK_HIP(ctx, hipMemcpy(host[i].data(), w[i], counts[i] * 4, hipMemcpyDeviceToHost));
-        else if (space == CK_HOST) memcpy(host[i].data(), w[i], counts[i] * 4);
+        float* h = host.data() + ck_cnn_offset(i);
+        if (space == CK_DEVICE) CK_HIP(ctx, hipMemcpy(h, w[i], CK_CNN_COUNTS[i] * 4, hipMemcpyDeviceToHost));
+        else if (space == CK_HOST) memcpy(h, w[i], CK_CNN_COUNTS[i] * 4);
         else return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", space);
+        arrays[i] = h;
     }
-    auto up = [&](DevBuf& b, const std::vector<float>& v) -> int {
-        CK_TRY(ck_ensure(ctx, b, v.size() * 4));
-        CK_HIP(ctx, hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-        return CK_OK;
+    CnnPacks P;
+    ck_cnn_pack(arrays, P);
+    CnnWeights& W = ctx->cnn;
+#define UP(m) { &W.m, &P.m }
+    const std::pair<DevBuf*, const CkBytes*> ups[CK_CNN_NPACKS] = {
+        UP(c1w), UP(c2w), UP(c3w), UP(c4w), UP(c1b), UP(c2b), UP(c3b), UP(c4b), UP(d1w), UP(d1b), UP(d2w), UP(d2b),
+        UP(c1w_f16), UP(d1w_bfp), UP(c2w_bf), UP(c3w_bf), UP(c4w_bf),
+        UP(c1w_h2), UP(c2w_h2), UP(c3w_h2), UP(c4w_h2), UP(c1w_q8), UP(c2x_q8), UP(c3x_q8), UP(c4x_q8), UP(d1w_h2),
     };
-    std::vector<float> t;
-    pack_conv1(host[0].data(), t);              CK_TRY(up(ctx->cnn.c1w, t));
-    pack_mfma16(host[2].data(), 5, 5, 32, 32, t); CK_TRY(up(ctx->cnn.c2w, t));
-    pack_mfma16(host[4].data(), 3, 3, 32, 90, t); CK_TRY(up(ctx->cnn.c3w, t));
-    pack_mfma16(host[6].data(), 3, 3, 90, 90, t); CK_TRY(up(ctx->cnn.c4w, t));
-    CK_TRY(up(ctx->cnn.c1b, host[1])); CK_TRY(up(ctx->cnn.c2b, host[3]));
-    CK_TRY(up(ctx->cnn.c3b, host[5])); CK_TRY(up(ctx->cnn.c4b, host[7]));
-    pack_fc1(host[8].data(), t);               CK_TRY(up(ctx->cnn.d1w, t));
-    CK_TRY(up(ctx->cnn.d1b, host[9]));
-    CK_TRY(up(ctx->cnn.d2w, host[10])); CK_TRY(up(ctx->cnn.d2b, host[11]));
-    // bf16 packs in MFMA fragment order: [16-channel tile][k-step][lane = kslot*16 + channel][8 consecutive cin],
-    // k-step = 32 input channels of one kernel tap; flip applied, padding channels zero
-    auto pack_bf = [&](const float* k, int KH, int KW, int CIN, int CINP, int COUT, int COUTS, DevBuf& dst) -> int {
-        const int KS = KH * KW * (CINP / 32), NT = COUTS / 16;
-        std::vector<uint16_t> v((size_t)NT * KS * 64 * 8, 0);
-        for (int nt = 0; nt < NT; nt++)
-            for (int i = 0; i < KH; i++)
-                for (int j = 0; j < KW; j++)
-                    for (int cc = 0; cc < CINP / 32; cc++)
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int e = 0; e < 8; e++) {
-                                const int c = 32 * cc + 8 * (lane / 16) + e, o = nt * 16 + lane % 16;
-                                if (c >= CIN || o >= COUT) continue;
-                                const int step = (i * KW + j) * (CINP / 32) + cc;
-                                v[(((size_t)nt * KS + step) * 64 + lane) * 8 + e] =
-                                    f2bf(k[(((size_t)(KH - 1 - i) * KW + (KW - 1 - j)) * CIN + c) * COUT + o]);
-                            }
-        CK_TRY(ck_ensure(ctx, dst, v.size() * 2));
-        CK_HIP(ctx, hipMemcpy(dst.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-        return CK_OK;
-    };
-    CK_TRY(k_cnn_bf16_pack_conv1(ctx, host[0].data(), ctx->cnn.c1w_f16));
-    CK_TRY(k_cnn_bf16_pack_fc1(ctx, host[8].data(), ctx->cnn.d1w_bfp));
-    CK_TRY(pack_bf(host[2].data(), 5, 5, 32, 32, 32, 32, ctx->cnn.c2w_bf));
-    CK_TRY(pack_bf(host[4].data(), 3, 3, 32, 32, 90, 96, ctx->cnn.c3w_bf));
-    CK_TRY(pack_bf(host[6].data(), 3, 3, 90, 96, 90, 96, ctx->cnn.c4w_bf));
-    // split-precision packs: weights x 2^8 as hi / lo fp16 planes in MFMA fragment order
-    // [16-channel tile][k-step][plane][lane = kslot*16 + channel][8 consecutive cin], flip applied
-    auto pack_h2 = [&](const float* k, int KH, int KW, int CIN, int COUT, DevBuf& dst) -> int {
-        const int CINP = (CIN + 31) / 32 * 32, KS = KH * KW * (CINP / 32), NT = (COUT + 15) / 16;
-        std::vector<uint16_t> v((size_t)NT * KS * 2 * 64 * 8, 0);
-        for (int nt = 0; nt < NT; nt++)
-            for (int i = 0; i < KH; i++)
-                for (int j = 0; j < KW; j++)
-                    for (int cc = 0; cc < CINP / 32; cc++)
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int e = 0; e < 8; e++) {
-                                const int c = 32 * cc + 8 * (lane / 16) + e, o = nt * 16 + lane % 16;
-                                if (c >= CIN || o >= COUT) continue;
-                                const int step = (i * KW + j) * (CINP / 32) + cc;
-                                const float wv = k[(((size_t)(KH - 1 - i) * KW + (KW - 1 - j)) * CIN + c) * COUT + o] * H2_WSCALE;
-                                const _Float16 hi = (_Float16)wv;
-                                const _Float16 lo = (_Float16)(wv - (float)hi);
-                                const size_t base = (((size_t)nt * KS + step) * 2) * 64 * 8 + (size_t)lane * 8 + e;
-                                memcpy(&v[base], &hi, 2);
-                                memcpy(&v[base + 64 * 8], &lo, 2);
-                            }
-        CK_TRY(ck_ensure(ctx, dst, v.size() * 2));
-        CK_HIP(ctx, hipMemcpy(dst.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-        return CK_OK;
-    };
-    {   // conv1: [channel tile][step][plane][lane][8]; k = (kernel row 2*step + kslot/2, slot 8*(kslot%2) + e), slot = kw*3 + cin
-        std::vector<uint16_t> v((size_t)2 * 3 * 2 * 64 * 8, 0);
-        for (int nt = 0; nt < 2; nt++)
-            for (int st = 0; st < 3; st++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 8; e++) {
-                        const int kqq = lane / 16, i = 2 * st + (kqq >> 1), slot = 8 * (kqq & 1) + e, o = nt * 16 + lane % 16;
-                        if (i > 4 || slot > 14) continue;
-                        const int j = slot / 3, c = slot % 3;
-                        const float wv = host[0][(((size_t)(4 - i) * 5 + (4 - j)) * 3 + c) * 32 + o] * H2_WSCALE;
-                        const _Float16 hi = (_Float16)wv;
-                        const _Float16 lo = (_Float16)(wv - (float)hi);
-                        const size_t base = (((size_t)nt * 3 + st) * 2) * 64 * 8 + (size_t)lane * 8 + e;
-                        memcpy(&v[base], &hi, 2);
-                        memcpy(&v[base + 64 * 8], &lo, 2);
-                    }
-        CK_TRY(ck_ensure(ctx, ctx->cnn.c1w_h2, v.size() * 2));
-        CK_HIP(ctx, hipMemcpy(ctx->cnn.c1w_h2.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-    }
-    CK_TRY(pack_h2(host[2].data(), 5, 5, 32, 32, ctx->cnn.c2w_h2));
-    CK_TRY(pack_h2(host[4].data(), 3, 3, 32, 90, ctx->cnn.c3w_h2));
-    CK_TRY(pack_h2(host[6].data(), 3, 3, 90, 90, ctx->cnn.c4w_h2));
-    CK_TRY(k_cnn_q8_pack(ctx, host[0].data(), host[2].data(), host[4].data(), host[6].data()));
-    {   // dense1 for fc1_h2_kernel: [output tile][k-step][plane][lane = kslot*16 + output][8 consecutive k], weights x 2^8
-        std::vector<uint16_t> v((size_t)10 * 104 * 2 * 64 * 8, 0);
-        for (int t = 0; t < 10; t++)
-            for (int st = 0; st < 104; st++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 8; e++) {
-                        const int k = 32 * st + 8 * (lane / 16) + e, o = 16 * t + lane % 16;
-                        if (k >= 3240) continue;
-                        const float wv = host[8][(size_t)k * 160 + o] * H2_WSCALE;
-                        const _Float16 hi = (_Float16)wv;
-                        const _Float16 lo = (_Float16)(wv - (float)hi);
-                        const size_t base = (((size_t)t * 104 + st) * 2) * 64 * 8 + (size_t)lane * 8 + e;
-                        memcpy(&v[base], &hi, 2);
-                        memcpy(&v[base + 64 * 8], &lo, 2);
-                    }
-        CK_TRY(ck_ensure(ctx, ctx->cnn.d1w_h2, v.size() * 2));
-        CK_HIP(ctx, hipMemcpy(ctx->cnn.d1w_h2.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-    }
-    ctx->cnn.set = true;
+#undef UP
+    for (const auto& u : ups) CK_TRY(upload(ctx, *u.first, *u.second));
+    W.q8_ok = P.q8_ok;
+    W.set = true;
     return CK_OK;
 }
 
@@ -1520,27 +1434,13 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
     float* a1 = (float*)ctx->act0.p;
     float* p2 = (float*)ctx->act1.p;
     float* p4_all = (float*)ctx->act2.p;
-    float* h1 = p4_all + (size_t)nframes * 100 * 3240;
     const CnnWeights& W = ctx->cnn;
-    if (ctx->cnn_mode == CK_CNN_BF16) {
-        // k_cnn_bf16.hip: conv1 + conv2 and conv3 + conv4 fused, one bf16 MFMA per product (conv1 on the fp16 pipe: its u8
-        // operand is exact there); the first dense layer on v_mfma_f32_32x32x16_bf16
-        uint16_t* b2 = (uint16_t*)ctx->act1.p;           // pooled conv2 output of a chunk: 16*16*32 per patch
-        uint16_t* q4_all = (uint16_t*)ctx->act2.p;       // pooled conv4 output, all frames: 36*96 per patch
-        float* hb = (float*)(q4_all + (((size_t)nframes * 100 * 3456 + 7) & ~(size_t)7));
-        for (int f0 = 0; f0 < nframes; f0 += CHUNK) {
-            const int nf = nframes - f0 < CHUNK ? nframes - f0 : CHUNK;
-            CK_TRY(k_cnn_bf16_convs(ctx, d_goban + (size_t)f0 * 380 * 380 * 3, nf * 100, b2, q4_all + (size_t)f0 * 100 * 3456));
-        }
-        TimeScope ts(ctx, "cnn_tail");
-        const int np = nframes * 100;
-        CK_TRY(k_cnn_bf16_fc1(ctx, q4_all, np, hb));
-        hipLaunchKernelGGL(fc2_softmax_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream, (const float*)hb,
-                           (const float*)W.d2w.p, (const float*)W.d2b.p, d_y, np);
-        hipLaunchKernelGGL(decode_kernel, dim3(nframes), dim3(128), 0, ctx->stream, (const float*)d_y, d_labels, d_conf, nframes, d_nonfinite, d_rlabel, d_rconf);
-        CK_HIP(ctx, hipGetLastError());
-        return CK_OK;
-    }
+    // k_cnn_bf16.hip: conv1 + conv2 and conv3 + conv4 fused, one bf16 MFMA per product (conv1 on the fp16 pipe: its u8
+    // operand is exact there); the first dense layer on v_mfma_f32_32x32x16_bf16
+    const bool bf = ctx->cnn_mode == CK_CNN_BF16;
+    uint16_t* b2 = (uint16_t*)ctx->act1.p;           // bf16: pooled conv2 output of a chunk, 16*16*32 per patch
+    uint16_t* q4_all = (uint16_t*)ctx->act2.p;       // bf16: pooled conv4 output, all frames, 36*96 per patch
+    float* h1 = bf ? (float*)(q4_all + (((size_t)nframes * 100 * 3456 + 7) & ~(size_t)7)) : p4_all + (size_t)nframes * 100 * 3240;
     const bool h2 = ck_cnn_split(ctx->cnn_mode);
     const bool q8 = ctx->cnn_mode == CK_CNN_F16Q8 && W.q8_ok;      // (weights outside the e4m3 range: the three-MFMA kernels)
     for (int f0 = 0; f0 < nframes; f0 += CHUNK) {
@@ -1548,6 +1448,10 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
         const int np = nf * 100;
         const uint8_t* gob = d_goban + (size_t)f0 * 380 * 380 * 3;
         float* p4 = p4_all + (size_t)f0 * 100 * 3240;
+        if (bf) {
+            CK_TRY(k_cnn_bf16_convs(ctx, gob, np, b2, q4_all + (size_t)f0 * 100 * 3456));
+            continue;
+        }
         {
             TimeScope ts(ctx, "cnn_conv1");
             if (!q8 && !h2)     // (q8, h2: conv1 is computed inside conv2's staging, below)
@@ -1565,59 +1469,7 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
                                    (const float*)a1, (const uint16_t*)W.c2w_h2.p, (const float*)W.c2b.p, p2, 1.f / H2_WSCALE, d_nonfinite,
                                    gob, (const uint16_t*)W.c1w_h2.p, (const float*)W.c1b.p);
 #if H2_DBG_TIME
-                {
-                    unsigned long long hp[8];
-                    (void)hipStreamSynchronize(ctx->stream);
-                    (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_h2_prof), sizeof hp);
-                    if (hp[7]) fprintf(stderr, "[conv2 phases, us per workgroup over %llu workgroups] stage %.2f  conv1 tiles (wave 0) %.2f  wait for the others %.2f  k-loop %.2f  epilogue %.2f\n", hp[7],
-                                       hp[0] * 0.01 / hp[7], hp[4] * 0.01 / hp[7], hp[1] * 0.01 / hp[7], hp[2] * 0.01 / hp[7], hp[3] * 0.01 / hp[7]);
-                    memset(hp, 0, sizeof hp);
-                    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h2_prof), hp, sizeof hp);
-                    // residency per CU from the per-wave log
-                    const int nw = std::min(np * 3 * 8, H2_LOG_CAP);
-                    std::vector<unsigned long long> lg((size_t)3 * nw);
-                    (void)hipMemcpyFromSymbol(lg.data(), HIP_SYMBOL(g_h2_log), lg.size() * 8);
-                    struct Wg { unsigned long long a, b, wsum; int n; };
-                    std::map<unsigned, std::map<unsigned, Wg>> cus;          // CU key -> workgroup id -> its interval
-                    unsigned long long t_lo = ~0ull, t_hi = 0;
-                    for (int i = 0; i < nw; i++) {
-                        const unsigned long long key = lg[3 * i], a = lg[3 * i + 1], b = lg[3 * i + 2];
-                        if (!b) continue;
-                        Wg& g = cus[(unsigned)(key & 0xFFFF)][(unsigned)(key >> 16)];
-                        if (!g.n) { g.a = a; g.b = b; } else { g.a = std::min(g.a, a); g.b = std::max(g.b, b); }
-                        g.wsum += b - a; g.n++;
-                        t_lo = std::min(t_lo, a); t_hi = std::max(t_hi, b);
-                    }
-                    double life = 0, wlife = 0, gap = 0, resid = 0; size_t nwg = 0, ngap = 0, nwave = 0;
-                    std::vector<double> gaps;
-                    for (auto& cu : cus) {
-                        std::vector<std::pair<unsigned long long, int>> ev;
-                        double busy = 0;
-                        for (auto& w : cu.second) {
-                            life += (double)(w.second.b - w.second.a); wlife += (double)w.second.wsum; nwave += w.second.n; nwg++;
-                            busy += (double)(w.second.b - w.second.a);
-                            ev.push_back({w.second.a, +1}); ev.push_back({w.second.b, -1});
-                        }
-                        resid += busy;
-                        std::sort(ev.begin(), ev.end());
-                        // a slot falls empty at every end; the next start on this CU fills it
-                        std::vector<unsigned long long> ends;
-                        for (auto& e : ev) {
-                            if (e.second < 0) ends.push_back(e.first);
-                            else if (!ends.empty()) { gaps.push_back((double)(e.first - ends.front())); ends.erase(ends.begin()); }
-                        }
-                    }
-                    std::sort(gaps.begin(), gaps.end());
-                    for (double g : gaps) gap += g;
-                    ngap = gaps.size();
-                    fprintf(stderr, "[conv2 residency] %zu CUs, %zu workgroups: workgroup lifetime %.2f us (its waves %.2f), %.2f workgroups resident per CU over the kernel's %.0f us; "
-                                    "slot empty between two workgroups: mean %.2f us, median %.2f, p90 %.2f (%zu refills)\n",
-                            cus.size(), nwg, 0.01 * life / std::max<size_t>(nwg, 1), 0.01 * wlife / std::max<size_t>(nwave, 1),
-                            resid / ((double)(t_hi - t_lo) * std::max<size_t>(cus.size(), 1)), 0.01 * (double)(t_hi - t_lo),
-                            0.01 * gap / std::max<size_t>(ngap, 1), ngap ? 0.01 * gaps[ngap / 2] : 0.0, ngap ? 0.01 * gaps[ngap * 9 / 10] : 0.0, ngap);
-                    std::fill(lg.begin(), lg.end(), 0ull);
-                    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h2_log), lg.data(), lg.size() * 8);
-                }
+                h2_conv2_report(ctx, np);
 #endif
             }
             else
@@ -1635,15 +1487,7 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
             hipLaunchKernelGGL(conv34_h2_kernel, dim3(np), dim3(64 * 2 * (6 / H2C34_RN)), 0, ctx->stream, (const float*)p2, (const uint16_t*)W.c3w_h2.p,
                                (const float*)W.c3b.p, (const uint16_t*)W.c4w_h2.p, (const float*)W.c4b.p, p4, 1.f / H2_WSCALE, d_nonfinite);
 #if H2_DBG_TIME
-            {
-                unsigned long long hp[8];
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_h34_prof), sizeof hp);
-                if (hp[3]) fprintf(stderr, "[conv3+4 phases, us per workgroup over %llu workgroups] stage + conv3 + relayout (wave 0) %.2f (stage %.2f, k-loop %.2f, relayout %.2f)  barrier %.2f  conv4 + epilogue %.2f\n",
-                                   hp[3], hp[0] * 0.01 / hp[3], hp[4] * 0.01 / hp[3], hp[5] * 0.01 / hp[3], hp[6] * 0.01 / hp[3], hp[1] * 0.01 / hp[3], hp[2] * 0.01 / hp[3]);
-                memset(hp, 0, sizeof hp);
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(g_h34_prof), hp, sizeof hp);
-            }
+            h2_conv34_report(ctx);
 #endif
         } else {
             {
@@ -1665,12 +1509,14 @@ int k_cnn_predict(ck_ctx* ctx, const uint8_t* d_goban, int nframes, float* d_y, 
     {
         TimeScope ts(ctx, "cnn_tail");
         const int np = nframes * 100;
-        if (h2)
+        if (bf)
+            CK_TRY(k_cnn_bf16_fc1(ctx, q4_all, np, h1));
+        else if (h2)
             hipLaunchKernelGGL(fc1_h2_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream, (const float*)p4_all,
                                (const uint16_t*)W.d1w_h2.p, (const float*)W.d1b.p, h1, np, 1.f / H2_WSCALE, d_nonfinite);
         else
-        hipLaunchKernelGGL(fc1_mfma16_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream,
-                           (const float*)p4_all, (const float*)W.d1w.p, (const float*)W.d1b.p, h1, np);
+            hipLaunchKernelGGL(fc1_mfma16_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream,
+                               (const float*)p4_all, (const float*)W.d1w.p, (const float*)W.d1b.p, h1, np);
         hipLaunchKernelGGL(fc2_softmax_kernel, dim3((np + 63) / 64), dim3(256), 0, ctx->stream, (const float*)h1,
                            (const float*)W.d2w.p, (const float*)W.d2b.p, d_y, np);
         hipLaunchKernelGGL(decode_kernel, dim3(nframes), dim3(128), 0, ctx->stream, (const float*)d_y, d_labels, d_conf, nframes, d_nonfinite, d_rlabel, d_rconf);

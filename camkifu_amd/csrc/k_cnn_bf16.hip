@@ -84,7 +84,7 @@ __device__ __forceinline__ int swz32(int x) { return (x >> 1) & 3; }
 //   w1    : conv1 weights as fp16 A fragments [channel tile 2][k-step 4][lane][8]: k = 32 s + 8 kq + e <-> fragment
 //           index f = 4 s + kq = kernel row i * 3 + tap pair p (f = 15: zero), e = (tap 2 p + (e >> 2), channel e & 3);
 //           the u8 pixels are exact halves, so conv1 runs on v_mfma_f32_16x16x32_f16 with 11-bit weights (flip applied)
-//   w2    : conv2 weights bf16 [channel tile 2][tap 25][lane][8] (pack_bf of k_cnn.hip: lane = kslot * 16 + channel)
+//   w2    : conv2 weights bf16 [channel tile 2][tap 25][lane][8] (conv_k32 of ck_cnn_pack.cpp: lane = kslot * 16 + channel)
 //   out   : [patch][16 * 16 pooled pixels][32] bf16
 // LDS: the staged pixels as halves [24 rows][40 px][B, G, R, 0] (a fragment = two neighbouring taps = 16 aligned bytes)
 // and conv1's output tile [20 rows][36 px][32 ch] bf16, swizzled (swz32).  53 760 B = 42 allocation units of 1 280 B: three
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(192, BF_C34_MINW) void conv34_bf16_kernel(
 // w + 8 (< 10) and all four patch tiles; the activations of a chunk of 128 k go through LDS (copied as they are: the maps
 // are bf16 already), the weight fragments stream from L2 in fragment order, a chunk ahead.
 //   x  : [patch][36 px][96 ch] bf16 (conv34's output; channels 90 .. 95 are zero)
-//   wt : bf16 [output tile 10][k-step 108][lane][8] with k = px * 96 + ch (pack below)      out : [patch][160] f32
+//   wt : bf16 [output tile 10][k-step 108][lane][8] with k = px * 96 + ch (fc1_bf16 of ck_cnn_pack.cpp)      out : [patch][160] f32
 __global__ __launch_bounds__(256) void fc1_bf16_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ wt,
                                                        const float* __restrict__ bias, float* __restrict__ out, int npatch)
 {
@@ -570,44 +570,6 @@ __global__ __launch_bounds__(256) void fc1_bf16_kernel(const uint16_t* __restric
 }
 
 }  // namespace
-
-// conv1's weights for conv12_bf16_kernel: fp16 A fragments [channel tile][k-step][lane = kslot * 16 + channel][8] (layout at
-// the kernel).  `k1` is the Keras kernel [kh][kw][cin][cout]; the flip of the Theano convolution is applied here.
-int k_cnn_bf16_pack_conv1(ck_ctx* ctx, const float* k1, DevBuf& dst)
-{
-    std::vector<uint16_t> v((size_t)2 * 4 * 64 * 8, 0);
-    for (int nt = 0; nt < 2; nt++)
-        for (int s = 0; s < 4; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int f = 4 * s + lane / 16, i = f / 3, j = 2 * (f % 3) + (e >> 2), c = e & 3, o = nt * 16 + lane % 16;
-                    if (f > 14 || j > 4 || c > 2) continue;
-                    const _Float16 h = (_Float16)k1[(((size_t)(4 - i) * 5 + (4 - j)) * 3 + c) * 32 + o];
-                    memcpy(&v[(((size_t)nt * 4 + s) * 64 + lane) * 8 + e], &h, 2);
-                }
-    CK_TRY(ck_ensure(ctx, dst, v.size() * 2));
-    CK_HIP(ctx, hipMemcpy(dst.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-    return CK_OK;
-}
-
-// dense-1 weights for fc1_bf16_kernel: bf16 A fragments [output tile][k-step][lane = kslot * 16 + output][8], k = px * 96 + ch over the
-// padded maps; `w` is the Keras matrix [3240 = px * 90 + ch][160]
-int k_cnn_bf16_pack_fc1(ck_ctx* ctx, const float* w, DevBuf& dst)
-{
-    std::vector<uint16_t> v((size_t)10 * 108 * 64 * 8, 0);
-    for (int t = 0; t < 10; t++)
-        for (int st = 0; st < 108; st++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int k = 32 * st + 8 * (lane / 16) + e, px = k / 96, c = k % 96, o = 16 * t + lane % 16;
-                    if (c >= 90) continue;
-                    const __bf16 b = (__bf16)w[(size_t)(px * 90 + c) * 160 + o];
-                    memcpy(&v[(((size_t)t * 108 + st) * 64 + lane) * 8 + e], &b, 2);
-                }
-    CK_TRY(ck_ensure(ctx, dst, v.size() * 2));
-    CK_HIP(ctx, hipMemcpy(dst.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-    return CK_OK;
-}
 
 int k_cnn_bf16_fc1(ck_ctx* ctx, const uint16_t* q4, int np, float* h1)
 {

@@ -18,7 +18,7 @@
 // Activations in LDS: per pixel and 32 channels a hi plane (32 halves, round-to-nearest fp16 of the f32 value) and a q
 // plane (64 bytes: e4m3(hi / 4) of the 32 channels, then e4m3((value - hi) * 2^11 / 4)).  Both planes have the geometry of
 // the bf16 kernels' tiles (64 bytes per pixel and 32 channels), hence their swizzles.  Weights: x 2^8 as in k_cnn.hip; the
-// main term reads the hi planes of the c?w_h2 packs, the cross terms their own e4m3 packs (k_cnn_q8_pack).
+// main term reads the hi planes of the c?w_h2 packs, the cross terms their own e4m3 packs (cross of ck_cnn_pack.cpp).
 // A value beyond the e4m3 range (|x| >= 1792 with the block scale 4; the conversion then gives NaN) raises the same flag
 // as an fp16 overflow in k_cnn.hip and the batch is recomputed by the f32 chain (ck_api.hip: cnn_finish).
 #include <algorithm>
@@ -78,8 +78,8 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-constexpr float Q8_WSCALE = 256.f;        // = H2_WSCALE of k_cnn.hip: the c?w_h2 packs hold w x 2^8
-constexpr int Q8_SA = 2, Q8_SW = 2;       // block scales 2^2 of the e4m3 operands (activations, weights): range +-1792
+constexpr float Q8_WSCALE = CK_CNN_WSCALE; // = H2_WSCALE of k_cnn.hip: the c?w_h2 packs hold w x 2^8
+constexpr int Q8_SA = 2, Q8_SW = CK_CNN_Q8_SW;       // block scales 2^2 of the e4m3 operands (activations, weights): range +-1792
 constexpr float Q8_LIMIT = 1700.f;        // an activation above this raises the overflow flag
 
 __device__ __forceinline__ int region_origin(int i) { return i == 9 ? 340 : 40 * i; }
@@ -685,112 +685,6 @@ __global__ __launch_bounds__(256, 2) void conv34_q8_kernel(
 }
 
 }  // namespace
-
-// ---- host side: packs ------------------------------------------------------------------------------------------------
-// OCP e4m3 (no infinities, 0x7F = NaN, largest 448), round to nearest even; the caller keeps |v| <= 448
-static uint8_t e4m3_of(float v)
-{
-    if (v == 0.f || v != v) return 0;
-    const uint8_t sgn = v < 0 ? 0x80 : 0;
-    v = fabsf(v);
-    if (v > 448.f) v = 448.f;
-    int e;
-    float m = frexpf(v, &e);
-    e -= 1; m *= 2.f;                               // v = m 2^e, m in [1, 2)
-    if (e < -6) return sgn | (uint8_t)lrintf(v * 512.f);        // subnormals: steps of 2^-9 (8 = the smallest normal's code)
-    int q = (int)lrintf((m - 1.f) * 8.f);
-    if (q == 8) { q = 0; e += 1; }
-    if (e > 8 || (e == 8 && q > 6)) { e = 8; q = 6; }
-    return sgn | (uint8_t)(((e + 7) << 3) | q);
-}
-
-// cross-term weights of a convolution: [channel tile][unit pair][lane][32 bytes].  A unit is 32 input channels of one tap;
-// `pairs` lists the two units (tap, channel block) of every scaled MFMA, -1 for an empty half.  Lane = group * 16 + output
-// channel; group 0 / 1: w_lo of input channels 0..15 / 16..31 of the unit, group 2 / 3: w_hi.  Weights x 2^8, flip applied.
-struct Unit { int i, j, cc; };
-static int pack_cross(ck_ctx* ctx, const float* k, int KH, int KW, int CIN, int COUT, int NTILE, const std::vector<std::pair<Unit, Unit>>& pairs,
-                      DevBuf& dst, float* wmax)
-{
-    std::vector<uint8_t> v((size_t)NTILE * pairs.size() * 64 * 32, 0);
-    const float SW = (float)(1 << Q8_SW);
-    for (int nt = 0; nt < NTILE; nt++)
-        for (size_t u = 0; u < pairs.size(); u++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int half = 0; half < 2; half++) {
-                    const Unit& un = half ? pairs[u].second : pairs[u].first;
-                    if (un.i < 0) continue;
-                    for (int e = 0; e < 16; e++) {
-                        const int g = lane / 16, c = 32 * un.cc + 16 * (g & 1) + e, o = nt * 16 + lane % 16;
-                        if (c >= CIN || o >= COUT) continue;
-                        const float wv = k[(((size_t)(KH - 1 - un.i) * KW + (KW - 1 - un.j)) * CIN + c) * COUT + o] * Q8_WSCALE;
-                        const _Float16 hi = (_Float16)wv;
-                        const float lo = (float)(_Float16)(wv - (float)hi);
-                        if (wmax && fabsf((float)hi) > *wmax) *wmax = fabsf((float)hi);
-                        v[(((size_t)nt * pairs.size() + u) * 64 + lane) * 32 + 16 * half + e] = g < 2 ? e4m3_of(lo * 2048.f / SW) : e4m3_of((float)hi / SW);
-                    }
-                }
-    CK_TRY(ck_ensure(ctx, dst, v.size()));
-    CK_HIP(ctx, hipMemcpy(dst.p, v.data(), v.size(), hipMemcpyHostToDevice));
-    return CK_OK;
-}
-
-// host[0], [2], [4], [6]: the Keras kernels [kh][kw][cin][cout] of conv1 .. conv4
-int k_cnn_q8_pack(ck_ctx* ctx, const float* k1, const float* k2, const float* k3, const float* k4)
-{
-    CnnWeights& W = ctx->cnn;
-    {   // conv1: both planes of w x 2^8 in conv12_bf16_kernel's fragment order
-        std::vector<uint16_t> v((size_t)2 * 2 * 4 * 64 * 8, 0);
-        for (int nt = 0; nt < 2; nt++)
-            for (int s = 0; s < 4; s++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 8; e++) {
-                        const int f = 4 * s + lane / 16, i = f / 3, j = 2 * (f % 3) + (e >> 2), c = e & 3, o = nt * 16 + lane % 16;
-                        if (f > 14 || j > 4 || c > 2) continue;
-                        const float wv = k1[(((size_t)(4 - i) * 5 + (4 - j)) * 3 + c) * 32 + o] * Q8_WSCALE;
-                        const _Float16 hi = (_Float16)wv, lo = (_Float16)(wv - (float)hi);
-                        memcpy(&v[((((size_t)0 * 2 + nt) * 4 + s) * 64 + lane) * 8 + e], &hi, 2);
-                        memcpy(&v[((((size_t)1 * 2 + nt) * 4 + s) * 64 + lane) * 8 + e], &lo, 2);
-                    }
-        CK_TRY(ck_ensure(ctx, W.c1w_q8, v.size() * 2));
-        CK_HIP(ctx, hipMemcpy(W.c1w_q8.p, v.data(), v.size() * 2, hipMemcpyHostToDevice));
-    }
-    float wmax = 0.f;
-    {   // conv2: per kernel row the column pairs (0, 1), (2, 3), (4, -)
-        std::vector<std::pair<Unit, Unit>> pr;
-        for (int i = 0; i < 5; i++) {
-            pr.push_back({Unit{i, 0, 0}, Unit{i, 1, 0}});
-            pr.push_back({Unit{i, 2, 0}, Unit{i, 3, 0}});
-            pr.push_back({Unit{i, 4, 0}, Unit{-1, 0, 0}});       // (not read by the kernel -- the last column's taps are paired vertically,
-                                                                 //  below -- but the kernel's fragment index is 3 i + pair: the slot stays)
-        }
-        pr.push_back({Unit{0, 4, 0}, Unit{1, 4, 0}});
-        pr.push_back({Unit{2, 4, 0}, Unit{3, 4, 0}});
-        pr.push_back({Unit{4, 4, 0}, Unit{-1, 0, 0}});
-        CK_TRY(pack_cross(ctx, k2, 5, 5, 32, 32, 2, pr, W.c2x_q8, &wmax));
-    }
-    {   // conv3: per kernel row the column pairs (0, 1), (2, -)
-        std::vector<std::pair<Unit, Unit>> pr;
-        for (int i = 0; i < 3; i++) {
-            pr.push_back({Unit{i, 0, 0}, Unit{i, 1, 0}});
-            pr.push_back({Unit{i, 2, 0}, Unit{-1, 0, 0}});       // (not read: the vertical pairs below; kept for the fragment index 2 i + pair)
-        }
-        pr.push_back({Unit{0, 2, 0}, Unit{1, 2, 0}});
-        pr.push_back({Unit{2, 2, 0}, Unit{-1, 0, 0}});
-        CK_TRY(pack_cross(ctx, k3, 3, 3, 32, 90, 6, pr, W.c3x_q8, &wmax));
-    }
-    {   // conv4: pairs of consecutive k-steps (step = tap * 3 + channel block), the 27th alone
-        std::vector<std::pair<Unit, Unit>> pr;
-        for (int u = 0; u < 14; u++) {
-            const int s0 = 2 * u, s1 = 2 * u + 1;
-            pr.push_back({Unit{s0 / 9, (s0 / 3) % 3, s0 % 3}, s1 < 27 ? Unit{s1 / 9, (s1 / 3) % 3, s1 % 3} : Unit{-1, 0, 0}});
-        }
-        CK_TRY(pack_cross(ctx, k4, 3, 3, 90, 90, 6, pr, W.c4x_q8, &wmax));
-    }
-    // weights beyond the e4m3 range of their block scale: the mode is not available with them (k_cnn_predict then runs the
-    // three-MFMA kernels instead)
-    W.q8_ok = wmax <= 448.f * (float)(1 << Q8_SW);
-    return CK_OK;
-}
 
 #if Q8_DBG_TIME
 // workgroups resident per CU over the kernel's duration, from the per-workgroup log

@@ -393,16 +393,6 @@ int dropout(ck_ctx* ctx, float* a, size_t per_patch, int np, size_t first_patch,
 
 }  // namespace
 
-const size_t CK_TRAIN_COUNTS[12] = { 5 * 5 * 3 * 32, 32, 5 * 5 * 32 * 32, 32, 3 * 3 * 32 * 90, 90,
-                                     3 * 3 * 90 * 90, 90, 3240 * 160, 160, 160 * 81, 81 };
-
-size_t ck_train_offset(int i)
-{
-    size_t o = 0;
-    for (int k = 0; k < i; k++) o += CK_TRAIN_COUNTS[k];
-    return o;
-}
-
 int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int space)
 {
     if (space != CK_HOST && space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", space);
@@ -410,7 +400,7 @@ int k_train_create(ck_ctx* ctx, CkTrainer& tr, const float* const w[12], int spa
     DevBuf* bufs[] = { &tr.w, &tr.g, &tr.m, &tr.v };
     for (DevBuf* b : bufs) CK_TRY(ck_ensure(ctx, *b, bytes));
     for (int i = 0; i < 12; i++)
-        CK_HIP(ctx, hipMemcpyAsync((float*)tr.w.p + ck_train_offset(i), w[i], CK_TRAIN_COUNTS[i] * sizeof(float),
+        CK_HIP(ctx, hipMemcpyAsync((float*)tr.w.p + ck_cnn_offset(i), w[i], CK_CNN_COUNTS[i] * sizeof(float),
                                    space == CK_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
     CK_HIP(ctx, hipMemsetAsync(tr.g.p, 0, bytes, ctx->stream));
     CK_HIP(ctx, hipMemsetAsync(tr.m.p, 0, bytes, ctx->stream));
@@ -445,7 +435,7 @@ int k_train_grads(ck_ctx* ctx, CkTrainer& tr, const uint8_t* d_x, const uint8_t*
     }
     float* W[12];
     float* G[12];
-    for (int i = 0; i < 12; i++) { W[i] = (float*)tr.w.p + ck_train_offset(i); G[i] = (float*)tr.g.p + ck_train_offset(i); }
+    for (int i = 0; i < 12; i++) { W[i] = (float*)tr.w.p + ck_cnn_offset(i); G[i] = (float*)tr.g.p + ck_cnn_offset(i); }
     float *a1 = (float*)tr.a1.p, *a2 = (float*)tr.a2.p, *p1 = (float*)tr.p1.p, *a3 = (float*)tr.a3.p, *a4 = (float*)tr.a4.p,
           *p2 = (float*)tr.p2.p, *h1 = (float*)tr.h1.p, *lg = (float*)tr.lg.p, *dlg = (float*)tr.dlg.p, *dh1 = (float*)tr.dh1.p,
           *dp2 = (float*)tr.dp2.p, *dz4 = (float*)tr.dz4.p, *dz3 = (float*)tr.dz3.p, *dp1 = (float*)tr.dp1.p, *dz2 = (float*)tr.dz2.p,

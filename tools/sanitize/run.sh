@@ -3,7 +3,9 @@
 # halves (ck_fold.cpp) with fuzz harnesses, the oracle's C restatement through its own quick self-checks, and the worker pool of the
 # host loops (ck_pool.h / ck_pool.cpp) under ThreadSanitizer as well (leaks are not checked there: the pool's threads live as long as the process).  GPU ASan is not available on
 # the pool; this is the sanitizer coverage the repository has.  The owning buffer types of the GPU library (ck_buf.h) are
-# checked on their own, over counting malloc / free in place of the HIP allocator (buf_stress.cpp).
+# checked on their own, over counting malloc / free in place of the HIP allocator (buf_stress.cpp).  The classifier's weight
+# packer (ck_cnn_pack.cpp) packs random, denormal, huge and NaN weight sets (cnn_pack_fuzz.cpp); it is built with ROCm's clang++,
+# the compiler of the library, because it needs _Float16 and __bf16, which g++ 11 does not have on x86.
 set -e
 cd "$(dirname "$0")/../.."
 mkdir -p tools/sanitize/_build
@@ -23,6 +25,9 @@ ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1 OMP_NUM_THREADS=4 tool
 g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer \
     tools/sanitize/buf_stress.cpp -o tools/sanitize/_build/buf_stress
 ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1 tools/sanitize/_build/buf_stress
+${ROCM_PATH:-/opt/rocm}/llvm/bin/clang++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off \
+    tools/sanitize/cnn_pack_fuzz.cpp camkifu_amd/csrc/ck_cnn_pack.cpp -o tools/sanitize/_build/cnn_pack_fuzz
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1 tools/sanitize/_build/cnn_pack_fuzz
 for san in thread address,undefined; do
   g++ -O1 -g -std=c++17 -fsanitize=$san -fno-omit-frame-pointer tools/sanitize/pool_stress.cpp camkifu_amd/csrc/ck_pool.cpp \
       -lpthread -o tools/sanitize/_build/pool_stress_${san%%,*}

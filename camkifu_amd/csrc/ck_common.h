@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -217,6 +219,23 @@ struct TimeScope {
 };
 int ck_timing_collect(ck_ctx* ctx);
 
+// debugging aid (CK_PROFILE_HOST set): host-side lap times of an entry point on stderr, `lap("what")` after each step;
+// every lap ends with a stream synchronisation
+struct HostLap {
+    ck_ctx* ctx;
+    const char* tag;
+    std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    void operator()(const char* what)
+    {
+        static const bool prof = getenv("CK_PROFILE_HOST") != nullptr;
+        if (!prof) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[%s] %-18s %8.3f ms\n", tag, what, std::chrono::duration<double, std::milli>(now - t_start).count());
+        t_start = now;
+    }
+};
+
 // bring a possibly-host input to the device (returns device pointer in *dev)
 int ck_to_device(ck_ctx* ctx, const void* src, size_t bytes, int space, DevBuf& stage, const void** dev);
 // deliver a device result to a possibly-host output
@@ -299,8 +318,4 @@ int k_zone_counts(ck_ctx* ctx, const uint8_t* d_mask, int n, int side, int32_t* 
 int k_records_put_board(ck_ctx* ctx, const uint8_t* d_parts, int n, ck_frame_record* d_rec);
 int k_records_put_regions(ck_ctx* ctx, const uint8_t* d_rlabel, const double* d_rconf, int n, ck_frame_record* d_rec);
 
-// host geometry (ck_host_geom.cpp)
-void ck_invert3x3(const double* s, double* d);
-void ck_min_area_rect(const int32_t* pts, int n, float* out_wh);
-void ck_min_area_rect_box(const int32_t* pts, int n, float* out_wha);     // + angle in degrees (cv2.minAreaRect's box[2])
-std::vector<int32_t> ck_hull_points(const int32_t* pts, int n);           // strictly convex hull, x0, y0, x1, y1, ...
+#include "ck_host_geom.h"  // host geometry and the host decisions of k_board_lines (ck_host_geom.cpp)

@@ -12,9 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/camkifu_amd.h"
-
-void ck_min_area_rect_box(const int32_t* pts, int n, float* out_wha);
+#include "ck_host_geom.h"
 
 void ck_invert3x3(const double* s, double* d)
 {
@@ -201,4 +199,100 @@ extern "C" int ck_get_perspective_transform(const float* src, const float* dst, 
     for (int i = 0; i < 8; i++) M[i] = a[i][8] / a[i][i];
     M[8] = 1.;
     return CK_OK;
+}
+
+// ---- K4 / K6: the host decisions of k_board_lines (k_contours.hip) ----------------------------------------------------
+// A frame's components are parallel arrays over its table slots: root (first pixel, raster index = discovery order key),
+// ub (bounding-box area: upper bound of the minAreaRect area), area (exact once known[s]).  extern "C" so that the CPU
+// tests reach them through ctypes as they are.
+
+// Which unknown components the exact-area round `round` measures: want[s] = 1 for each (the caller cleared want), their
+// number returned.  Round 0 takes the 16 largest bounding boxes, later rounds whatever could still reach the top three.
+extern "C" int ck_board_round_want(int round, int nc, const double* ub, const double* area, const uint8_t* known, uint8_t* want)
+{
+    int any = 0;
+    if (round == 0) {
+        std::vector<int> idx;
+        for (int s = 0; s < nc; s++) if (!known[s]) idx.push_back(s);
+        const int k = std::min<int>(16, (int)idx.size());
+        std::partial_sort(idx.begin(), idx.begin() + k, idx.end(), [&](int a, int b) { return ub[a] > ub[b]; });
+        for (int i = 0; i < k; i++) { want[idx[i]] = 1; any++; }
+        return any;
+    }
+    double b[3] = { -1, -1, -1 };
+    for (int s = 0; s < nc; s++) if (known[s]) {
+        double a = area[s];
+        for (int i = 0; i < 3; i++) if (a > b[i]) std::swap(a, b[i]);
+    }
+    const double third = b[2];          // -1 while fewer than three areas are known
+    for (int s = 0; s < nc; s++)
+        if (!known[s] && ub[s] * (1.0 + 1e-5) >= third) { want[s] = 1; any++; }
+    return any;
+}
+
+// Selection: bisect.insort order = (area ascending, discovery order descending), so the top three are the largest areas,
+// the raster-earlier contour first among equals.  Fills sel = (three slots or -1, go) and res->biggest_area; a frame that
+// fails the area gate gets CK_BOARD_TOO_SMALL.  Returns go: 1 when the frame has a ghost to draw.
+extern "C" int ck_board_rank(int nc, const int32_t* root, const double* area, const uint8_t* known, int h, int w,
+                             int32_t* sel, ck_board_result* res)
+{
+    sel[0] = sel[1] = sel[2] = -1;
+    sel[3] = 0;
+    std::vector<int> rank;
+    for (int s = 0; s < nc; s++) if (known[s]) rank.push_back(s);
+    if (rank.empty()) return 0;
+    std::sort(rank.begin(), rank.end(), [&](int a, int b) {
+        if (area[a] != area[b]) return area[a] > area[b];
+        return root[a] < root[b];                    // raster-earlier contour ranks higher
+    });
+    res->biggest_area = area[rank[0]];
+    const double frame_area = (double)h * (double)w;
+    if (!(frame_area / 3 < area[rank[0]])) { res->status = CK_BOARD_TOO_SMALL; return 0; }
+    for (int i = 0; i < 3 && i < (int)rank.size(); i++) sel[i] = rank[i];
+    sel[3] = 1;
+    return 1;
+}
+
+// Hough slab of hough_vote_peaks_kernel for a call of n frames: bytes per LDS row, inner theta rows per workgroup (+ 2 halo
+// rows) and threads.  -1 when not even one inner row fits.
+extern "C" int ck_hough_slab(int n, int h, int w, int small_n, int max_threads, size_t* row_bytes_out, int* rb_out, int* threads_out)
+{
+    const int stride = 2 * (w + h) + 1 + 2;
+    const size_t row_bytes = (size_t)((stride + 1) / 2) * 4;               // 16-bit counters, two per dword
+    int rb = (int)((144 * 1024) / row_bytes) - 2;                          // inner rows per workgroup (+ 2 halo rows)
+    if (rb > 10) rb = 10;
+    if (rb < 1) return -1;
+    int threads = max_threads;
+    // A call of a few frames (the hold-off-aware fold's windows, a live finder's single frame) is a latency matter, and
+    // next to the classifier -- two workgroups of 79 KB on every CU -- a workgroup that wants a whole CU's LDS waits until
+    // that kernel's grid drains: 1.5 ms of a 16-frame call's 3.0 (tools/board_call_latency.py).  Small batches take
+    // slabs that fit the hole ONE retiring classifier workgroup leaves (<= 72 KB, 512 threads): same peaks (rows with
+    // their halo, sorted on the host), more workgroups re-reading the point list.
+    if (n <= small_n) {
+        const int rs = (int)((72 * 1024) / row_bytes) - 2;
+        if (rs >= 1) { rb = rs < rb ? rs : rb; threads = max_threads < 512 ? max_threads : 512; }
+    }
+    *row_bytes_out = row_bytes; *rb_out = rb; *threads_out = threads;
+    return 0;
+}
+
+// One frame's Hough peaks, np pairs (accumulator index, count), as cv2.HoughLines hands them back: by count descending,
+// then index ascending, decoded to (rho, theta) in float32; at most cap lines are written.
+extern "C" void ck_peaks_to_lines(const int32_t* pf, int np, int numrho, int cap, float* lines)
+{
+    const float theta = (float)(3.1415926535897932384626433832795 / 180);
+    const double scale = 1. / (numrho + 2);
+    std::vector<int> order((size_t)np);
+    for (int i = 0; i < np; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        if (pf[2 * a + 1] != pf[2 * b + 1]) return pf[2 * a + 1] > pf[2 * b + 1];
+        return pf[2 * a] < pf[2 * b];
+    });
+    for (int i = 0; i < np && i < cap; i++) {
+        const int idx = pf[2 * order[i]];
+        const int nn = (int)floor(idx * scale) - 1;
+        const int rr = idx - (nn + 1) * (numrho + 2) - 1;
+        lines[(size_t)i * 2] = (rr - (numrho - 1) * 0.5f) * 1.f;
+        lines[(size_t)i * 2 + 1] = 0.f + nn * theta;
+    }
 }

@@ -25,8 +25,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <chrono>
-#include <thread>
 
 #include "ck_common.h"
 
@@ -165,113 +163,16 @@ __global__ __launch_bounds__(256) void prep_rows4_kernel(const uint8_t* __restri
     }
 }
 
-// Rows of up to 256*NS pixels, fully unrolled: all NS dword loads of the row are in flight at
-// once and the row takes ONE atomic on the frame's edge counter (the loop version above pays a
-// load round trip and an atomic per 256 pixels).
-// (Tried: writing a background pixel's parent only where later kernels read it -- next to an edge pixel, at x = 0 --
-// which needs the edge bits of the rows above and below: bit-exact, but the two extra row loads and the scattered
-// 4-byte stores cost more than the dense 16-byte stores they replace: ccl 7.95 against 7.65 us.)
-template <int NS>
-__global__ __launch_bounds__(256) void prep_rows4u_kernel(const uint8_t* __restrict__ edges, int h, int w,
-                                                          uint8_t* __restrict__ ez, int32_t* __restrict__ L,
-                                                          FrameTab* __restrict__ tab, int32_t* __restrict__ elist,
-                                                          const int* __restrict__ canny_border_flag)
-{
-    const int lane = threadIdx.x & 63;
-    const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int f = blockIdx.y;
-    if (y >= h) return;                                  // whole wave leaves together
-    // L still holds Canny's hysteresis labels: every edge pixel already points at the first pixel of its
-    // 8-connected component.  Unless an edge touched the image frame (cleared below, which may split a
-    // component) those parents are exactly what the edge unions would rebuild, so they are kept.
-    const bool keep_edge_parents = canny_border_flag != nullptr && canny_border_flag[f] == 0;
-    const size_t off = ((size_t)f * h + y) * w;
-    const bool row_inner = y > 0 && y < h - 1;
-    int32_t* E = elist + (size_t)f * h * w;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint32_t v[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int x = 256 * s + 4 * lane;
-        v[s] = 0;
-        if (x < w && row_inner) v[s] = *reinterpret_cast<const uint32_t*>(edges + off + x);
-    }
-    int nib[NS], before[NS];          // before: edge pixels of this row in earlier lanes / steps
-    unsigned long long has[NS];
-    int total = 0;
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int x = 256 * s + 4 * lane;
-        int nb = ((v[s] & 0xFFu) ? 1 : 0) | ((v[s] & 0xFF00u) ? 2 : 0) | ((v[s] & 0xFF0000u) ? 4 : 0) | ((v[s] & 0xFF000000u) ? 8 : 0);
-        if (x == 0) nb &= ~1;                            // cleared frame: first and last column
-        if (x + 3 == w - 1) nb &= ~8;
-        nib[s] = nb;
-        has[s] = __builtin_amdgcn_ballot_w64(nb != 0);
-        before[s] = total;
-        if (has[s]) {                                    // wave-uniform
-            const unsigned long long b0 = __builtin_amdgcn_ballot_w64(nb & 1), b1 = __builtin_amdgcn_ballot_w64(nb & 2);
-            const unsigned long long b2 = __builtin_amdgcn_ballot_w64(nb & 4), b3 = __builtin_amdgcn_ballot_w64(nb & 8);
-            before[s] += __builtin_popcountll(b0 & lt) + __builtin_popcountll(b1 & lt) +
-                         __builtin_popcountll(b2 & lt) + __builtin_popcountll(b3 & lt);
-            total += __builtin_popcountll(b0) + __builtin_popcountll(b1) + __builtin_popcountll(b2) + __builtin_popcountll(b3);
-        }
-    }
-    int base = 0;
-    if (total) {
-        if (lane == 0) base = atomicAdd(&tab[f].n_edges, total);
-        base = __builtin_amdgcn_readfirstlane(base);
-    }
-    int last_edge = -1;                                  // wave-uniform: last edge column of earlier steps
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int x = 256 * s + 4 * lane;
-        const int nb = nib[s];
-        const int my_last = nb ? x + 31 - __builtin_clz((unsigned)nb) : -1;
-        const unsigned long long below = has[s] & lt;
-        const int src = below ? 63 - __builtin_clzll(below) : 0;
-        int prev_last = __shfl(my_last, src);
-        if (!below) prev_last = last_edge;
-        if (x < w) {
-            *reinterpret_cast<uint32_t*>(ez + off + x) =
-                (nb & 1 ? 1u : 0u) | (nb & 2 ? 0x100u : 0u) | (nb & 4 ? 0x10000u : 0u) | (nb & 8 ? 0x1000000u : 0u);
-            int4 par;
-            int le = prev_last;
-            par.x = (nb & 1) ? y * w + x : y * w + le + 1;
-            if (nb & 1) le = x;
-            par.y = (nb & 2) ? y * w + x + 1 : y * w + le + 1;
-            if (nb & 2) le = x + 1;
-            par.z = (nb & 4) ? y * w + x + 2 : y * w + le + 1;
-            if (nb & 4) le = x + 2;
-            par.w = (nb & 8) ? y * w + x + 3 : y * w + le + 1;
-            if (keep_edge_parents && nb) {
-                const int4 old = *reinterpret_cast<const int4*>(L + off + x);
-                if (nb & 1) par.x = old.x;
-                if (nb & 2) par.y = old.y;
-                if (nb & 4) par.z = old.z;
-                if (nb & 8) par.w = old.w;
-            }
-            *reinterpret_cast<int4*>(L + off + x) = par;
-            int slot = base + before[s];
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (nb & (1 << k)) E[slot++] = y * w + x + k;
-        }
-        if (has[s]) last_edge = __shfl(my_last, 63 - __builtin_clzll(has[s]));
-    }
-}
-
 // ---- B. unions: edge pixels (8-connectivity) and background runs (4-connectivity) -------
 // Work items: every edge pixel, plus one item per image row for the run that starts at x = 0.
 // A stretch of columns where this row and the row above are both background starts either at
 // x = 0 or right after an edge pixel of one of the two rows: one union per stretch.
 __global__ __launch_bounds__(256) void link_list_kernel(const uint8_t* __restrict__ ez, int h, int w,
                                                         int32_t* __restrict__ labels, const FrameTab* __restrict__ tab,
-                                                        const int32_t* __restrict__ elist,
-                                                        const int* __restrict__ canny_border_flag)
+                                                        const int32_t* __restrict__ elist)
 {
     int f, bx;
     list_frame_block(LIST_BLOCKS, f, bx);
-    const bool edges_linked = canny_border_flag != nullptr && canny_border_flag[f] == 0;   // parents kept from Canny
     const int ne = tab[f].n_edges;
     const uint8_t* e = ez + (size_t)f * h * w;
     int32_t* L = labels + (size_t)f * h * w;
@@ -279,13 +180,11 @@ __global__ __launch_bounds__(256) void link_list_kernel(const uint8_t* __restric
     for (int i = bx * 256 + threadIdx.x; i < ne + h - 1; i += LIST_BLOCKS * 256) {
         if (i < ne) {
             const int p = E[i];                        // 1 <= x <= w-2, 1 <= y <= h-2
-            if (!edges_linked) {
-                if (e[p - 1]) uf_union(L, p, p - 1);
-                if (e[p - w]) uf_union(L, p, p - w);
-                else {
-                    if (e[p - w - 1]) uf_union(L, p, p - w - 1);
-                    if (e[p - w + 1]) uf_union(L, p, p - w + 1);
-                }
+            if (e[p - 1]) uf_union(L, p, p - 1);
+            if (e[p - w]) uf_union(L, p, p - w);
+            else {
+                if (e[p - w - 1]) uf_union(L, p, p - w - 1);
+                if (e[p - w + 1]) uf_union(L, p, p - w + 1);
             }
             const int q1 = p + 1, q2 = p + w + 1;      // background stretches opening right of p
             if (!e[q1] && !e[q1 - w]) uf_union(L, q1, q1 - w);
@@ -302,12 +201,10 @@ __global__ __launch_bounds__(256) void link_list_kernel(const uint8_t* __restric
 // ---- C. flatten the nodes that later lookups go through --------------------------------
 __global__ __launch_bounds__(256) void flatten_list_kernel(const uint8_t* __restrict__ ez, int h, int w,
                                                            int32_t* __restrict__ labels, const FrameTab* __restrict__ tab,
-                                                           const int32_t* __restrict__ elist,
-                                                           const int* __restrict__ canny_border_flag)
+                                                           const int32_t* __restrict__ elist)
 {
     int f, bx;
     list_frame_block(LIST_BLOCKS, f, bx);
-    const bool edges_flat = canny_border_flag != nullptr && canny_border_flag[f] == 0;   // Canny left every edge pixel at its root
     const int ne = tab[f].n_edges;
     const size_t off = (size_t)f * h * w;
     const uint8_t* e = ez + off;
@@ -316,7 +213,7 @@ __global__ __launch_bounds__(256) void flatten_list_kernel(const uint8_t* __rest
     for (int i = bx * 256 + threadIdx.x; i < ne + h; i += LIST_BLOCKS * 256) {
         if (i < ne) {
             const int p = E[i];
-            if (!edges_flat) L[p] = uf_find(L, p);
+            L[p] = uf_find(L, p);
             if (!e[p + 1]) L[p + 1] = uf_find(L, p + 1);       // head of the run right of p
         } else {
             const int q = (i - ne) * w;
@@ -332,6 +229,19 @@ __device__ __forceinline__ bool in_s0(const int32_t* L, int q, int root0)
 }
 
 // ---- D. top-level roots -------------------------------------------------------------------
+// p is the first pixel of a top-level component: it takes the next slot of its frame's tables, with an empty bounding box
+__device__ __forceinline__ void claim_root(int f, size_t off, int p, int32_t* __restrict__ compid, FrameTab* __restrict__ tab, int maxc,
+                                           int32_t* __restrict__ roots, int32_t* __restrict__ aabb)
+{
+    const int slot = atomicAdd(&tab[f].n_roots, 1);
+    if (slot >= maxc) { tab[f].overflow = 1; compid[off + p] = -1; return; }
+    compid[off + p] = slot;
+    int32_t* fr = roots + (size_t)f * maxc;      // the frame's table on its own: f * maxc stays hoisted out of the callers' loops
+    fr[slot] = p;
+    int32_t* bb = aabb + ((size_t)f * maxc + slot) * 4;
+    bb[0] = 0x7fffffff; bb[1] = -1; bb[2] = 0x7fffffff; bb[3] = -1;
+}
+
 __global__ __launch_bounds__(256) void roots_list_kernel(int h, int w, const int32_t* __restrict__ labels,
                                                          int32_t* __restrict__ compid, FrameTab* __restrict__ tab, int maxc,
                                                          int32_t* __restrict__ roots, int32_t* __restrict__ aabb,
@@ -348,16 +258,41 @@ __global__ __launch_bounds__(256) void roots_list_kernel(int h, int w, const int
         const int p = E[i];
         if (L[p] != p) continue;
         if (!in_s0(L, p - 1, root0)) continue;      // west neighbour of a first pixel is background
-        const int slot = atomicAdd(&tab[f].n_roots, 1);
-        if (slot >= maxc) { tab[f].overflow = 1; compid[off + p] = -1; continue; }
-        compid[off + p] = slot;
-        roots[(size_t)f * maxc + slot] = p;
-        int32_t* bb = aabb + ((size_t)f * maxc + slot) * 4;
-        bb[0] = 0x7fffffff; bb[1] = -1; bb[2] = 0x7fffffff; bb[3] = -1;
+        claim_root(f, off, p, compid, tab, maxc, roots, aabb);
     }
 }
 
 // ---- E. outer-border list + bounding boxes ----------------------------------------------
+// Bounding boxes, called by the whole wave: lanes with `b` hold a border pixel p of the component in slot cslot.  A wave's
+// border pixels belong to one component or to a few; reduce per component inside the wave and let one lane update the
+// box -- and only where the box actually grows (a relaxed read first: a stale value merely costs a redundant atomic,
+// min / max are monotone), so the big contours stop hammering four addresses
+__device__ __forceinline__ void grow_boxes(bool b, int cslot, int p, int w, int f, int maxc, int32_t* __restrict__ aabb)
+{
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(b);
+    const int y = p / w, x = p - y * w;
+    const int lane = threadIdx.x & 63;
+    while (todo) {
+        const int lead = __builtin_ctzll(todo);
+        const int s_lead = __builtin_amdgcn_readlane(cslot, lead);
+        const bool mine = b && cslot == s_lead;
+        todo &= ~__builtin_amdgcn_ballot_w64(mine);
+        int mnx = mine ? x : 0x7fffffff, mxx = mine ? x : -1, mny = mine ? y : 0x7fffffff, mxy = mine ? y : -1;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            mnx = min(mnx, __shfl_xor(mnx, d)); mxx = max(mxx, __shfl_xor(mxx, d));
+            mny = min(mny, __shfl_xor(mny, d)); mxy = max(mxy, __shfl_xor(mxy, d));
+        }
+        if (lane == lead) {
+            int32_t* bb = aabb + ((size_t)f * maxc + s_lead) * 4;
+            if (mnx < uf_load(bb, 0)) atomicMin(bb + 0, mnx);
+            if (mxx > uf_load(bb, 1)) atomicMax(bb + 1, mxx);
+            if (mny < uf_load(bb, 2)) atomicMin(bb + 2, mny);
+            if (mxy > uf_load(bb, 3)) atomicMax(bb + 3, mxy);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void border_list_kernel(const uint8_t* __restrict__ ez, int h, int w,
                                                           const int32_t* __restrict__ labels, const int32_t* __restrict__ compid,
                                                           int maxc, FrameTab* __restrict__ tab, int32_t* __restrict__ aabb,
@@ -397,33 +332,7 @@ __global__ __launch_bounds__(256) void border_list_kernel(const uint8_t* __restr
                 if ((unsigned)cslot >= (unsigned)maxc) b = false;
             }
         }
-        // bounding boxes: a wave's border pixels belong to one component or to a few; reduce per component inside the wave
-        // and let one lane update the box -- and only where the box actually grows (a relaxed read first: a stale value
-        // merely costs a redundant atomic, min / max are monotone), so the big contours stop hammering four addresses
-        {
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(b);
-            const int y = p / w, x = p - y * w;
-            const int lane = threadIdx.x & 63;
-            while (todo) {
-                const int lead = __builtin_ctzll(todo);
-                const int s_lead = __builtin_amdgcn_readlane(cslot, lead);
-                const bool mine = b && cslot == s_lead;
-                todo &= ~__builtin_amdgcn_ballot_w64(mine);
-                int mnx = mine ? x : 0x7fffffff, mxx = mine ? x : -1, mny = mine ? y : 0x7fffffff, mxy = mine ? y : -1;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    mnx = min(mnx, __shfl_xor(mnx, d)); mxx = max(mxx, __shfl_xor(mxx, d));
-                    mny = min(mny, __shfl_xor(mny, d)); mxy = max(mxy, __shfl_xor(mxy, d));
-                }
-                if (lane == lead) {
-                    int32_t* bb = aabb + ((size_t)f * maxc + s_lead) * 4;
-                    if (mnx < uf_load(bb, 0)) atomicMin(bb + 0, mnx);
-                    if (mxx > uf_load(bb, 1)) atomicMax(bb + 1, mxx);
-                    if (mny < uf_load(bb, 2)) atomicMin(bb + 2, mny);
-                    if (mxy > uf_load(bb, 3)) atomicMax(bb + 3, mxy);
-                }
-            }
-        }
+        grow_boxes(b, cslot, p, w, f, maxc, aabb);
         const int slot = wave_append(&tab[f].n_border, b);
         if (b) B[slot] = p;
     }
@@ -484,11 +393,11 @@ __device__ __forceinline__ unsigned long long row16_or(unsigned long long v)
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// A'. one wave per image row: cleared-frame edge bytes (later kernels read them), bit words + rank prefix, the row's
-// segment of the edge list, the run nodes' parents.  Rows of up to 256 * NS pixels, all loads of a row in flight at once.
+// A'. one wave per image row: bit words + rank prefix, the row's segment of the edge list, the run nodes' parents.  (No
+// cleared-frame edge bytes: the run-table form never reads them, and the gather's hull-candidate test reads the edge
+// image as it came in: round 4.)  Rows of up to 256 * NS pixels, all loads of a row in flight at once.
 template <int NS>
-__global__ __launch_bounds__(256) void prep_runs_kernel(const uint8_t* __restrict__ edges, int h, int w,
-                                                        uint8_t* __restrict__ ez, int32_t* __restrict__ L,
+__global__ __launch_bounds__(256) void prep_runs_kernel(const uint8_t* __restrict__ edges, int h, int w, int32_t* __restrict__ L,
                                                         FrameTab* __restrict__ tab, int32_t* __restrict__ elist, RunTab rt,
                                                         const int* __restrict__ canny_border_flag)
 {
@@ -563,9 +472,6 @@ __global__ __launch_bounds__(256) void prep_runs_kernel(const uint8_t* __restric
         const int nb = nib[s];
         const unsigned long long word = row16_or((unsigned long long)nb << (4 * (lane & 15)));
         if (x < w) {
-            if (ez)                                      // (the run-table form itself never reads the cleared bytes: round 4)
-                *reinterpret_cast<uint32_t*>(ez + off + x) =
-                    (nb & 1 ? 1u : 0u) | (nb & 2 ? 0x100u : 0u) | (nb & 4 ? 0x10000u : 0u) | (nb & 8 ? 0x1000000u : 0u);
             if ((lane & 15) == 0) {
                 bw[4 * s + (lane >> 4)] = word;
                 rw[4 * s + (lane >> 4)] = (uint16_t)before[s];
@@ -671,12 +577,7 @@ __global__ __launch_bounds__(256) void roots_runs_kernel(int h, int w, const int
         const int y = p / w;
         const int west = (i == rb[y]) ? y : h + i - 1;  // the west neighbour of a component's first pixel is background
         if (rp[west] != root0) continue;
-        const int slot = atomicAdd(&tab[f].n_roots, 1);
-        if (slot >= maxc) { tab[f].overflow = 1; compid[off + p] = -1; continue; }
-        compid[off + p] = slot;
-        roots[(size_t)f * maxc + slot] = p;
-        int32_t* bb = aabb + ((size_t)f * maxc + slot) * 4;
-        bb[0] = 0x7fffffff; bb[1] = -1; bb[2] = 0x7fffffff; bb[3] = -1;
+        claim_root(f, off, p, compid, tab, maxc, roots, aabb);
     }
 }
 
@@ -723,31 +624,7 @@ __global__ __launch_bounds__(256) void border_runs_kernel(int h, int w, const in
                 if ((unsigned)cslot >= (unsigned)maxc) b = false;
             }
         }
-        // bounding boxes: reduce per component inside the wave, one lane updates the box and only where it grows
-        {
-            unsigned long long todo = __builtin_amdgcn_ballot_w64(b);
-            const int y = p / w, x = p - y * w;
-            const int lane = threadIdx.x & 63;
-            while (todo) {
-                const int lead = __builtin_ctzll(todo);
-                const int s_lead = __builtin_amdgcn_readlane(cslot, lead);
-                const bool mine = b && cslot == s_lead;
-                todo &= ~__builtin_amdgcn_ballot_w64(mine);
-                int mnx = mine ? x : 0x7fffffff, mxx = mine ? x : -1, mny = mine ? y : 0x7fffffff, mxy = mine ? y : -1;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    mnx = min(mnx, __shfl_xor(mnx, d)); mxx = max(mxx, __shfl_xor(mxx, d));
-                    mny = min(mny, __shfl_xor(mny, d)); mxy = max(mxy, __shfl_xor(mxy, d));
-                }
-                if (lane == lead) {
-                    int32_t* bb = aabb + ((size_t)f * maxc + s_lead) * 4;
-                    if (mnx < uf_load(bb, 0)) atomicMin(bb + 0, mnx);
-                    if (mxx > uf_load(bb, 1)) atomicMax(bb + 1, mxx);
-                    if (mny < uf_load(bb, 2)) atomicMin(bb + 2, mny);
-                    if (mxy > uf_load(bb, 3)) atomicMax(bb + 3, mxy);
-                }
-            }
-        }
+        grow_boxes(b, cslot, p, w, f, maxc, aabb);
         const int slot = wave_append(&tab[f].n_border, b);
         if (b) B[slot] = p;
     }
@@ -794,14 +671,19 @@ __device__ __forceinline__ bool mid_of_run_raw(const uint8_t* e, int p, int w, i
     return (at(0, -1) && at(0, 1)) || (at(-1, 0) && at(1, 0)) || (at(-1, -1) && at(1, 1)) || (at(-1, 1) && at(1, -1));
 }
 
+// a hull candidate: a border pixel outside the middle of every straight run (raw: `e` is the edge image as it came in)
+__device__ __forceinline__ bool hull_candidate(const uint8_t* __restrict__ ez, size_t off, int p, int w, int h, int raw)
+{
+    return !(raw ? mid_of_run_raw(ez + off, p, w, h) : mid_of_run(ez + off, p, w));
+}
+
 // ---- F. gather hull-candidate points of the components the host asked for ---------------
 __global__ __launch_bounds__(256) void gather_points_kernel(const uint8_t* __restrict__ ez, int h, int w,
                                                             const int32_t* __restrict__ labels, const int32_t* __restrict__ compid,
                                                             int maxc, const uint8_t* __restrict__ want, int wpitch, const FrameTab* __restrict__ tab,
                                                             const int32_t* __restrict__ blist, int32_t* __restrict__ counter, int cap,
                                                             int32_t* __restrict__ pts /* x|y<<16, slot ; then frame */,
-                                                            int keep_mid /* 1: every border pixel, not only hull candidates */,
-                                                            int raw = 0 /* 1: `ez` is the edge image as it came in (frame not cleared) */)
+                                                            int raw /* 1: `ez` is the edge image as it came in (frame not cleared) */)
 {
     int f, bx;
     list_frame_block(LIST_BLOCKS, f, bx);
@@ -816,7 +698,7 @@ __global__ __launch_bounds__(256) void gather_points_kernel(const uint8_t* __res
         if (i < nb) {
             p = B[i];
             slot = compid[off + labels[off + p]];
-            take = want[(size_t)f * wpitch + slot] && (keep_mid || !(raw ? mid_of_run_raw(ez + off, p, w, h) : mid_of_run(ez + off, p, w)));
+            take = want[(size_t)f * wpitch + slot] && hull_candidate(ez, off, p, w, h, raw);
         }
         const int k = wave_append(counter, take);           // one atomic per wave
         if (take && k < cap) {
@@ -852,7 +734,7 @@ __global__ __launch_bounds__(256) void gather_segments_kernel(const uint8_t* __r
         if (i < nb) {
             p = B[i];
             slot = compid[off + labels[off + p]];
-            take = want[(size_t)f * wpitch + slot] && !(raw ? mid_of_run_raw(ez + off, p, w, h) : mid_of_run(ez + off, p, w));
+            take = want[(size_t)f * wpitch + slot] && hull_candidate(ez, off, p, w, h, raw);
         }
         const int k = wave_append(fcnt + f, take);
         if (take && k < cap) {
@@ -1115,326 +997,317 @@ __global__ __launch_bounds__(HOUGH_THREADS) void hough_vote_peaks_kernel(const u
     }
 }
 
-template <typename F>
-void parallel_for(int n, F fn) { ck_parallel_for(n, 16, fn); }
-
-struct Comp {
-    int root;       // first pixel (raster index) = discovery order key
-    int slot;
-    double ub;      // bounding-box area: upper bound of the minAreaRect area
-    double area;    // exact area once known
-    bool known;
+// ---- host: labelling set-up, shared by k_board_lines and k_contour_survey -------------------------------------------
+// The labelling scratch of a call, carved out of the context's buffers: cleared-frame edge bytes (ghost), union-find
+// parents (labels), the slot of every root (labels2: only read at roots), edge list + border list (lists), the per-frame
+// counters at the head of misc, the root and bounding-box tables at the head of comp.
+struct LabelScratch {
+    uint8_t* ez;
+    int32_t *L, *compid, *elist, *blist;
+    FrameTab* d_tab;
+    int32_t *d_roots, *d_aabb;
+    int maxc;
+    size_t fpx, npx, tab_bytes;
+    dim3 lgrid;
 };
 
-}  // namespace
-
-int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,
-                  float* lines, int cap, ck_board_result* res, uint8_t* d_ghost_out, const int* d_canny_border_flag)
+// misc_extra: bytes the caller keeps behind the counters in misc; comp_extra: bytes per component behind the two tables
+int label_scratch(ck_ctx* ctx, int n, int h, int w, size_t misc_extra, size_t comp_extra, LabelScratch& s)
 {
-    static const bool prof = getenv("CK_PROFILE_HOST") != nullptr;   // debugging aid: host-side lap times on stderr
-    auto t_start = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!prof) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[board_lines] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_start).count());
-        t_start = now;
-    };
-    const size_t fpx = (size_t)h * w, npx = fpx * n;
-    int maxc = (int)(fpx / 4 + 1);
-    if (maxc > MAXC_LIMIT) maxc = MAXC_LIMIT;
-    const int pcap = (int)(fpx < (1u << 16) ? fpx : (fpx / 8 > (1u << 16) ? fpx / 8 : (1u << 16)));
-    const int numrho = 2 * (w + h) + 1;
-    const int stride = numrho + 2;
-    if (w > 65535 || h > 65535) return ck_fail(ctx, CK_ERR_ARG, "image side > 65535");
+    s.fpx = (size_t)h * w, s.npx = s.fpx * n;
+    s.maxc = (int)(s.fpx / 4 + 1);
+    if (s.maxc > MAXC_LIMIT) s.maxc = MAXC_LIMIT;
+    s.tab_bytes = sizeof(FrameTab) * (size_t)n;
+    CK_TRY(ck_ensure(ctx, ctx->ghost, s.npx));                       // ez
+    CK_TRY(ck_ensure(ctx, ctx->labels, s.npx * 4));
+    CK_TRY(ck_ensure(ctx, ctx->labels2, s.npx * 4));                 // compid
+    CK_TRY(ck_ensure(ctx, ctx->lists, s.npx * 8));                   // edge list + border list
+    CK_TRY(ck_ensure(ctx, ctx->misc, s.tab_bytes + misc_extra + 64));
+    CK_TRY(ck_ensure(ctx, ctx->comp, (size_t)n * s.maxc * (4 + 16 + comp_extra)));
+    s.ez = (uint8_t*)ctx->ghost.p;
+    s.L = (int32_t*)ctx->labels.p;
+    s.compid = (int32_t*)ctx->labels2.p;
+    s.elist = (int32_t*)ctx->lists.p;
+    s.blist = s.elist + s.npx;
+    s.d_tab = (FrameTab*)ctx->misc.p;
+    s.d_roots = (int32_t*)ctx->comp.p;
+    s.d_aabb = s.d_roots + (size_t)n * s.maxc;
+    s.lgrid = list_grid(LIST_BLOCKS, n);
+    return CK_OK;
+}
 
-    CK_TRY(ck_ensure(ctx, ctx->ghost, npx));                       // ez
-    CK_TRY(ck_ensure(ctx, ctx->labels, npx * 4));
-    CK_TRY(ck_ensure(ctx, ctx->labels2, npx * 4));                 // compid (only read at roots)
-    CK_TRY(ck_ensure(ctx, ctx->lists, npx * 8));                   // edge list + border list
-    const size_t tab_bytes = sizeof(FrameTab) * (size_t)n;
-    const size_t sel_bytes = sizeof(int32_t) * 4 * (size_t)n;
-    CK_TRY(ck_ensure(ctx, ctx->misc, tab_bytes + sel_bytes + 4 * NUMANGLE * 2 + 64));
-    CK_TRY(ck_ensure(ctx, ctx->comp, (size_t)n * maxc * (4 + 16 + 1)));
-    uint8_t* ez = (uint8_t*)ctx->ghost.p;
-    int32_t* L = (int32_t*)ctx->labels.p;
-    int32_t* compid = (int32_t*)ctx->labels2.p;
-    int32_t* elist = (int32_t*)ctx->lists.p;
-    int32_t* blist = elist + npx;
-    FrameTab* d_tab = (FrameTab*)ctx->misc.p;
-    int32_t* d_sel = (int32_t*)((char*)ctx->misc.p + tab_bytes);
-    float* d_trig = (float*)((char*)ctx->misc.p + tab_bytes + sel_bytes);
-    int32_t* d_roots = (int32_t*)ctx->comp.p;
-    int32_t* d_aabb = d_roots + (size_t)n * maxc;
-    uint8_t* d_want = (uint8_t*)(d_aabb + (size_t)n * maxc * 4);
+// the dword path needs 4-byte aligned rows: w % 4 == 0 and an aligned base pointer
+bool dword_rows(const uint8_t* d_edges, int w) { return (w & 3) == 0 && ((uintptr_t)d_edges & 3) == 0; }
 
-    const dim3 lgrid = list_grid(LIST_BLOCKS, n), lblock(256);
-    // the dword path needs 4-byte aligned rows: w % 4 == 0 and an aligned base pointer
-    const bool dwords = (w & 3) == 0 && ((uintptr_t)d_edges & 3) == 0;
-    bool run_table = dwords && w <= 4096;
-    auto launch_ccl = [&](bool runs) -> int {
-        TimeScope ts(ctx, "ccl");
-        CK_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_bytes, ctx->stream));
-        if (runs) {
-            // run-table form: no dense parent image.  Reuse of Canny's component roots (ck_board_detect only) needs this
-            // form's row kernel, which preserves them.
-            const int* kflag = d_canny_border_flag;
-            RunTab rt;
-            rt.w64 = (w + 63) / 64;
-            // run nodes for a quarter of the pixels (at least 64 K): a frame with more edge pixels than that sends the
-            // call to the dense form below
-            const size_t cap_e = std::min(fpx, std::max(fpx / 4, (size_t)1 << 16));
-            rt.cap_e = (int)cap_e;
-            rt.rp_stride = cap_e + (size_t)h;
-            const size_t bits_b = (size_t)n * h * rt.w64 * 8, rank_b = (size_t)n * h * rt.w64 * 2, rb_b = (size_t)n * h * 4;
-            const size_t rank_o = bits_b, rb_o = (rank_o + rank_b + 15) & ~(size_t)15, rp_o = (rb_o + rb_b + 15) & ~(size_t)15;
-            CK_TRY(ck_ensure(ctx, ctx->runs, rp_o + (size_t)n * rt.rp_stride * 4));
-            rt.bits = (unsigned long long*)ctx->runs.p;
-            rt.rank = (uint16_t*)((char*)ctx->runs.p + rank_o);
-            rt.rowbase = (int32_t*)((char*)ctx->runs.p + rb_o);
-            rt.rp = (int32_t*)((char*)ctx->runs.p + rp_o);
-            if (w <= 1024)
-                hipLaunchKernelGGL(prep_runs_kernel<4>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
-            else if (w <= 2048)
-                hipLaunchKernelGGL(prep_runs_kernel<8>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
-            else
-                hipLaunchKernelGGL(prep_runs_kernel<16>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, (uint8_t*)nullptr, L, d_tab, elist, rt, kflag);
-            hipLaunchKernelGGL(link_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, L, (const FrameTab*)d_tab, (const int32_t*)elist, rt, kflag);
-            hipLaunchKernelGGL(flatten_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, L, (const FrameTab*)d_tab, (const int32_t*)elist, rt, kflag);
-            hipLaunchKernelGGL(roots_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, compid, d_tab, maxc,
-                               d_roots, d_aabb, (const int32_t*)elist, rt);
-            hipLaunchKernelGGL(border_runs_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, (const int32_t*)compid, maxc,
-                               d_tab, d_aabb, (const int32_t*)elist, blist, rt);
-        } else {
-            // dense form: every label rebuilt from the edge map (Canny's are not reused)
-            if (dwords)
-                hipLaunchKernelGGL(prep_rows4_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, ez, L, d_tab, elist);
-            else
-                hipLaunchKernelGGL(prep_rows_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, ez, L, d_tab, elist);
-            hipLaunchKernelGGL(link_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, L,
-                               (const FrameTab*)d_tab, (const int32_t*)elist, (const int*)nullptr);
-            hipLaunchKernelGGL(flatten_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, L,
-                               (const FrameTab*)d_tab, (const int32_t*)elist, (const int*)nullptr);
-            hipLaunchKernelGGL(roots_list_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, compid, d_tab, maxc,
-                               d_roots, d_aabb, (const int32_t*)elist);
-            hipLaunchKernelGGL(border_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, (const int32_t*)L,
-                               (const int32_t*)compid, maxc, d_tab, d_aabb, (const int32_t*)elist, blist);
-        }
-        CK_HIP(ctx, hipGetLastError());
-        return CK_OK;
-    };
-    CK_TRY(launch_ccl(run_table));
+// steps A..E, dense form: every label rebuilt from the edge map (Canny's are not reused)
+int label_dense(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, const LabelScratch& s)
+{
+    const dim3 lblock(256);
+    CK_HIP(ctx, hipMemsetAsync(s.d_tab, 0, s.tab_bytes, ctx->stream));
+    if (dword_rows(d_edges, w))
+        hipLaunchKernelGGL(prep_rows4_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, s.ez, s.L, s.d_tab, s.elist);
+    else
+        hipLaunchKernelGGL(prep_rows_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, s.ez, s.L, s.d_tab, s.elist);
+    hipLaunchKernelGGL(link_list_kernel, s.lgrid, lblock, 0, ctx->stream, (const uint8_t*)s.ez, h, w, s.L,
+                       (const FrameTab*)s.d_tab, (const int32_t*)s.elist);
+    hipLaunchKernelGGL(flatten_list_kernel, s.lgrid, lblock, 0, ctx->stream, (const uint8_t*)s.ez, h, w, s.L,
+                       (const FrameTab*)s.d_tab, (const int32_t*)s.elist);
+    hipLaunchKernelGGL(roots_list_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)s.L, s.compid, s.d_tab, s.maxc,
+                       s.d_roots, s.d_aabb, (const int32_t*)s.elist);
+    hipLaunchKernelGGL(border_list_kernel, s.lgrid, lblock, 0, ctx->stream, (const uint8_t*)s.ez, h, w, (const int32_t*)s.L,
+                       (const int32_t*)s.compid, s.maxc, s.d_tab, s.d_aabb, (const int32_t*)s.elist, s.blist);
+    CK_HIP(ctx, hipGetLastError());
+    return CK_OK;
+}
 
-    lap("ccl kernels");
-    // ---- host: component tables (one strided copy each) -------------------------------------
-    std::vector<FrameTab> tab((size_t)n);
-    CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (run_table) {
-        bool redo = false;
-        for (int f = 0; f < n; f++) redo = redo || tab[f].runs_overflow;
-        if (redo) {                                       // an edge map denser than the run nodes provided for: dense form
-            run_table = false;
-            CK_TRY(launch_ccl(false));
-            CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    int nc_max = 0;
-    for (int f = 0; f < n; f++) {
-        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: more than %d external contours", f, maxc);
-        nc_max = std::max(nc_max, tab[f].n_roots);
-    }
-    std::vector<std::vector<Comp>> comps((size_t)n);
+// steps A'..E', run-table form: no dense parent image.  Reuse of Canny's component roots (kflag, ck_board_detect only)
+// needs this form's row kernel, which preserves them.
+int label_runs(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, const LabelScratch& s, const int* kflag)
+{
+    const dim3 lblock(256);
+    CK_HIP(ctx, hipMemsetAsync(s.d_tab, 0, s.tab_bytes, ctx->stream));
+    RunTab rt;
+    rt.w64 = (w + 63) / 64;
+    // run nodes for a quarter of the pixels (at least 64 K): a frame with more edge pixels than that sends the call to
+    // the dense form
+    const size_t cap_e = std::min(s.fpx, std::max(s.fpx / 4, (size_t)1 << 16));
+    rt.cap_e = (int)cap_e;
+    rt.rp_stride = cap_e + (size_t)h;
+    const size_t bits_b = (size_t)n * h * rt.w64 * 8, rank_b = (size_t)n * h * rt.w64 * 2, rb_b = (size_t)n * h * 4;
+    const size_t rank_o = bits_b, rb_o = (rank_o + rank_b + 15) & ~(size_t)15, rp_o = (rb_o + rb_b + 15) & ~(size_t)15;
+    CK_TRY(ck_ensure(ctx, ctx->runs, rp_o + (size_t)n * rt.rp_stride * 4));
+    rt.bits = (unsigned long long*)ctx->runs.p;
+    rt.rank = (uint16_t*)((char*)ctx->runs.p + rank_o);
+    rt.rowbase = (int32_t*)((char*)ctx->runs.p + rb_o);
+    rt.rp = (int32_t*)((char*)ctx->runs.p + rp_o);
+    if (w <= 1024)
+        hipLaunchKernelGGL(prep_runs_kernel<4>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, s.L, s.d_tab, s.elist, rt, kflag);
+    else if (w <= 2048)
+        hipLaunchKernelGGL(prep_runs_kernel<8>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, s.L, s.d_tab, s.elist, rt, kflag);
+    else
+        hipLaunchKernelGGL(prep_runs_kernel<16>, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, s.L, s.d_tab, s.elist, rt, kflag);
+    hipLaunchKernelGGL(link_runs_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, s.L, (const FrameTab*)s.d_tab, (const int32_t*)s.elist, rt, kflag);
+    hipLaunchKernelGGL(flatten_runs_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, s.L, (const FrameTab*)s.d_tab, (const int32_t*)s.elist, rt, kflag);
+    hipLaunchKernelGGL(roots_runs_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)s.L, s.compid, s.d_tab, s.maxc,
+                       s.d_roots, s.d_aabb, (const int32_t*)s.elist, rt);
+    hipLaunchKernelGGL(border_runs_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)s.L, (const int32_t*)s.compid, s.maxc,
+                       s.d_tab, s.d_aabb, (const int32_t*)s.elist, s.blist, rt);
+    CK_HIP(ctx, hipGetLastError());
+    return CK_OK;
+}
+
+// ---- host: the stages of k_board_lines ----------------------------------------------------------------------------------
+// What the stages share.  The components of all frames lie end to end in root / ub / area / known (see ck_board_round_want,
+// ck_host_geom.cpp): frame f has the entries first[f] .. first[f + 1], its table slot s at first[f] + s.
+struct Board {
+    ck_ctx* ctx;
+    const uint8_t* d_edges;
+    int n, h, w;
+    HostLap lap;
+    LabelScratch s;
+    int32_t* d_sel;              // behind the counters in misc: (three slots, go) per frame, then the trig tables
+    float* d_trig;
+    uint8_t* d_want;             // behind the tables in comp: one byte per component
+    bool run_table;
+    std::vector<FrameTab> tab;   // the counters as last downloaded
+    int nc_max;
+    std::vector<size_t> first;
+    std::vector<int32_t> root;
+    std::vector<double> ub, area;
+    std::vector<uint8_t> known;
+
+    int fetch_tab()
     {
+        CK_HIP(ctx, hipMemcpyAsync(tab.data(), s.d_tab, s.tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CK_OK;
+    }
+
+    // K3: labelling in the run-table form where the rows allow it, redone in the dense form when a frame's edge map is denser
+    // than the run nodes provided for; the counters come down
+    int label(const int* d_canny_border_flag)
+    {
+        run_table = dword_rows(d_edges, w) && w <= 4096;
+        auto launch_ccl = [&](bool runs) -> int {
+            TimeScope ts(ctx, "ccl");
+            return runs ? label_runs(ctx, d_edges, n, h, w, s, d_canny_border_flag) : label_dense(ctx, d_edges, n, h, w, s);
+        };
+        CK_TRY(launch_ccl(run_table));
+        lap("ccl kernels");
+        tab.resize((size_t)n);
+        CK_TRY(fetch_tab());
+        if (run_table) {
+            bool redo = false;
+            for (int f = 0; f < n; f++) redo = redo || tab[f].runs_overflow;
+            if (redo) {                                       // an edge map denser than the run nodes provided for: dense form
+                run_table = false;
+                CK_TRY(launch_ccl(false));
+                CK_TRY(fetch_tab());
+            }
+        }
+        return CK_OK;
+    }
+
+    // component tables (one packed copy each) -> res and the components with their bounding-box areas
+    int tables(ck_board_result* res)
+    {
+        nc_max = 0;
+        first.assign((size_t)n + 1, 0);
+        for (int f = 0; f < n; f++) {
+            if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: more than %d external contours", f, s.maxc);
+            nc_max = std::max(nc_max, tab[f].n_roots);
+            first[f + 1] = first[f] + (size_t)tab[f].n_roots;
+        }
         std::vector<int32_t> hroots((size_t)n * nc_max), haabb((size_t)n * nc_max * 4);
         if (nc_max) {
             const size_t cnt = (size_t)n * nc_max;
             CK_TRY(ck_ensure(ctx, ctx->pts, cnt * 20 + 64));
             int32_t* d_pack = (int32_t*)ctx->pts.p;
             hipLaunchKernelGGL(pack_tables_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const int32_t*)d_roots, (const int32_t*)d_aabb, maxc, nc_max, n, d_pack);
+                               (const int32_t*)s.d_roots, (const int32_t*)s.d_aabb, s.maxc, nc_max, n, d_pack);
             CK_HIP(ctx, hipMemcpyAsync(hroots.data(), d_pack, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
             CK_HIP(ctx, hipMemcpyAsync(haabb.data(), d_pack + cnt, cnt * 16, hipMemcpyDeviceToHost, ctx->stream));
             CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
+        const size_t total = first[(size_t)n];
+        root.resize(total); ub.resize(total); area.assign(total, 0.0); known.resize(total);
         for (int f = 0; f < n; f++) {
             const int nc = tab[f].n_roots;
             res[f].status = nc == 0 ? CK_BOARD_NO_CONTOUR : CK_BOARD_LINES;
             res[f].n_contours = nc; res[f].n_lines = 0; res[f].reserved = 0; res[f].biggest_area = 0;
-            auto& cv = comps[f];
-            cv.resize((size_t)nc);
             const int32_t* hr = hroots.data() + (size_t)f * nc_max;
             const int32_t* hb = haabb.data() + (size_t)f * nc_max * 4;
-            for (int s = 0; s < nc; s++) {
-                const double dx = (double)hb[4 * s + 1] - hb[4 * s], dy = (double)hb[4 * s + 3] - hb[4 * s + 2];
-                cv[s] = { hr[s], s, dx * dy, 0.0, dx * dy == 0.0 };
+            for (int k = 0; k < nc; k++) {
+                const double dx = (double)hb[4 * k + 1] - hb[4 * k], dy = (double)hb[4 * k + 3] - hb[4 * k + 2];
+                const size_t c = first[f] + k;
+                root[c] = hr[k]; ub[c] = dx * dy; known[c] = dx * dy == 0.0;
             }
         }
+        lap("tables d2h");
+        return CK_OK;
     }
 
-    lap("tables d2h");
-    // ---- exact areas for the components that can still reach the top three -------------------
-    const int gcap = (int)(npx < (1u << 22) ? npx : (1u << 22));     // points per gather round
-    CK_TRY(ck_ensure(ctx, ctx->pts, (size_t)gcap * 12 + 64));
-    int32_t* d_pts = (int32_t*)ctx->pts.p;
-    int32_t* d_counter = d_pts + (size_t)gcap * 3;
-    std::vector<uint8_t> want((size_t)n * std::max(nc_max, 1));
-    auto third_best = [](const std::vector<Comp>& cv) {
-        double b[3] = { -1, -1, -1 };
-        for (const Comp& c : cv) if (c.known) {
-            double a = c.area;
-            for (int i = 0; i < 3; i++) if (a > b[i]) std::swap(a, b[i]);
-        }
-        return b[2];          // -1 while fewer than three areas are known
-    };
-    for (int round = 0; round < 3 && nc_max > 0; round++) {
-        bool any = false;
-        std::fill(want.begin(), want.end(), 0);
-        for (int f = 0; f < n; f++) {
-            auto& cv = comps[f];
-            if (cv.empty()) continue;
-            uint8_t* wf = want.data() + (size_t)f * nc_max;
-            if (round == 0) {
-                std::vector<int> idx;
-                for (int s = 0; s < (int)cv.size(); s++) if (!cv[s].known) idx.push_back(s);
-                const int k = std::min<int>(16, (int)idx.size());
-                std::partial_sort(idx.begin(), idx.begin() + k, idx.end(), [&](int a, int b) { return cv[a].ub > cv[b].ub; });
-                for (int i = 0; i < k; i++) { wf[idx[i]] = 1; any = true; }
-            } else {
-                const double third = third_best(cv);
-                for (auto& c : cv)
-                    if (!c.known && c.ub * (1.0 + 1e-5) >= third) { wf[c.slot] = 1; any = true; }
-            }
-        }
-        if (!any) break;
-        if (round == 2) return ck_fail(ctx, CK_ERR_STATE, "contour selection did not converge");
+    // F: the hull candidates of the wanted components into d_pts (gcap points: x | y << 16, slot; then the frames), their
+    // number into npts
+    int gather(const std::vector<uint8_t>& want, int gcap, int32_t* d_pts, int32_t* d_counter, int& npts)
+    {
+        const dim3 lblock(256);
+        // (run-table form: the cleared-frame bytes were not written; the hull-candidate test reads the edge image as it came in)
+        const bool raw_edges = run_table;
+        const uint8_t* e_img = raw_edges ? d_edges : (const uint8_t*)s.ez;
         {
             TimeScope ts(ctx, "contour_gather");
             CK_HIP(ctx, hipMemcpyAsync(d_want, want.data(), (size_t)n * nc_max, hipMemcpyHostToDevice, ctx->stream));
-            // one segment per frame + compaction; a frame with more points than its segment holds (never seen: a
-            // segment is gcap / n >= 32 768 points at 1080p) sends the round through the single-counter kernel instead
+            // one segment per frame + compaction; a frame with more points than its segment holds (a segment is
+            // gcap / n >= 32 768 points at 1080p) sends the round through the single-counter kernel instead
             const int segcap = gcap / n;
             CK_TRY(ck_ensure(ctx, ctx->accum, (size_t)n * segcap * 8 + (size_t)n * 4 + 64));
             int32_t* d_seg = (int32_t*)ctx->accum.p;
             int32_t* d_fcnt = d_seg + (size_t)n * segcap * 2;
             CK_HIP(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)n * 4, ctx->stream));
             CK_HIP(ctx, hipMemsetAsync(d_counter, 0, 8, ctx->stream));
-            // (run-table form: the cleared-frame bytes were not written; the hull-candidate test reads the edge image as it came in)
-            const bool raw_edges = run_table;
-            const uint8_t* e_img = raw_edges ? d_edges : (const uint8_t*)ez;
-            hipLaunchKernelGGL(gather_segments_kernel, lgrid, lblock, 0, ctx->stream, e_img, h, w,
-                               (const int32_t*)L, (const int32_t*)compid, maxc, (const uint8_t*)d_want, nc_max,
-                               (const FrameTab*)d_tab, (const int32_t*)blist, d_fcnt, segcap, d_seg, (int)raw_edges);
+            hipLaunchKernelGGL(gather_segments_kernel, s.lgrid, lblock, 0, ctx->stream, e_img, h, w,
+                               (const int32_t*)s.L, (const int32_t*)s.compid, s.maxc, (const uint8_t*)d_want, nc_max,
+                               (const FrameTab*)s.d_tab, (const int32_t*)s.blist, d_fcnt, segcap, d_seg, (int)raw_edges);
             hipLaunchKernelGGL(compact_points_kernel, dim3(n), dim3(256), 0, ctx->stream, (const int32_t*)d_fcnt, n, segcap,
                                (const int32_t*)d_seg, gcap, d_pts, d_counter);
             CK_HIP(ctx, hipGetLastError());
         }
-        int npts = 0;
-        {
-            int two[2] = {0, 0};
-            CK_HIP(ctx, hipMemcpyAsync(two, d_counter, 8, hipMemcpyDeviceToHost, ctx->stream));
+        int two[2] = {0, 0};
+        CK_HIP(ctx, hipMemcpyAsync(two, d_counter, 8, hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        npts = two[0];
+        if (two[1]) {                                   // a segment overflowed: the whole round again, one counter for all
+            TimeScope ts(ctx, "contour_gather");
+            CK_HIP(ctx, hipMemsetAsync(d_counter, 0, 4, ctx->stream));
+            hipLaunchKernelGGL(gather_points_kernel, s.lgrid, lblock, 0, ctx->stream, e_img, h, w,
+                               (const int32_t*)s.L, (const int32_t*)s.compid, s.maxc, (const uint8_t*)d_want, nc_max,
+                               (const FrameTab*)s.d_tab, (const int32_t*)s.blist, d_counter, gcap, d_pts, (int)raw_edges);
+            CK_HIP(ctx, hipGetLastError());
+            CK_HIP(ctx, hipMemcpyAsync(&npts, d_counter, 4, hipMemcpyDeviceToHost, ctx->stream));
             CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            npts = two[0];
-            if (two[1]) {                                   // a segment overflowed: the whole round again, one counter for all
-                TimeScope ts(ctx, "contour_gather");
-                CK_HIP(ctx, hipMemsetAsync(d_counter, 0, 4, ctx->stream));
-                const bool raw_edges = run_table;
-                hipLaunchKernelGGL(gather_points_kernel, lgrid, lblock, 0, ctx->stream, raw_edges ? d_edges : (const uint8_t*)ez, h, w,
-                                   (const int32_t*)L, (const int32_t*)compid, maxc, (const uint8_t*)d_want, nc_max,
-                                   (const FrameTab*)d_tab, (const int32_t*)blist, d_counter, gcap, d_pts, 0, (int)raw_edges);
-                CK_HIP(ctx, hipGetLastError());
-                CK_HIP(ctx, hipMemcpyAsync(&npts, d_counter, 4, hipMemcpyDeviceToHost, ctx->stream));
-                CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            }
         }
         if (npts > gcap) return ck_fail(ctx, CK_ERR_CAPACITY, "too many contour points (%d > %d)", npts, gcap);
-        std::vector<int32_t> hp((size_t)npts * 2), hf((size_t)npts);
-        if (npts) {
-            CK_HIP(ctx, hipMemcpyAsync(hp.data(), d_pts, (size_t)npts * 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipMemcpyAsync(hf.data(), d_pts + (size_t)gcap * 2, (size_t)npts * 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        lap("  gather kernel+d2h");
-        // bucket by (frame, slot)
-        std::vector<std::vector<std::vector<int32_t>>> bucket((size_t)n);
-        for (int f = 0; f < n; f++) bucket[f].resize(comps[f].size());
-        for (int i = 0; i < npts; i++) {
-            auto& b = bucket[hf[i]][hp[2 * (size_t)i + 1]];
-            b.push_back(hp[2 * (size_t)i] & 0xFFFF);
-            b.push_back(hp[2 * (size_t)i] >> 16);
-        }
-        lap("  bucket");
-        parallel_for(n, [&](int f) {
-            auto& cv = comps[f];
-            for (size_t s = 0; s < cv.size(); s++) {
-                if (!want[(size_t)f * nc_max + s]) continue;
-                float wh[2];
-                ck_min_area_rect(bucket[f][s].data(), (int)(bucket[f][s].size() / 2), wh);
-                cv[s].area = (double)wh[0] * (double)wh[1];
-                cv[s].known = true;
-            }
-        });
-        lap("  hull+calipers");
+        return CK_OK;
     }
 
-    lap("gather+calipers");
-    // ---- selection: bisect.insort order = (area ascending, discovery order descending) ------
-    std::vector<int32_t> sel((size_t)n * 4, -1);
-    bool any_go = false;
-    for (int f = 0; f < n; f++) {
-        auto& cv = comps[f];
-        sel[(size_t)f * 4 + 3] = 0;
-        if (cv.empty()) continue;
-        std::vector<const Comp*> known;
-        for (const Comp& c : cv) if (c.known) known.push_back(&c);
-        std::sort(known.begin(), known.end(), [](const Comp* a, const Comp* b) {
-            if (a->area != b->area) return a->area > b->area;
-            return a->root < b->root;                    // raster-earlier contour ranks higher
-        });
-        res[f].biggest_area = known[0]->area;
-        const double frame_area = (double)h * (double)w;
-        if (!(frame_area / 3 < known[0]->area)) { res[f].status = CK_BOARD_TOO_SMALL; continue; }
-        for (int i = 0; i < 3 && i < (int)known.size(); i++) sel[(size_t)f * 4 + i] = known[i]->slot;
-        sel[(size_t)f * 4 + 3] = 1;
-        any_go = true;
-    }
-    if (d_ghost_out) CK_HIP(ctx, hipMemsetAsync(d_ghost_out, 0, npx, ctx->stream));
-    if (!any_go) return CK_OK;
-
-    // ---- ghost, Hough --------------------------------------------------------------------------
-    std::vector<float> trig(2 * NUMANGLE);
+    // K4: exact areas for the components that can still reach the top three.  The three biggest contours need float rotating
+    // calipers (ck_min_area_rect); ck_board_round_want says which components each round measures.
+    int areas()
     {
-        const float theta = (float)(3.1415926535897932384626433832795 / 180);
-        float ang = 0.f;
-        for (int k = 0; k < NUMANGLE; ang += theta, k++) {
-            trig[NUMANGLE + k] = (float)(sin((double)ang) * 1.f);
-            trig[k] = (float)(cos((double)ang) * 1.f);
+        const int gcap = (int)(s.npx < (1u << 22) ? s.npx : (1u << 22));     // points per gather round
+        CK_TRY(ck_ensure(ctx, ctx->pts, (size_t)gcap * 12 + 64));
+        int32_t* d_pts = (int32_t*)ctx->pts.p;
+        int32_t* d_counter = d_pts + (size_t)gcap * 3;
+        std::vector<uint8_t> want((size_t)n * std::max(nc_max, 1));
+        for (int round = 0; round < 3 && nc_max > 0; round++) {
+            bool any = false;
+            std::fill(want.begin(), want.end(), 0);
+            for (int f = 0; f < n; f++) {
+                const size_t c = first[f];
+                const int nc = (int)(first[f + 1] - c);
+                if (ck_board_round_want(round, nc, ub.data() + c, area.data() + c, known.data() + c, want.data() + (size_t)f * nc_max)) any = true;
+            }
+            if (!any) break;
+            if (round == 2) return ck_fail(ctx, CK_ERR_STATE, "contour selection did not converge");
+            int npts = 0;
+            CK_TRY(gather(want, gcap, d_pts, d_counter, npts));
+            std::vector<int32_t> hp((size_t)npts * 2), hf((size_t)npts);
+            if (npts) {
+                CK_HIP(ctx, hipMemcpyAsync(hp.data(), d_pts, (size_t)npts * 8, hipMemcpyDeviceToHost, ctx->stream));
+                CK_HIP(ctx, hipMemcpyAsync(hf.data(), d_pts + (size_t)gcap * 2, (size_t)npts * 4, hipMemcpyDeviceToHost, ctx->stream));
+                CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            lap("  gather kernel+d2h");
+            // bucket by (frame, slot)
+            std::vector<std::vector<int32_t>> bucket(root.size());
+            for (int i = 0; i < npts; i++) {
+                auto& b = bucket[first[hf[i]] + hp[2 * (size_t)i + 1]];
+                b.push_back(hp[2 * (size_t)i] & 0xFFFF);
+                b.push_back(hp[2 * (size_t)i] >> 16);
+            }
+            lap("  bucket");
+            ck_parallel_for(n, 16, [&](int f) {
+                for (size_t c = first[f]; c < first[f + 1]; c++) {
+                    if (!want[(size_t)f * nc_max + (c - first[f])]) continue;
+                    float wh[2];
+                    ck_min_area_rect(bucket[c].data(), (int)(bucket[c].size() / 2), wh);
+                    area[c] = (double)wh[0] * (double)wh[1];
+                    known[c] = true;
+                }
+            });
+            lap("  hull+calipers");
         }
+        lap("gather+calipers");
+        return CK_OK;
     }
-    const size_t row_bytes = (size_t)((stride + 1) / 2) * 4;               // 16-bit counters, two per dword
-    int rb = (int)((144 * 1024) / row_bytes) - 2;                          // inner rows per workgroup (+ 2 halo rows)
-    if (rb > 10) rb = 10;
-    if (rb < 1) return ck_fail(ctx, CK_ERR_ARG, "image too large for the Hough LDS slab");
-    int threads = HOUGH_THREADS;
-    // A call of a few frames (the hold-off-aware fold's windows, a live finder's single frame) is a latency matter, and
-    // next to the classifier -- two workgroups of 79 KB on every CU -- a workgroup that wants a whole CU's LDS waits until
-    // that kernel's grid drains: 1.5 ms of a 16-frame call's 3.0 (tools/board_call_latency.py).  Small batches take
-    // slabs that fit the hole ONE retiring classifier workgroup leaves (<= 72 KB, 512 threads): same peaks (rows with
-    // their halo, sorted on the host), more workgroups re-reading the point list.
-    if (n <= HOUGH_SMALL_N) {
-        const int rs = (int)((72 * 1024) / row_bytes) - 2;
-        if (rs >= 1) { rb = rs < rb ? rs : rb; threads = HOUGH_THREADS < 512 ? HOUGH_THREADS : 512; }
+
+    // K4: the three biggest contours of every frame and the area gate (ck_board_rank) -> sel; true when some frame goes on
+    bool select(ck_board_result* res, std::vector<int32_t>& sel)
+    {
+        sel.assign((size_t)n * 4, -1);
+        bool any_go = false;
+        for (int f = 0; f < n; f++) {
+            const size_t c = first[f];
+            if (ck_board_rank((int)(first[f + 1] - c), root.data() + c, area.data() + c, known.data() + c, h, w,
+                              sel.data() + (size_t)f * 4, &res[f]))
+                any_go = true;
+        }
+        return any_go;
     }
-    // the ghost's point list holds pc points per frame; ghost_list_kernel counts every point, also past pc
-    auto launch_ghost_hough = [&](int pc) -> int {
+
+    // one pass of G and H + I.  The ghost's point list holds pc points per frame; ghost_list_kernel counts every point, also
+    // past pc.  The counters come down.
+    int ghost_hough_pass(int pc, int rb, int threads, size_t row_bytes, int hough_thresh, uint8_t* d_ghost_out)
+    {
+        const int numrho = 2 * (w + h) + 1;
         CK_TRY(ck_ensure(ctx, ctx->peaks, (size_t)n * PEAK_CAP * 8 + (size_t)n * pc * 4));
         int32_t* d_peaks = (int32_t*)ctx->peaks.p;
         uint32_t* d_hpts = (uint32_t*)(d_peaks + (size_t)n * PEAK_CAP * 2);
         {
             TimeScope ts(ctx, "ghost");
-            hipLaunchKernelGGL(ghost_list_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, (const int32_t*)compid,
-                               (const int32_t*)d_sel, d_tab, (const int32_t*)blist, pc, d_hpts, d_ghost_out);
+            hipLaunchKernelGGL(ghost_list_kernel, s.lgrid, dim3(256), 0, ctx->stream, h, w, (const int32_t*)s.L, (const int32_t*)s.compid,
+                               (const int32_t*)d_sel, s.d_tab, (const int32_t*)s.blist, pc, d_hpts, d_ghost_out);
             CK_HIP(ctx, hipGetLastError());
         }
         {
@@ -1442,70 +1315,96 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
             CK_HIP(ctx, hipFuncSetAttribute((const void*)hough_vote_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)(144 * 1024)));
             hipLaunchKernelGGL(hough_vote_peaks_kernel, dim3((NUMANGLE + rb - 1) / rb, n), dim3(threads), (rb + 2) * row_bytes, ctx->stream,
-                               (const uint32_t*)d_hpts, d_tab, pc, (const float*)d_trig, numrho, rb, hough_thresh, d_peaks);
+                               (const uint32_t*)d_hpts, s.d_tab, pc, (const float*)d_trig, numrho, rb, hough_thresh, d_peaks);
             CK_HIP(ctx, hipGetLastError());
         }
-        CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CK_OK;
-    };
-    CK_HIP(ctx, hipMemcpyAsync(d_sel, sel.data(), sel_bytes, hipMemcpyHostToDevice, ctx->stream));
-    CK_HIP(ctx, hipMemcpyAsync(d_trig, trig.data(), trig.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    CK_TRY(launch_ghost_hough(pcap));
-    lap("ghost+hough");
-    // A ghost with more points than the list holds (a comb of 1-px teeth is all outer border): the whole call again with
-    // the list sized by the largest count, as the labelling falls back to its dense form.  overflow also marks more than
-    // PEAK_CAP peaks; only n_hough_pts > pcap tells the point list's overflow apart.
-    int pts_max = 0;
-    for (int f = 0; f < n; f++) pts_max = std::max(pts_max, tab[f].n_hough_pts);
-    if (pts_max > pcap) {
-        for (int f = 0; f < n; f++) tab[f].n_hough_pts = tab[f].n_peaks = tab[f].overflow = 0;
-        CK_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-        CK_TRY(launch_ghost_hough(pts_max));
-        lap("ghost+hough again");
+        return fetch_tab();
     }
-    int np_max = 0;
-    for (int f = 0; f < n; f++) {
-        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: more than %d Hough peaks", f, PEAK_CAP);
-        if (res[f].status == CK_BOARD_LINES) np_max = std::max(np_max, tab[f].n_peaks);
-    }
-    if (!np_max) return CK_OK;
-    std::vector<int32_t> pk((size_t)n * np_max * 2);
+
+    // K5 + K6: ghost and Hough votes of the selected contours, the slab sized by ck_hough_slab
+    int ghost_hough(const std::vector<int32_t>& sel, int hough_thresh, uint8_t* d_ghost_out)
     {
+        const size_t fpx = s.fpx;
+        const int pcap = (int)(fpx < (1u << 16) ? fpx : (fpx / 8 > (1u << 16) ? fpx / 8 : (1u << 16)));
+        std::vector<float> trig(2 * NUMANGLE);
+        {
+            const float theta = (float)(3.1415926535897932384626433832795 / 180);
+            float ang = 0.f;
+            for (int k = 0; k < NUMANGLE; ang += theta, k++) {
+                trig[NUMANGLE + k] = (float)(sin((double)ang) * 1.f);
+                trig[k] = (float)(cos((double)ang) * 1.f);
+            }
+        }
+        size_t row_bytes;
+        int rb, threads;
+        if (ck_hough_slab(n, h, w, HOUGH_SMALL_N, HOUGH_THREADS, &row_bytes, &rb, &threads))
+            return ck_fail(ctx, CK_ERR_ARG, "image too large for the Hough LDS slab");
+        CK_HIP(ctx, hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        CK_HIP(ctx, hipMemcpyAsync(d_trig, trig.data(), trig.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        CK_TRY(ghost_hough_pass(pcap, rb, threads, row_bytes, hough_thresh, d_ghost_out));
+        lap("ghost+hough");
+        // A ghost with more points than the list holds (a comb of 1-px teeth is all outer border): the whole pass again with
+        // the list sized by the largest count, as the labelling falls back to its dense form.  overflow also marks more than
+        // PEAK_CAP peaks; only n_hough_pts > pcap tells the point list's overflow apart.
+        int pts_max = 0;
+        for (int f = 0; f < n; f++) pts_max = std::max(pts_max, tab[f].n_hough_pts);
+        if (pts_max > pcap) {
+            for (int f = 0; f < n; f++) tab[f].n_hough_pts = tab[f].n_peaks = tab[f].overflow = 0;
+            CK_HIP(ctx, hipMemcpyAsync(s.d_tab, tab.data(), s.tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+            CK_TRY(ghost_hough_pass(pts_max, rb, threads, row_bytes, hough_thresh, d_ghost_out));
+            lap("ghost+hough again");
+        }
+        return CK_OK;
+    }
+
+    // K6: the peaks come down (one packed copy) and become lines (ck_peaks_to_lines)
+    int peaks(ck_board_result* res, float* lines, int cap)
+    {
+        int np_max = 0;
+        for (int f = 0; f < n; f++) {
+            if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "frame %d: more than %d Hough peaks", f, PEAK_CAP);
+            if (res[f].status == CK_BOARD_LINES) np_max = std::max(np_max, tab[f].n_peaks);
+        }
+        if (!np_max) return CK_OK;
+        std::vector<int32_t> pk((size_t)n * np_max * 2);
         const size_t cnt = (size_t)n * np_max;
         CK_TRY(ck_ensure(ctx, ctx->pts, cnt * 8 + 64));
         hipLaunchKernelGGL(pack_peaks_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
                            (const int32_t*)ctx->peaks.p, np_max, n, (int32_t*)ctx->pts.p);
         CK_HIP(ctx, hipMemcpyAsync(pk.data(), ctx->pts.p, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const float theta = (float)(3.1415926535897932384626433832795 / 180);
-    const double scale = 1. / (numrho + 2);
-    std::vector<int> order;
-    for (int f = 0; f < n; f++) {
-        if (res[f].status != CK_BOARD_LINES) continue;
-        const int np = tab[f].n_peaks;
-        res[f].n_lines = np;
-        if (!np) continue;
-        const int32_t* pf = pk.data() + (size_t)f * np_max * 2;
-        order.resize((size_t)np);
-        for (int i = 0; i < np; i++) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) {
-            if (pf[2 * a + 1] != pf[2 * b + 1]) return pf[2 * a + 1] > pf[2 * b + 1];
-            return pf[2 * a] < pf[2 * b];
-        });
-        for (int i = 0; i < np && i < cap; i++) {
-            const int idx = pf[2 * order[i]];
-            const int nn = (int)floor(idx * scale) - 1;
-            const int rr = idx - (nn + 1) * (numrho + 2) - 1;
-            lines[((size_t)f * cap + i) * 2] = (rr - (numrho - 1) * 0.5f) * 1.f;
-            lines[((size_t)f * cap + i) * 2 + 1] = 0.f + nn * theta;
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int f = 0; f < n; f++) {
+            if (res[f].status != CK_BOARD_LINES) continue;
+            res[f].n_lines = tab[f].n_peaks;
+            ck_peaks_to_lines(pk.data() + (size_t)f * np_max * 2, tab[f].n_peaks, 2 * (w + h) + 1, cap, lines + (size_t)f * cap * 2);
         }
+        lap("peaks d2h+sort");
+        return CK_OK;
     }
-    lap("peaks d2h+sort");
-    return CK_OK;
-}
+};
 
+}  // namespace
+
+int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,
+                  float* lines, int cap, ck_board_result* res, uint8_t* d_ghost_out, const int* d_canny_border_flag)
+{
+    Board B{ctx, d_edges, n, h, w, HostLap{ctx, "board_lines"}};
+    if (w > 65535 || h > 65535) return ck_fail(ctx, CK_ERR_ARG, "image side > 65535");
+    const size_t sel_bytes = sizeof(int32_t) * 4 * (size_t)n;
+    CK_TRY(label_scratch(ctx, n, h, w, sel_bytes + 4 * NUMANGLE * 2, 1, B.s));
+    B.d_sel = (int32_t*)((char*)ctx->misc.p + B.s.tab_bytes);
+    B.d_trig = (float*)((char*)ctx->misc.p + B.s.tab_bytes + sel_bytes);
+    B.d_want = (uint8_t*)(B.s.d_aabb + (size_t)n * B.s.maxc * 4);
+    CK_TRY(B.label(d_canny_border_flag));
+    CK_TRY(B.tables(res));
+    CK_TRY(B.areas());
+    std::vector<int32_t> sel;
+    const bool any_go = B.select(res, sel);
+    if (d_ghost_out) CK_HIP(ctx, hipMemsetAsync(d_ghost_out, 0, B.s.npx, ctx->stream));
+    if (!any_go) return CK_OK;
+    CK_TRY(B.ghost_hough(sel, hough_thresh, d_ghost_out));
+    return B.peaks(res, lines, cap);
+}
 
 // ---- external contours of a batch of (small) edge maps, handed to the host -------------------------------------
 // The survey SfContours.find_stones needs of each edge map (stone/sf_contours.py:78-83, 264-270): every RETR_EXTERNAL
@@ -1514,53 +1413,23 @@ int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int 
 // first.  Same labelling kernels as the board path above; the follower (F2) only counts.
 int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, std::vector<std::vector<CkContour>>& out)
 {
-    const size_t fpx = (size_t)h * w, npx = fpx * n;
-    int maxc = (int)(fpx / 4 + 1);
-    if (maxc > MAXC_LIMIT) maxc = MAXC_LIMIT;
     if (w > 65535 || h > 65535) return ck_fail(ctx, CK_ERR_ARG, "image side > 65535");
     if (h < 3 || w < 3) return ck_fail(ctx, CK_ERR_ARG, "edge map smaller than 3x3");
-    CK_TRY(ck_ensure(ctx, ctx->ghost, npx));
-    CK_TRY(ck_ensure(ctx, ctx->labels, npx * 4));
-    CK_TRY(ck_ensure(ctx, ctx->labels2, npx * 4));
-    CK_TRY(ck_ensure(ctx, ctx->lists, npx * 8));
-    const size_t tab_bytes = sizeof(FrameTab) * (size_t)n;
-    CK_TRY(ck_ensure(ctx, ctx->misc, tab_bytes + 64));
-    CK_TRY(ck_ensure(ctx, ctx->comp, (size_t)n * maxc * (4 + 16 + 1 + 4)));
-    uint8_t* ez = (uint8_t*)ctx->ghost.p;
-    int32_t* L = (int32_t*)ctx->labels.p;
-    int32_t* compid = (int32_t*)ctx->labels2.p;
-    int32_t* elist = (int32_t*)ctx->lists.p;
-    int32_t* blist = elist + npx;
-    FrameTab* d_tab = (FrameTab*)ctx->misc.p;
-    int32_t* d_roots = (int32_t*)ctx->comp.p;
-    int32_t* d_aabb = d_roots + (size_t)n * maxc;
-    int32_t* d_nvert = d_aabb + (size_t)n * maxc * 4;
-    const dim3 lgrid = list_grid(LIST_BLOCKS, n), lblock(256);
+    LabelScratch s;
+    CK_TRY(label_scratch(ctx, n, h, w, 0, 1 + 4, s));
+    int32_t* d_nvert = s.d_aabb + (size_t)n * s.maxc * 4;      // behind the tables in comp
+    const dim3 lblock(256);
     {
         TimeScope ts(ctx, "survey_ccl");
-        CK_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_bytes, ctx->stream));
-        const bool dwords = (w & 3) == 0 && ((uintptr_t)d_edges & 3) == 0;
-        if (dwords)
-            hipLaunchKernelGGL(prep_rows4_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, ez, L, d_tab, elist);
-        else
-            hipLaunchKernelGGL(prep_rows_kernel, dim3((h + 3) / 4, n), dim3(256), 0, ctx->stream, d_edges, h, w, ez, L, d_tab, elist);
-        hipLaunchKernelGGL(link_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, L,
-                           (const FrameTab*)d_tab, (const int32_t*)elist, (const int*)nullptr);
-        hipLaunchKernelGGL(flatten_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, L,
-                           (const FrameTab*)d_tab, (const int32_t*)elist, (const int*)nullptr);
-        hipLaunchKernelGGL(roots_list_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, compid, d_tab, maxc,
-                           d_roots, d_aabb, (const int32_t*)elist);
-        hipLaunchKernelGGL(border_list_kernel, lgrid, lblock, 0, ctx->stream, (const uint8_t*)ez, h, w, (const int32_t*)L,
-                           (const int32_t*)compid, maxc, d_tab, d_aabb, (const int32_t*)elist, blist);
-        CK_HIP(ctx, hipGetLastError());
+        CK_TRY(label_dense(ctx, d_edges, n, h, w, s));
     }
     std::vector<FrameTab> tab((size_t)n);
-    CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CK_HIP(ctx, hipMemcpyAsync(tab.data(), s.d_tab, s.tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
     CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     int nc_max = 0;
     size_t nb_total = 0;
     for (int f = 0; f < n; f++) {
-        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "edge map %d: more than %d external contours", f, maxc);
+        if (tab[f].overflow) return ck_fail(ctx, CK_ERR_CAPACITY, "edge map %d: more than %d external contours", f, s.maxc);
         nc_max = std::max(nc_max, tab[f].n_roots);
         nb_total += (size_t)tab[f].n_border;
     }
@@ -1570,11 +1439,11 @@ int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, s
         TimeScope ts(ctx, "survey_trace");
         const size_t bit_bytes = (size_t)h * ((w + 31) / 32) * 4 + 4;
         if (bit_bytes <= 64 * 1024)                            // goban-sized maps: follow the borders in LDS
-            hipLaunchKernelGGL(trace_count_lds_kernel, dim3(n), dim3(256), bit_bytes, ctx->stream, (const uint8_t*)ez, h, w, d_tab,
-                               (const int32_t*)d_roots, maxc, d_nvert);
+            hipLaunchKernelGGL(trace_count_lds_kernel, dim3(n), dim3(256), bit_bytes, ctx->stream, (const uint8_t*)s.ez, h, w, s.d_tab,
+                               (const int32_t*)s.d_roots, s.maxc, d_nvert);
         else
-            hipLaunchKernelGGL(trace_count_kernel, dim3((nc_max + 63) / 64, n), dim3(64), 0, ctx->stream, (const uint8_t*)ez, h, w, d_tab,
-                               (const int32_t*)d_roots, maxc, d_nvert);
+            hipLaunchKernelGGL(trace_count_kernel, dim3((nc_max + 63) / 64, n), dim3(64), 0, ctx->stream, (const uint8_t*)s.ez, h, w, s.d_tab,
+                               (const int32_t*)s.d_roots, s.maxc, d_nvert);
         CK_HIP(ctx, hipGetLastError());
     }
     // roots and vertex counts (strided tables -> dense), then every outer-border pixel with its contour slot: the border
@@ -1582,9 +1451,9 @@ int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, s
     // as contiguous segments it can bucket in parallel
     const size_t cnt = (size_t)n * nc_max;
     std::vector<int32_t> hroots(cnt), hnvert(cnt);
-    CK_HIP(ctx, hipMemcpy2DAsync(hroots.data(), (size_t)nc_max * 4, d_roots, (size_t)maxc * 4, (size_t)nc_max * 4, (size_t)n,
+    CK_HIP(ctx, hipMemcpy2DAsync(hroots.data(), (size_t)nc_max * 4, s.d_roots, (size_t)s.maxc * 4, (size_t)nc_max * 4, (size_t)n,
                                  hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipMemcpy2DAsync(hnvert.data(), (size_t)nc_max * 4, d_nvert, (size_t)maxc * 4, (size_t)nc_max * 4, (size_t)n,
+    CK_HIP(ctx, hipMemcpy2DAsync(hnvert.data(), (size_t)nc_max * 4, d_nvert, (size_t)s.maxc * 4, (size_t)nc_max * 4, (size_t)n,
                                  hipMemcpyDeviceToHost, ctx->stream));
     std::vector<int32_t> base((size_t)n + 1, 0);
     for (int f = 0; f < n; f++) base[f + 1] = base[f] + tab[f].n_border;
@@ -1597,17 +1466,17 @@ int k_contour_survey(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, s
     {
         TimeScope ts(ctx, "survey_gather");
         CK_HIP(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(survey_points_kernel, lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)L, (const int32_t*)compid,
-                           (const FrameTab*)d_tab, (const int32_t*)blist, (const int32_t*)d_base, d_pts);
+        hipLaunchKernelGGL(survey_points_kernel, s.lgrid, lblock, 0, ctx->stream, h, w, (const int32_t*)s.L, (const int32_t*)s.compid,
+                           (const FrameTab*)s.d_tab, (const int32_t*)s.blist, (const int32_t*)d_base, d_pts);
         CK_HIP(ctx, hipGetLastError());
     }
     if (npts) CK_HIP(ctx, hipMemcpyAsync(hp, d_pts, npts * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipMemcpyAsync(tab.data(), d_tab, tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CK_HIP(ctx, hipMemcpyAsync(tab.data(), s.d_tab, s.tab_bytes, hipMemcpyDeviceToHost, ctx->stream));
     CK_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (base is a local: its upload is done too)
     for (int f = 0; f < n; f++)
         if (tab[f].overflow) return ck_fail(ctx, CK_ERR_STATE, "edge map %d: the border follower did not close", f);
     // per map: contours in cv2 order (root descending = reverse discovery), border pixels bucketed by counting
-    parallel_for(n, [&](int f) {
+    ck_parallel_for(n, 16, [&](int f) {
         const int nc = tab[f].n_roots;
         if (!nc) return;
         std::vector<int> order((size_t)nc), pos((size_t)nc), fill((size_t)nc, 0);

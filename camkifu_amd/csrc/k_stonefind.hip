@@ -18,7 +18,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <chrono>
 #include <thread>
 
 #include "ck_common.h"
@@ -165,15 +164,7 @@ int fg_contours(const std::vector<CkContour>& found, const uint8_t* sub_fg, int 
 int k_contour_stones(ck_ctx* ctx, const uint8_t* d_goban, const uint8_t* d_fg, int n, int side, const int32_t* rects,
                      int rs, int re, int cs, int ce, uint8_t* stones, int16_t* zones_out, uint8_t* mask_out)
 {
-    static const bool prof = getenv("CK_PROFILE_HOST") != nullptr;   // debugging aid: host-side lap times on stderr
-    auto t_start = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!prof) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[contour_stones] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_start).count());
-        t_start = now;
-    };
+    HostLap lap{ctx, "contour_stones"};
     const int R = re - rs, C = ce - cs, nz = R * C;
     const int x0 = rects[((size_t)rs * GS + cs) * 4], y0 = rects[((size_t)rs * GS + cs) * 4 + 1];
     const int x1 = rects[((size_t)(re - 1) * GS + ce - 1) * 4 + 2], y1 = rects[((size_t)(re - 1) * GS + ce - 1) * 4 + 3];

@@ -54,6 +54,21 @@ def external_contours(edges):
     return out
 
 
+def hull_candidates(edges):
+    """[h][w] bool: the outer-border pixels without two opposite edge neighbours (8 directions, frame cleared) -- the
+    points k_board_lines gathers for the calipers: a pixel in the middle of a straight run is no hull vertex"""
+    e = np.asarray(edges) != 0
+    e[0, :] = e[-1, :] = e[:, 0] = e[:, -1] = False
+    h, w = e.shape
+    border = np.zeros_like(e)
+    for c in external_contours(edges):
+        border[c["ys"], c["xs"]] = True
+    p = np.pad(e, 1)
+    nb = lambda dy, dx: p[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+    mid = (nb(0, -1) & nb(0, 1)) | (nb(-1, 0) & nb(1, 0)) | (nb(-1, -1) & nb(1, 1)) | (nb(-1, 1) & nb(1, -1))
+    return border & ~mid
+
+
 # ---------------------------------------------------------------- K4 minAreaRect
 def min_area(xs, ys):
     """float64 area of the minimum-area enclosing rectangle of the points"""
@@ -106,6 +121,31 @@ def select(areas_cv):
     for i, a in enumerate(areas_cv):
         bisect.insort(s, _Box(a, i))
     return [b.pos for b in s[-3:]], s[-1].area, [b.area for b in s]
+
+
+def round_wants(rnd, ub, area, known):
+    """which components k_board_lines measures in exact-area round `rnd` -> (must, may, count): it takes `count`
+    components, all of `must` and the rest from `may`.  Round 0: the 16 largest bounding boxes `ub` among the unknown
+    components (boxes equal to the 16th may stand in for each other); later rounds: every unknown component whose box,
+    times 1 + 1e-5, reaches the third best known area (-1 while fewer than three are known)."""
+    unknown = [s for s in range(len(ub)) if not known[s]]
+    if rnd == 0:
+        k = min(16, len(unknown))
+        if k == 0:
+            return set(), set(), 0
+        cut = sorted((ub[s] for s in unknown), reverse=True)[k - 1]
+        return {s for s in unknown if ub[s] > cut}, {s for s in unknown if ub[s] == cut}, k
+    best = sorted((area[s] for s in range(len(ub)) if known[s]), reverse=True)
+    third = best[2] if len(best) >= 3 else -1.0
+    must = {s for s in unknown if ub[s] * (1.0 + 1e-5) >= third}
+    return must, set(), len(must)
+
+
+def peaks(img, thr):
+    """the peaks of hough_accum(img) as (accumulator index, votes) pairs, int32 [k][2], in raster order of the cells"""
+    acc = hough_accum(img)
+    n, r = np.nonzero(peak_mask(acc, thr))
+    return np.stack([(n + 1) * acc.shape[1] + r + 1, acc[n + 1, r + 1]], 1).astype(np.int32).reshape(-1, 2)
 
 
 # ---------------------------------------------------------------- K6 HoughLines
@@ -327,6 +367,17 @@ def comb(h, w, step):
     e = np.zeros((h, w), np.uint8)
     e[2:h - 2, 2:w - 2:step] = 255
     e[2, 2:w - 2] = 255
+    return e
+
+
+def zigzag(h, w):
+    """horizontal zigzag strokes, the pixels (x, y0 + (x & 1)), one every third row, joined by one column at the left
+    into a single component: every stroke pixel is outer border and has no two opposite neighbours"""
+    e = np.zeros((h, w), np.uint8)
+    xs = np.arange(3, w - 3)
+    for y0 in range(3, h - 4, 3):
+        e[y0 + (xs & 1), xs] = 255
+    e[3:h - 3, 2] = 255
     return e
 
 

@@ -121,7 +121,7 @@ def test_hough_vectorised_equals_naive():
 
 
 def test_hough_slab_formula():
-    """(rb, threads) as k_board_lines computes them (k_contours.hip, `launch_ghost_hough` and the lines before it)"""
+    """(rb, threads) as k_board_lines computes them (`ck_hough_slab`, csrc/ck_host_geom.cpp; tests/test_board_select_cpu.py holds that function to this one)"""
     assert R.hough_slab(1, 720, 1280) == (7, 512) and R.hough_slab(32, 720, 1280) == (7, 512)
     assert R.hough_slab(33, 720, 1280) == (10, 1024) and R.hough_slab(1, 768, 1024) == (8, 512)
     assert R.hough_slab(33, 1440, 2560) == (7, 1024) and R.hough_slab(1, 1080, 1920) == (4, 512)

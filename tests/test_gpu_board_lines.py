@@ -10,6 +10,8 @@ exact on axis-aligned outlines (float32 calipers are exact there) and within 1e-
 * Selection on edge maps: equal areas, the gate at exactly h*w/3 and one above, zero-area strokes and single pixels,
   nesting, strokes split by the cleared frame, 17 and 18 diagonal decoys whose bounding boxes beat the winner.
 * Every labelling form, each on a map that yields lines.
+* The single-counter gather: 128 frames of 2^24 pixels in all, one of them a zigzag component with more hull candidates
+  than its segment of the gather buffer holds, in both labelling forms.
 * Capacity: ghosts with more points than the first point list holds (combs, a striped frame through K1+K2), alone and
   in batches; the top-level contour cap min(h*w/4 + 1, 131072) still raises CkError."""
 import numpy as np
@@ -206,6 +208,32 @@ def test_ccl_denser_than_the_run_nodes(ck):
         ck.timing_reset()
         _run(ck, [sparse, dense], refs, 30, "dense fallback")
         assert ck.timing_get("ccl")[1] == 2
+    finally:
+        ck.timing_enable(False)
+
+
+@pytest.mark.parametrize("w, form", [(512, "runs"), (510, "dense")])
+def test_gather_segment_overflow(ck, w, form):
+    """n * h * w >= 2^22 gives every frame a segment of 2^22 // n hull candidates; the zigzag frame has more, so the round
+    is gathered again through one counter for all frames: contour_gather runs twice for the one round there is"""
+    n, h, thr = 128, 256, 100
+    z, sq = R.zigzag(h, w), R.outline(np.zeros((h, w), np.uint8), 10, 10, 30, 40)
+    cz, cs = int(R.hull_candidates(z).sum()), int(R.hull_candidates(sq).sum())
+    print("%s: %d candidates in the zigzag frame, segment %d, %d edge pixels" % (form, cz, 2 ** 22 // n, int((z > 0).sum())))
+    assert n * h * w >= 2 ** 22 and cz > 2 ** 22 // n
+    if form == "runs":
+        assert int((z > 0).sum()) <= 65536                    # the run nodes fit: the call stays in the run-table form
+    assert cz + (n - 1) * cs < 2 ** 22
+    rz, rs = R.board_lines(z, thr), R.board_lines(sq, thr)
+    assert rz["status"] == R.LINES and rz["n_contours"] == 1 and rs["n_contours"] == 1
+    assert int((rz["ghost"] > 0).sum()) < max(h * w // 8, 1 << 16)
+    maps, refs = [sq] * 5 + [z] + [sq] * (n - 6), [rs] * 5 + [rz] + [rs] * (n - 6)
+    ck.timing_enable(True)
+    try:
+        ck.timing_reset()
+        _run(ck, maps, refs, thr, "zigzag, " + form, cap=16384)
+        assert ck.timing_get("contour_gather")[1] == 2
+        assert ck.timing_get("ccl")[1] == 1                   # the form the width selects, no dense redo
     finally:
         ck.timing_enable(False)
 

@@ -9,10 +9,8 @@
 #include <random>
 #include <vector>
 
+#include "../../camkifu_amd/csrc/ck_host_geom.h"
 #include "../../camkifu_amd/csrc/ck_stonegeom.h"
-
-void ck_min_area_rect_box(const int32_t* pts, int n, float* out_wha);
-std::vector<int32_t> ck_hull_points(const int32_t* pts, int n);
 
 int main()
 {

@@ -32,6 +32,7 @@ EXPORTS = [
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
     "ck_train_get_adam_state", "ck_train_handover",
+    "ck_harvest_patches", "ck_augment_patches",
     "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
     "ck_board_detect_records", "ck_cnn_regions_records",
     "ck_contour_stones", "ck_cluster_stones", "ck_rng_get", "ck_rng_set", "ck_contours_external", "ck_find_intersections", "ck_update_grid",
@@ -132,6 +133,9 @@ def lib():
         L.ck_train_grads.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
                                      + [C.c_int, C.c_uint64, C.c_longlong] + [C.c_void_p] * 5)
         L.ck_train_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
+        L.ck_harvest_patches.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+                                         + [C.c_int] * 3 + [C.c_uint32, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
+        L.ck_augment_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.ck_rng_set.argtypes = [C.c_void_p, C.c_uint64]
         L.ck_jpeg_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.ck_jpeg_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
@@ -662,6 +666,71 @@ class Context:
     def train_handover(self, handle):
         """the trainer's current weights become the context's classifier (no host round trip)"""
         self._chk(lib().ck_train_handover(self._h, int(handle)))
+
+    # ---- training data from goban images (csrc/k_harvest.hip) ------------------------------------------------
+    def harvest_patches(self, goban, fgcount, state_of, positions, calm_max=16, empty_keep=256, seed=0, first_frame=0, cap=None):
+        """the labelled regions of n goban images (n, 380, 380, 3), host or device: region q of frame i is kept when
+        state_of[i] >= 0 (an index into positions (n_pos, 19, 19), codes 0 / 1 / 2), the foreground counts fgcount (n, 19, 19)
+        of its four zones sum to <= calm_max and, if its label is 0, the hash of (seed, first_frame + i, q) lets it through
+        (empty_keep of 256).  -> (x (k, 40, 40, 3) uint8, labels (k,) uint8, src (k, 2) int32 = (frame, region)) in ascending
+        (frame, region) order, where goban lies; at most `cap` of them (default: room for all n * 100)"""
+        shp = tuple(int(v) for v in goban.shape)
+        if len(shp) == 3:
+            shp = (1,) + shp
+        if len(shp) != 4 or shp[1:] != (380, 380, 3):
+            raise ValueError("goban images (n, 380, 380, 3) expected, got %r" % (tuple(goban.shape),))
+        n = shp[0]
+        state = np.ascontiguousarray(state_of, np.int32).reshape(-1)
+        pos = np.ascontiguousarray(positions, np.uint8).reshape(-1, 361)
+        if len(state) != n or tuple(fgcount.shape) not in ((n, 19, 19), (n, 361)):
+            raise ValueError("%d frames with %d states and counts %r" % (n, len(state), tuple(fgcount.shape)))
+        cap = n * 100 if cap is None else int(cap)
+        if _is_torch(goban):
+            goban = goban.contiguous()
+        if _is_torch(fgcount):
+            fgcount = fgcount.contiguous()
+        room = max(cap, 0)
+        x, xp, osp = self._out(goban, (room, 40, 40, 3), np.uint8)
+        lab, lp, _ = self._out(goban, (room,), np.uint8)
+        src, sp_, _ = self._out(goban, (room, 2), np.int32)
+        p, sp, keep = self._in(goban)
+        fp, fsp, fkeep = self._in(fgcount, np.int32)
+        found = C.c_int32(0)
+        self._chk(lib().ck_harvest_patches(self._h, p, n, sp, fp, fsp, state.ctypes.data_as(C.c_void_p),
+                                           pos.ctypes.data_as(C.c_void_p), len(pos), int(calm_max), int(empty_keep),
+                                           int(seed) & 0xffffffff, int(first_frame), xp, lp, sp_, cap, osp, C.byref(found)))
+        self.harvest_found = int(found.value)                # the total, also when cap cut the outputs short
+        k = min(self.harvest_found, room)
+        return x[:k], lab[:k], src[:k]
+
+    def augment_patches(self, x, t, to_device=None, out=None):
+        """x (n, 40, 40, 3) uint8, host or device; t: n codes 0..7 -> numpy.rot90(x[k], t[k] & 3), its columns mirrored when
+        t[k] & 4, as a new array where x lies -- or a device tensor on `to_device`, or written into `out`"""
+        shp = tuple(int(v) for v in x.shape)
+        if len(shp) != 4 or shp[1:] != (40, 40, 3):
+            raise ValueError("patches (n, 40, 40, 3) expected, got %r" % (shp,))
+        n = shp[0]
+        if _is_torch(t):
+            t = t.detach().cpu().numpy()
+        t = np.asarray(t).reshape(-1)
+        if len(t) != n:
+            raise ValueError("%d transform codes for %d patches" % (len(t), n))
+        codes = np.ascontiguousarray(np.where((t < 0) | (t > 255), 255, t), np.uint8)       # out of range: the library says so
+        if _is_torch(x):
+            x = x.contiguous()
+        if out is not None:
+            if tuple(out.shape) != shp:
+                raise ValueError("out %r for patches %r" % (tuple(out.shape), shp))
+            assert out.is_contiguous() if _is_torch(out) else (out.dtype == np.uint8 and out.flags.c_contiguous)
+            op, osp, _ = self._in(out)
+            res = out
+        elif to_device is not None:
+            res, op, osp = self._out_on(to_device, shp, np.uint8)
+        else:
+            res, op, osp = self._out(x, shp, np.uint8)
+        p, sp, keep = self._in(x)
+        self._chk(lib().ck_augment_patches(self._h, p, n, sp, codes.ctypes.data_as(C.c_void_p), op, osp))
+        return res
 
     def stones_detect(self, bgr, M):
         n, h, w = self._shape(bgr, 3)

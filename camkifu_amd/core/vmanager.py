@@ -69,6 +69,28 @@ class VManagerBase(Thread):
     def vid_progress(self, percent):
         """progress listeners (a GUI) hook in here"""
 
+    def snapshot(self, save_goban=False):
+        """save the stones finder's canonical goban image as the next free snapshot-N.npy of cvconf.snapshot_dir (lossless;
+        the reference writes a PNG, core/vmanager.py:309-325) and, with save_goban, the game so far as game-N.sgf beside
+        it: what NNManager.gen_data reads.  -> the snapshot's path, None without an image"""
+        import os
+        import re
+        import numpy as np
+        img = getattr(self.stones_finder, "goban_img", None)
+        if img is None:
+            print("No goban image available to save")
+            return None
+        folder = cvconf.snapshot_dir
+        taken = [int(m.group(1)) for m in (re.fullmatch(r"snapshot-(\d+)\.npy", f) for f in os.listdir(folder))
+                 if m and os.path.isfile(os.path.join(folder, m.group(0)))]
+        name = "snapshot-%d.npy" % (max(taken, default=-1) + 1)
+        img = np.asarray(img.cpu() if hasattr(img, "cpu") else img)
+        np.save(os.path.join(folder, name), img[0] if img.ndim == 4 else img)
+        print("Saved %s in %s" % (name, folder))
+        if save_goban:
+            self.controller.kifu.save(os.path.join(folder, name.replace("snapshot", "game").replace(".npy", ".sgf")))
+        return os.path.join(folder, name)
+
     # ---- finders ------------------------------------------------------------------------------
     def finders(self):
         return [p for p in (self.board_finder, self.stones_finder) if p is not None]

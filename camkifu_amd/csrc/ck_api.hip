@@ -1384,4 +1384,97 @@ int ck_train_handover(ck_ctx* ctx, int handle)
     CK_API_END(ctx)
 }
 
+// ---- labelled patches from goban images (k_harvest.hip) ------------------------------------------------------------------
+static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+int ck_harvest_patches(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, const int32_t* fgcount, int fg_space,
+                       const int32_t* state_of, const uint8_t* positions, int n_pos, int calm_max, int empty_keep, uint32_t seed,
+                       long long first_frame, uint8_t* x, uint8_t* labels, int32_t* src, int cap, int out_space, int32_t* n_found)
+{
+    CK_API_BEGIN(ctx)
+    if (!n_found) return ck_fail(ctx, CK_ERR_ARG, "n_found is NULL");
+    *n_found = 0;
+    if (n < 0 || n > (1 << 20)) return ck_fail(ctx, CK_ERR_ARG, "n = %d: 0 .. 2^20 frames per call", n);
+    if (cap < 0) return ck_fail(ctx, CK_ERR_ARG, "cap = %d is negative", cap);
+    if (empty_keep < 0 || empty_keep > 256) return ck_fail(ctx, CK_ERR_ARG, "empty_keep = %d: 0 .. 256", empty_keep);
+    if (n_pos < 0 || (n_pos > 0 && !positions)) return ck_fail(ctx, CK_ERR_ARG, "positions NULL or n_pos < 0");
+    if (n == 0) return CK_OK;
+    if (!goban || !fgcount || !state_of) return ck_fail(ctx, CK_ERR_ARG, "goban, fgcount or state_of is NULL");
+    if (cap > 0 && (!x || !labels || !src)) return ck_fail(ctx, CK_ERR_ARG, "x, labels or src is NULL with cap > 0");
+    if ((in_space != CK_HOST && in_space != CK_DEVICE) || (fg_space != CK_HOST && fg_space != CK_DEVICE))
+        return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d / %d", in_space, fg_space);
+    for (int i = 0; i < n; i++)
+        if (state_of[i] >= n_pos) return ck_fail(ctx, CK_ERR_ARG, "state_of[%d] = %d with %d positions", i, state_of[i], n_pos);
+    for (size_t i = 0; i < (size_t)n_pos * 361; i++)
+        if (positions[i] > 2)
+            return ck_fail(ctx, CK_ERR_ARG, "position %d holds code %d at point %d: 0 empty, 1 black, 2 white", (int)(i / 361),
+                           (int)positions[i], (int)(i % 361));
+    if (in_space == CK_DEVICE && ((uintptr_t)goban & 3) != 0)
+        return ck_fail(ctx, CK_ERR_ARG, "goban images in device memory must be 4-byte aligned");
+    if (out_space != CK_HOST && cap > 0 && (((uintptr_t)x & 7) != 0 || ((uintptr_t)src & 3) != 0))
+        return ck_fail(ctx, CK_ERR_ARG, "x in device memory must be 8-byte aligned, src 4-byte aligned");
+    // one scratch block: state_of | positions | codes of the n * 100 candidates | block totals + the grand total
+    const int nb = ck_harvest_blocks(n);
+    const size_t at_pos = up16((size_t)n * 4), at_code = at_pos + up16((size_t)n_pos * 361 + 1);
+    const size_t at_blocks = at_code + up16((size_t)n * 400), bytes = at_blocks + up16(((size_t)nb + 1) * 4);
+    CK_TRY(ck_ensure(ctx, ctx->harvest, bytes));
+    uint8_t* scratch = (uint8_t*)ctx->harvest.p;
+    CK_HIP(ctx, hipMemcpyAsync(scratch, state_of, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_pos > 0)
+        CK_HIP(ctx, hipMemcpyAsync(scratch + at_pos, positions, (size_t)n_pos * 361, hipMemcpyHostToDevice, ctx->stream));
+    const void *d_goban, *d_fg;
+    CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_goban));
+    CK_TRY(ck_to_device(ctx, fgcount, (size_t)n * 361 * sizeof(int32_t), fg_space, ctx->in_stage2, &d_fg));
+    OutStage<uint8_t> ox, ol;
+    OutStage<int32_t> os;
+    if (cap > 0) {
+        CK_TRY(ox.open(ctx, x, (size_t)cap * 4800, out_space, ctx->out_stage));
+        CK_TRY(ol.open(ctx, labels, (size_t)cap, out_space, ctx->lblbuf));
+        CK_TRY(os.open(ctx, src, (size_t)cap * 2 * sizeof(int32_t), out_space, ctx->harvest_src));
+    }
+    int32_t* d_blocks = (int32_t*)(scratch + at_blocks);
+    CK_TRY(k_harvest(ctx, (const uint8_t*)d_goban, (const int32_t*)d_fg, (const int32_t*)scratch, scratch + at_pos, n, calm_max,
+                     empty_keep, seed, (uint32_t)(unsigned long long)first_frame, (int32_t*)(scratch + at_code), d_blocks,
+                     ox.dev, ol.dev, os.dev, cap));
+    int32_t total = 0;
+    CK_HIP(ctx, hipMemcpyAsync(&total, d_blocks + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CK_TRY(finish(ctx));
+    *n_found = total;
+    // only what was found travels home: the rows beyond min(total, cap) of a host output stay as the caller left them
+    const size_t got = (size_t)(total < cap ? total : cap);
+    if (got > 0 && out_space == CK_HOST) {
+        CK_TRY(ck_from_device(ctx, x, ox.dev, got * 4800, CK_HOST));
+        CK_TRY(ck_from_device(ctx, labels, ol.dev, got, CK_HOST));
+        CK_TRY(ck_from_device(ctx, src, os.dev, got * 2 * sizeof(int32_t), CK_HOST));
+        CK_TRY(finish(ctx));
+    }
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_augment_patches(ck_ctx* ctx, const uint8_t* x, int n, int in_space, const uint8_t* t, uint8_t* x_out, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    if (n < 0 || n > (1 << 24)) return ck_fail(ctx, CK_ERR_ARG, "n = %d: 0 .. 2^24 patches per call", n);
+    if (n == 0) return CK_OK;
+    if (!x || !t || !x_out) return ck_fail(ctx, CK_ERR_ARG, "x, t or x_out is NULL");
+    for (int i = 0; i < n; i++)
+        if (t[i] > 7) return ck_fail(ctx, CK_ERR_ARG, "t[%d] = %d: a transform code is 0 .. 7", i, (int)t[i]);
+    const size_t bytes = (size_t)n * 4800;
+    if ((in_space == CK_HOST) == (out_space == CK_HOST) && x < x_out + bytes && x_out < x + bytes)
+        return ck_fail(ctx, CK_ERR_ARG, "x_out overlaps x: the transform does not work in place");
+    if ((in_space != CK_HOST && ((uintptr_t)x & 3) != 0) || (out_space != CK_HOST && ((uintptr_t)x_out & 3) != 0))
+        return ck_fail(ctx, CK_ERR_ARG, "patches in device memory must be 4-byte aligned");
+    CK_TRY(ck_ensure(ctx, ctx->harvest, (size_t)n));
+    CK_HIP(ctx, hipMemcpyAsync(ctx->harvest.p, t, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    const void* d_x;
+    CK_TRY(ck_to_device(ctx, x, bytes, in_space, ctx->in_stage, &d_x));
+    OutStage<uint8_t> out;
+    CK_TRY(out.open(ctx, x_out, bytes, out_space, ctx->out_stage));
+    CK_TRY(k_augment(ctx, (const uint8_t*)d_x, (const uint8_t*)ctx->harvest.p, n, out.dev));
+    CK_TRY(out.deliver(ctx));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
 }  // extern "C"

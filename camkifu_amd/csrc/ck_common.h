@@ -129,6 +129,8 @@ struct ck_ctx {
     DevBuf mats;
     DevBuf pyr0, pyr1;   // pyramid levels between the first and the last (ping-pong)
     DevBuf rec_stage;    // the device twin of rec_host, for records that live in HBM
+    DevBuf harvest;      // ck_harvest_patches / ck_augment_patches: the small host inputs, the flags' codes, the block totals
+    DevBuf harvest_src;  // staged (frame, region) pairs of a harvest that goes to the host
 
     CnnWeights cnn;
     int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
@@ -243,6 +245,14 @@ int ck_from_device(ck_ctx* ctx, void* dst, const void* dev, size_t bytes, int sp
 
 static inline int ck_pitch(int w) { return (w + 63) & ~63; }
 
+// the 32-bit finaliser of MurmurHash3: the stateless hash under the trainer's dropout masks (k_cnn_train.hip) and the
+// harvest's thinning of empty regions (k_harvest.hip)
+__host__ __device__ inline uint32_t mix32(uint32_t h)
+{
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+
 // ---- kernels (one launcher per stage; all asynchronous on ctx->stream) -----------------
 // d_range (nullable): per (frame, channel, CK_RANGE_TILE^2 tile) two bytes lo, hi with lo <= every median of the tile <= hi
 // (n * 3 * ceil(h / T) * ceil(w / T) * 2 bytes; what k_canny_planar takes to skip its flat tiles)
@@ -317,5 +327,12 @@ int k_zone_counts(ck_ctx* ctx, const uint8_t* d_mask, int n, int side, int32_t* 
 // contiguous region outputs
 int k_records_put_board(ck_ctx* ctx, const uint8_t* d_parts, int n, ck_frame_record* d_rec);
 int k_records_put_regions(ck_ctx* ctx, const uint8_t* d_rlabel, const double* d_rconf, int n, ck_frame_record* d_rec);
+// labelled patches out of goban images and their augmentation (k_harvest.hip); the flag pass runs blocks of 1024 candidates
+#define CK_HARVEST_BLOCK 1024
+static inline int ck_harvest_blocks(int n) { return (int)(((long long)n * 100 + CK_HARVEST_BLOCK - 1) / CK_HARVEST_BLOCK); }
+int k_harvest(ck_ctx* ctx, const uint8_t* d_goban, const int32_t* d_fgcount, const int32_t* d_state, const uint8_t* d_positions, int n,
+              int calm_max, int empty_keep, uint32_t seed, uint32_t first_frame, int32_t* d_code, int32_t* d_blocks,
+              uint8_t* d_x, uint8_t* d_labels, int32_t* d_src, int cap);
+int k_augment(ck_ctx* ctx, const uint8_t* d_x, const uint8_t* d_t, int n, uint8_t* d_out);
 
 #include "ck_host_geom.h"  // host geometry and the host decisions of k_board_lines (ck_host_geom.cpp)

@@ -279,12 +279,6 @@ __global__ void tr_pool_back(const float* a, const float* pooled, const float* d
     dz[i] = (mine == best && pooled[j] > 0.0f) ? dpooled[j] / keep : 0.0f;
 }
 
-__host__ __device__ inline uint32_t mix32(uint32_t h)
-{
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
-
 // Dropout in place: unit e of the layer (e = global patch index * units per patch + unit) is kept when the top 24 bits of
 // mix32(mix32(lo(e) ^ key) + hi(e) * 0x9e3779b1 + key) are >= p * 2^24; key = a mix of (seed, step, layer).  Kept units are
 // divided by 1 - p.  mask (nullable): 1 kept / 0 dropped, at the unit's global index.

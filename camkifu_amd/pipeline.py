@@ -597,10 +597,13 @@ class GpuCore:
     slices of one goban tensor, and a dedicated context runs the model over it batch after batch (world == 1); with
     world > 1 the goban tensor is handed back for the pixel-sharded exchange instead."""
 
-    def __init__(self, lanes, bg_ctx=None, local_model=True, records_device=None):
+    def __init__(self, lanes, bg_ctx=None, local_model=True, records_device=None, keep_gobans=False):
         """records_device: where the shard's record buffer lives -- a torch device (HBM: the records go through RCCL from
-        there) or None (host memory: one rank, or collectives on host buffers)"""
+        there) or None (host memory: one rank, or collectives on host buffers).  keep_gobans: the goban tensor and the
+        foreground counts of the last batch that went through the local model stay reachable (last_gobans, last_fgcount;
+        both None after a batch without a transform) instead of being dropped with the batch"""
         self.records_device = records_device
+        self.keep_gobans, self.last_gobans, self.last_fgcount = bool(keep_gobans), None, None
         # A context belongs to ONE thread (the library refuses a second one: CK_ERR_STATE).  A lane given without a board
         # context, or a core given without a model context, gets one of its own when the stones context is a real
         # capi.Context; with stand-in contexts (tests) the orphan work shares the stones context AND its thread.
@@ -693,6 +696,8 @@ class GpuCore:
         board_f = [pb.submit(board_into, cb, fr, recs[1 + cuts[i]:1 + cuts[i + 1]]) if len(fr) and want_board else None
                    for i, ((pb, _), (cb, _), fr) in enumerate(zip(self.pools, self.lanes, parts))]
         fg, gobans = None, None
+        if self.keep_gobans:
+            self.last_gobans = self.last_fgcount = None
         if mtx is not None:
             on_gpu = hasattr(frames, "is_cuda") and frames.is_cuda
             if on_gpu:
@@ -719,7 +724,10 @@ class GpuCore:
                 if f is not None:
                     f.result()
             if self.local_model:
-                fg, gobans = self._host(fg_f.result()), None
+                fg = self._host(fg_f.result())
+                if self.keep_gobans:
+                    self.last_gobans, self.last_fgcount = gobans, fg
+                gobans = None
         for f in board_f:
             if f is not None:
                 f.result()
@@ -784,7 +792,10 @@ class FastFilePipeline:
 
     def __init__(self, h, w, controller, ctx=None, rank=0, world=1, device=None, compute=None, ctx_board=None,
                  bg_init_frames=50, band_model=None, lanes=None, ctx_bg=None, board_lazy=False, force_exchange=False,
-                 records_in_hbm=None):
+                 records_in_hbm=None, keep_gobans=False):
+        if keep_gobans and (world > 1 or force_exchange or compute is not None):
+            raise ValueError("keep_gobans needs the one-rank pipeline with its own GPU core: the background model runs on the "
+                             "whole goban tensor there; across ranks every rank holds a band of it only")
         self.h, self.w = h, w
         self.rank, self.world = rank, world
         self.group = _Group(rank, world, device)
@@ -806,7 +817,7 @@ class FastFilePipeline:
             self.records_device = device
         if compute is None:
             compute = GpuCore(lanes or [(ctx_board, ctx)], bg_ctx=ctx_bg, local_model=not self.exchange,
-                              records_device=self.records_device)
+                              records_device=self.records_device, keep_gobans=keep_gobans)
         self.compute = compute
         gpu = getattr(compute, "device", None)
         if gpu is None:
@@ -1313,6 +1324,17 @@ class FastFilePipeline:
 
     def process_batch(self, my_frames, n_total):
         return self.finish(self.submit(my_frames, n_total))
+
+    @property
+    def last_gobans(self):
+        """with keep_gobans: the goban images (n, 380, 380, 3) of the last finished batch, where the lanes warped them (HBM
+        for frames in HBM); None when the batch had no transform yet"""
+        return getattr(self.compute, "last_gobans", None)
+
+    @property
+    def last_fgcount(self):
+        """with keep_gobans: the foreground counts (n, 19, 19) int32 of the last finished batch, on the host"""
+        return getattr(self.compute, "last_fgcount", None)
 
     def close(self, wait=True):
         """stop this pipeline's stage threads (and the GPU core's, when it was built here); idempotent.  By default it

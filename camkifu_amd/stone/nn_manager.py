@@ -9,8 +9,11 @@ Tables (gsize 19, 10 x 10 regions of 2 x 2 intersections, the last region pulled
     DIGITS[label]    the four base-3 digits of a label, least significant first = intersections
                      (0,0) (0,1) (1,0) (1,1) of the region         nn_manager.py:236-254
     PATCH_ORIGIN[i]  first pixel of region i's 40-pixel window     0, 40, ..., 320, 340
+    AUG_LABEL[t, l]  the label of a region labelled l after transform t of its window: numpy.rot90 by t & 3 quarter
+                     turns, then the columns mirrored when t & 4 (Context.augment_patches does the same to the pixels)
 """
 import os
+import re
 from threading import RLock
 
 import numpy as np
@@ -28,6 +31,20 @@ CODE = {E: 0, B: 1, W: 2}
 CELL_PX = cvconf.canonical_size // gsize
 PATCH_ORIGIN = REGION_START * CELL_PX
 PATCH_SIDE = STEP * CELL_PX
+
+
+def _aug_label_table():
+    table = np.empty((8, NB_CLASSES), np.uint8)
+    for t in range(8):
+        for label in range(NB_CLASSES):
+            block = np.rot90(DIGITS[label].reshape(STEP, STEP), t & 3)
+            block = block[:, ::-1] if t & 4 else block
+            table[t, label] = int((block.reshape(-1).astype(np.int64) * 3 ** np.arange(STEP * STEP)).sum())
+    return table
+
+
+AUG_LABEL = _aug_label_table()
+SNAPSHOT_SUFFIXES = (".npy", ".jpg", ".jpeg")      # lossless, or a still read through open_capture (the project reads no PNG)
 
 # The trained model file.  The reference downloads the author's keras.h5 into its training directory
 # (stone/nn_manager.py:22, 65-90); that file cannot be fetched here, so the package ships a classifier trained on the
@@ -164,6 +181,74 @@ class NNManager:
                 ys[i * SPLIT + j, NNManager.compute_label(r0, r0 + STEP, c0, c0 + STEP, stones)] = True
         return ys
 
+    # ---- datasets from snapshots (nn_manager.py:133-176) -------------------------------------------------------
+    @staticmethod
+    def _stem(path):
+        for suffix in SNAPSHOT_SUFFIXES:
+            if str(path).lower().endswith(suffix):
+                return str(path)[:-len(suffix)]
+        raise ValueError("a snapshot is a .npy or .jpg file: %s" % (path,))
+
+    @staticmethod
+    def get_ref_game(img_path):
+        """snapshot-N.* -> game-N.sgf beside it; a copy's name 'snapshot-N (2).npy' falls back to the game of snapshot-N"""
+        folder, name = os.path.split(NNManager._stem(img_path))
+        game_path = os.path.join(folder, name.replace("snapshot", "game") + ".sgf")
+        return game_path if os.path.isfile(game_path) else re.sub(r" \(\d*\)", "", game_path)
+
+    @staticmethod
+    def get_ref_y(path):
+        """snapshot-N.* -> snapshot-N-y.npz (labels saved earlier), with the same fall-back"""
+        y_path = NNManager._stem(path) + "-y.npz"
+        return y_path if os.path.isfile(y_path) else re.sub(r" \(\d*\)", "", y_path)
+
+    @staticmethod
+    def load_snapshot(img_path):
+        NNManager._stem(img_path)
+        if str(img_path).lower().endswith(".npy"):
+            return np.load(img_path)
+        from ..core.capture import open_capture
+        ok, img = open_capture(str(img_path)).read()
+        if not ok:
+            raise ValueError("cannot read %s" % (img_path,))
+        return img
+
+    def suggest_stones(self, img, img_path):
+        """the stones of a snapshot (19, 19) of E / B / W: from game-N.sgf beside it (played out under the rules, as the
+        reference's controller does), else from snapshot-N-y.npz, else the classifier's own reading of the image.
+        self.stones_source says which: "sgf", "y" or "guess"."""
+        game_path, y_path = NNManager.get_ref_game(img_path), NNManager.get_ref_y(img_path)
+        if os.path.isfile(game_path):
+            from .harvest import reference_positions
+            self.stones_source = "sgf"
+            return SYMBOLS[reference_positions(game_path, rules=True)[-1]]
+        if os.path.isfile(y_path):
+            stones = np.empty((gsize, gsize), dtype=object)
+            with np.load(y_path) as z:
+                y = np.asarray(z["Y"])
+            for i, r0 in enumerate(REGION_START):
+                for j, c0 in enumerate(REGION_START):
+                    stones[r0:r0 + STEP, c0:c0 + STEP] = NNManager.compute_stones(np.argmax(y[i * SPLIT + j])).reshape(STEP, STEP)
+            self.stones_source = "y"
+            return stones
+        from .nn_cache import NNCache
+        self.stones_source = "guess"
+        return NNCache(self, img, self._context()).predict_all_stones()[:, :, 0]
+
+    def gen_data(self, img_path, validate=None):
+        """(X (100, 40, 40, 3), Y (100, 81)) of a snapshot of the canonical goban image, or (None, None).  validate: the
+        reference's labelling window as a callable (stones, img) -> bool that may edit `stones` in place; without one only
+        stones that come from a game record or from saved labels are accepted -- a guess is not training data."""
+        img = NNManager.load_snapshot(img_path)
+        if tuple(img.shape[:2]) != self.canonical_shape:
+            raise ValueError("canonical image expected, got %r" % (tuple(img.shape),))
+        if validate is None and not (os.path.isfile(NNManager.get_ref_game(img_path)) or os.path.isfile(NNManager.get_ref_y(img_path))):
+            return None, None
+        stones = self.suggest_stones(img, img_path)
+        if validate is not None and not validate(stones, img):
+            return None, None
+        return self.generate_xs(img), self.generate_ys(stones)
+
     # ---- training ------------------------------------------------------------------------------------
     def _context(self):
         if getattr(self, "ctx", None) is None:
@@ -181,14 +266,22 @@ class NNManager:
         """the order in which epoch `epoch` visits the n samples: a function of (seed, epoch) alone"""
         return np.random.default_rng([int(seed), int(epoch)]).permutation(n)
 
+    @staticmethod
+    def augment_codes(idx, seed, epoch, n):
+        """the transform codes 0..7 (AUG_LABEL) of samples idx of a dataset of n in epoch `epoch`: one draw of n codes from
+        the generator seeded [seed, epoch, 1], indexed by idx -- a function of the sample, not of the batch it rides in"""
+        return np.random.default_rng([int(seed), int(epoch), 1]).integers(0, 8, size=int(n), dtype=np.uint8)[np.asarray(idx)]
+
     def train(self, x, y, vdata=None, batch_size=1000, nb_epoch=2, lr=0.001, seed=20161001, dropout=True, checkpoint=None,
-              net=None, verbose=True):
+              net=None, verbose=True, augment=False):
         """Fit the classifier to patches x (N, 40, 40, 3) uint8 with labels y (one-hot (N, 81) or N class indices) on the
         GPU, starting from `net` (default: the current network, see get_net).  Adam, categorical cross-entropy,
         the samples reshuffled per epoch from `seed`.  Prints the loss per epoch (and the loss on vdata = (xv, yv)),
         writes `checkpoint` (.npz) whenever the epoch's mean loss improves -- ModelCheckpoint(monitor='loss',
         save_best_only=True) -- hands the trained weights to the context's classifier and makes them the current
-        network.  -> history dict(loss=[..], val_loss=[..])"""
+        network.  -> history dict(loss=[..], val_loss=[..])
+        augment: every sample is turned / mirrored by its code of the epoch (augment_codes) on the GPU -- the batch goes
+        through Context.augment_patches into HBM and into the training step from there, with labels AUG_LABEL[t, label]."""
         ctx = self._context()
         x, labels = np.ascontiguousarray(x, np.uint8), self._class_index(y)
         start = NNManager.get_net() if net is None else net
@@ -199,7 +292,12 @@ class NNManager:
                 order, total = self.epoch_order(len(x), seed, epoch), 0.0
                 for k in range(0, len(order), int(batch_size)):
                     idx = order[k:k + int(batch_size)]
-                    total += ctx.train_step(handle, x[idx], labels[idx], lr=lr, dropout=dropout, seed=seed) * len(idx)
+                    xb, lb = x[idx], labels[idx]
+                    if augment:
+                        import torch
+                        t = self.augment_codes(idx, seed, epoch, len(x))
+                        xb, lb = ctx.augment_patches(xb, t, to_device=torch.device("cuda", ctx.device)), AUG_LABEL[t, lb]
+                    total += ctx.train_step(handle, xb, lb, lr=lr, dropout=dropout, seed=seed) * len(idx)
                     step += 1
                 history["loss"].append(total / len(x))
                 line = "epoch %d/%d - loss: %.4f" % (epoch + 1, nb_epoch, history["loss"][-1])

@@ -247,6 +247,25 @@ int ck_train_get_adam_state(ck_ctx* ctx, int handle, float* const m[12], float* 
  * and the other inference calls then run on them */
 int ck_train_handover(ck_ctx* ctx, int handle);
 
+/* ---- training data from goban images: NNManager.generate_xs / generate_ys for the regions whose label is certain
+ *      (stone/nn_manager.py:220-254), selected and cut where the images lie.
+ * goban: n x 380 x 380 x 3 in `in_space`; fgcount: n x 361 int32 foreground counts (ck_mog2_band_run / ck_zone_counts) in
+ * `fg_space`; state_of: HOST, n int32 -- the reference position frame i shows, < 0: the frame is not harvested; positions:
+ * HOST, n_pos x 361 codes 0 E / 1 B / 2 W.  Region q = 10 ri + cj of frame i is kept when state_of[i] >= 0, the counts of its
+ * 2 x 2 zones (rows rs(ri).., columns rs(cj).., rs = 0, 2, .., 16, 17) sum to <= calm_max, and -- for a region whose label is
+ * 0 -- hash(seed, first_frame + i, q) & 255 < empty_keep (0: no empty region, 256: all; the hash is stateless, so what is
+ * kept does not depend on how a film is cut into calls).  label = the base-3 number of the block, (0,0) least significant,
+ * then (0,1), (1,0), (1,1).  Outputs in `out_space`, in ascending (frame, region) order: x cap x 40 x 40 x 3 (the window at
+ * pixel (20 rs(ri), 20 rs(cj))), labels cap bytes, src cap x 2 int32 (i, q).  *n_found: the number of kept regions; only
+ * the first min(*n_found, cap) rows of the outputs are written.  CK_ERR_ARG before any launch: a code > 2,
+ * state_of[i] >= n_pos, empty_keep outside 0 .. 256, cap < 0.  n = 0 is fine. */
+int ck_harvest_patches(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, const int32_t* fgcount, int fg_space,
+                       const int32_t* state_of, const uint8_t* positions, int n_pos, int calm_max, int empty_keep, uint32_t seed,
+                       long long first_frame, uint8_t* x, uint8_t* labels, int32_t* src, int cap, int out_space, int32_t* n_found);
+/* x_out[k] = numpy.rot90(x[k], t[k] & 3, axes=(0, 1)), its columns mirrored when t[k] & 4; x: n x 40 x 40 x 3 in `in_space`,
+ * t: HOST, n codes 0 .. 7 (above: CK_ERR_ARG), x_out in `out_space`, which may not overlap x (CK_ERR_ARG). */
+int ck_augment_patches(ck_ctx* ctx, const uint8_t* x, int n, int in_space, const uint8_t* t, uint8_t* x_out, int out_space);
+
 /* ---- K8 + K10..K12: frame + M -> 19x19 labels   stonesfinder.py:140 + nn_cache.py:33-41 */
 int ck_stones_detect(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space,
                      const double* M, int m_count, uint8_t* labels, double* conf,

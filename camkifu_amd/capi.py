@@ -27,7 +27,8 @@ EXPORTS = [
     "ck_ctx_create", "ck_ctx_create_prio", "ck_ctx_destroy", "ck_ctx_destroy2", "ck_stream_wait", "ck_last_error", "ck_backend", "ck_version", "ck_stream",
     "ck_timing_enable", "ck_timing_reset", "ck_timing_get",
     "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
-    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_jpeg_probe", "ck_jpeg_coefficients", "ck_jpeg_reconstruct", "ck_jpeg_decode", "ck_jpeg_bad_frame", "ck_get_perspective_transform", "ck_warp_perspective",
+    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_jpeg_probe", "ck_jpeg_coefficients", "ck_jpeg_reconstruct", "ck_jpeg_decode", "ck_jpeg_bad_frame",
+    "ck_jpeg_quant", "ck_jpeg_encode_bound", "ck_jpeg_forward", "ck_jpeg_entropy_encode", "ck_jpeg_encode", "ck_get_perspective_transform", "ck_warp_perspective",
     "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
@@ -142,6 +143,11 @@ def lib():
         L.ck_jpeg_reconstruct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
         L.ck_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.ck_jpeg_bad_frame.argtypes = [C.c_void_p, C.c_void_p]
+        L.ck_jpeg_quant.argtypes = [C.c_int, C.c_void_p]
+        L.ck_jpeg_encode_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ck_jpeg_forward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.ck_jpeg_entropy_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ck_jpeg_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -461,6 +467,40 @@ class Context:
             op, osp, _ = self._in(out)
         self._chk(lib().ck_jpeg_reconstruct(self._h, cp, qp, n, int(h), int(w), int(sampling), sp, op, osp))
         return out
+
+    def jpeg_forward(self, frames, quant, sampling=CK_JPEG_420, out=None):
+        """the GPU half of the encoder alone: BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM,
+        and one set of quant tables (3, 64) as jpeg_quant gives them -> coefficients (n, blocks * 64) int16 in the memory
+        space of the input, in the layout jpeg_coefficients gives and jpeg_reconstruct takes"""
+        _check_frames(frames)
+        n, h, w = self._shape(frames, 3)
+        sampling = int(sampling)
+        quant = _quant_tables(quant)
+        p, sp, keep = self._in(frames)
+        shape = (n, jpeg_blocks(h, w, sampling) * 64)
+        if out is None:
+            out, op, osp = self._out(frames, shape, np.int16)
+        else:
+            _check_array(out, shape, np.int16, "out")
+            op, osp, _ = self._in(out, np.int16)
+        self._chk(lib().ck_jpeg_forward(self._h, p, n, h, w, sp, quant.ctypes.data_as(C.c_void_p), sampling, op, osp))
+        return out
+
+    def jpeg_encode(self, frames, quality=90, sampling=CK_JPEG_420, restart_interval=0):
+        """BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM -> a list of n `bytes`: baseline
+        JPEG streams, byte for byte what PIL.Image.save(.., "JPEG", quality=quality, subsampling=..) writes.  The forward
+        kernel runs on the GPU, the Huffman coder on the host (the frames of a batch in parallel).  restart_interval in
+        MCUs, 0: none."""
+        _check_frames(frames)
+        n, h, w = self._shape(frames, 3)
+        sampling = int(sampling)
+        stride = jpeg_encode_bound(h, w, sampling)
+        p, sp, keep = self._in(frames)
+        out = np.empty(n * stride, np.uint8)             # (pages the streams do not reach are never touched)
+        lens = (C.c_size_t * n)()
+        self._chk(lib().ck_jpeg_encode(self._h, p, n, h, w, sp, int(quality), sampling, int(restart_interval),
+                                       out.ctypes.data_as(C.c_void_p), stride, lens))
+        return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
     def pyr_down(self, frames, levels=1, out=None):
         """cv2.pyrDown of BGR frames (n, h, w, 3) or one frame (h, w, 3), applied `levels` (>= 1) times -> frames of
@@ -1020,6 +1060,63 @@ def jpeg_coefficients(streams):
         err.bad_frame = bad.value
         raise err
     return info, coef, quant
+
+
+def _check_frames(frames):
+    shp = tuple(frames.shape)
+    name = str(frames.dtype).replace("torch.", "")
+    if len(shp) not in (3, 4) or shp[-1] != 3 or name != "uint8" or 0 in shp:
+        raise CkError("frames: a uint8 array of shape (n, h, w, 3) or (h, w, 3) is needed, got %s %r" % (name, shp))
+    if _is_torch(frames) and not frames.is_contiguous():
+        raise CkError("frames: a contiguous tensor is needed")
+
+
+def _quant_tables(quant):
+    quant = np.ascontiguousarray(quant, np.uint16)
+    if quant.shape != (3, 64):
+        raise CkError("quant: tables of shape (3, 64) are needed, got %r" % (quant.shape,))
+    return quant
+
+
+def jpeg_quant(quality):
+    """the quant tables libjpeg derives from a quality (clamped to 1 .. 100) -> (3, 64) uint16, natural order, by
+    component (Y, Cb, Cr); host only"""
+    quant = np.empty((3, 64), np.uint16)
+    rc = lib().ck_jpeg_quant(int(quality), quant.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise _host_error(rc)
+    return quant
+
+
+def jpeg_encode_bound(h, w, sampling):
+    """the largest stream a frame of h x w can become, in bytes; host only"""
+    b = C.c_size_t(0)
+    rc = lib().ck_jpeg_encode_bound(int(h), int(w), int(sampling), C.byref(b))
+    if rc != 0:
+        raise _host_error(rc)
+    return b.value
+
+
+def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0):
+    """the Huffman stage of the encoder alone (host only): coefficients (n, blocks * 64) int16, or (blocks * 64,) of one
+    frame, in the layout of jpeg_coefficients + one set of quant tables (3, 64) -> a list of n `bytes` (one `bytes` for one
+    frame).  CkError (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code."""
+    h, w, sampling = int(h), int(w), int(sampling)
+    coef = np.ascontiguousarray(coef, np.int16)
+    single = coef.ndim == 1
+    coef = coef.reshape(1, -1) if single else coef
+    n = coef.shape[0]
+    _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
+    quant = _quant_tables(quant)
+    stride = jpeg_encode_bound(h, w, sampling)
+    out = np.empty(max(1, n) * stride, np.uint8)
+    lens = (C.c_size_t * max(1, n))()
+    rc = lib().ck_jpeg_entropy_encode(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+                                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
+    if rc != 0:
+        raise _host_error(rc)
+    streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+    return streams[0] if single else streams
 
 
 def get_perspective_transform(src4, dst4):

@@ -274,6 +274,119 @@ def write_mjpeg_avi(path, jpeg_frames, h, w, fps=(30, 1)):
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+AVI_MAX_BYTES = 1 << 30          # what AviMjpegCapture reads of a file: the first RIFF chunk, no OpenDML extension
+
+
+def _default_encode():
+    from .. import capi
+    return capi.get_context().jpeg_encode
+
+
+def write_jpeg(path, bgr, quality=90, sampling=None, encode=None):
+    """one BGR image (h, w, 3), a numpy array or a tensor in HBM, as a baseline JPEG still: the bytes libjpeg's default
+    compressor writes (cv2.imwrite, PIL.Image.save).  sampling: capi.CK_JPEG_* (4:2:0 when None); encode: a callable
+    (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context.  -> bytes written"""
+    from .. import capi
+    if len(bgr.shape) != 3 or bgr.shape[2] != 3:
+        raise ValueError("write_jpeg takes one (h, w, 3) image, got %r" % (tuple(bgr.shape),))
+    encode = encode or _default_encode()
+    data = encode(bgr[None], quality=quality, sampling=capi.CK_JPEG_420 if sampling is None else sampling)[0]
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
+class MjpegWriter:
+    """Motion-JPEG into a RIFF 'AVI ' file, streamed: write(frames) encodes a batch -- (n, h, w, 3) BGR, a numpy array or a
+    tensor in HBM -- and appends one '00dc' chunk per frame; close() patches the RIFF, movi, avih and strh fields that depend
+    on the frame count and appends the 'idx1' index.  The layout is write_mjpeg_avi's, so AviMjpegCapture reads it back.
+    `encode`: a callable (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context.
+    A batch that would take the file past AVI_MAX_BYTES raises AviError before any of it is written (the reader stops
+    there: no OpenDML); the file can still be closed and holds the batches before.  Use as a context manager, or close()."""
+
+    def __init__(self, path, h, w, fps=30.0, quality=90, sampling=None, encode=None):
+        from .. import capi
+        self.path, self.h, self.w = path, int(h), int(w)
+        self.quality = int(quality)
+        self.sampling = capi.CK_JPEG_420 if sampling is None else int(sampling)
+        self.encode = encode
+        self.rate, self.scale = (int(fps[0]), int(fps[1])) if isinstance(fps, (tuple, list)) else (int(round(float(fps) * 1000)), 1000)
+        self.frames = 0
+        self._index = []                     # (offset from the 'movi' tag, length) of every chunk
+        self._biggest = 0
+        head = self._headers(0)
+        self._movi = len(head) - 4           # where the 'movi' tag stands
+        self._end = len(head)                # where the next chunk goes
+        self._f = open(path, "wb")
+        self._f.write(head)
+
+    def _headers(self, chunk_bytes):
+        """everything up to the first chunk, for the frames written so far, whose chunks take chunk_bytes"""
+        def chunk(cc, body):
+            return cc + struct.pack("<I", len(body)) + body
+
+        def lst(kind, body):
+            return b"LIST" + struct.pack("<I", len(body) + 4) + kind + body
+
+        w, h, n = self.w, self.h, self.frames
+        avih = struct.pack("<14I", int(1e6 * self.scale / max(1, self.rate)), 0, 0, 0x10, n, 0, 1, self._biggest, w, h, 0, 0, 0, 0)
+        strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIIIhhhh", 0, 0, 0, 0, self.scale, self.rate, 0, n, self._biggest,
+                                              0xFFFFFFFF, 0, 0, 0, w, h)
+        strf = struct.pack("<IiiHH", 40, w, h, 1, 24) + b"MJPG" + struct.pack("<IiiII", w * h * 3, 0, 0, 0, 0)
+        hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
+        head = b"AVI " + hdrl + b"LIST" + struct.pack("<I", 4 + chunk_bytes) + b"movi"
+        return b"RIFF" + struct.pack("<I", len(head) + chunk_bytes + 8 + 16 * n) + head
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def write(self, frames):
+        if self._f is None:
+            raise AviError("the writer is closed")
+        shp = tuple(frames.shape)
+        if len(shp) == 3:
+            frames, shp = frames[None], (1,) + shp
+        if len(shp) != 4 or shp[1:] != (self.h, self.w, 3):
+            raise ValueError("frames of %r where the file holds %dx%d BGR" % (shp, self.w, self.h))
+        if shp[0] == 0:
+            return 0
+        if self.encode is None:
+            self.encode = _default_encode()
+        streams = self.encode(frames, quality=self.quality, sampling=self.sampling)
+        if len(streams) != shp[0]:
+            raise AviError("the encoder gave %d streams for %d frames" % (len(streams), shp[0]))
+        sizes = [len(s) for s in streams]
+        grown = self._end + sum(8 + n + (n & 1) for n in sizes)
+        if grown + 8 + 16 * (self.frames + len(sizes)) > AVI_MAX_BYTES:
+            raise AviError("%s would pass %d bytes with these %d frames: AVI files above 1 GiB (OpenDML) are not written"
+                           % (self.path, AVI_MAX_BYTES, len(sizes)))
+        for s, n in zip(streams, sizes):
+            self._index.append((self._end - self._movi, n))
+            self._f.write(b"00dc" + struct.pack("<I", n))
+            self._f.write(s)
+            if n & 1:
+                self._f.write(b"\0")
+            self._end += 8 + n + (n & 1)
+        self.frames += len(sizes)
+        self._biggest = max([self._biggest] + sizes)
+        return len(sizes)
+
+    def close(self):
+        if self._f is None:
+            return
+        f, self._f = self._f, None
+        try:
+            f.write(b"idx1" + struct.pack("<I", 16 * self.frames)
+                    + b"".join(b"00dc" + struct.pack("<III", 0x10, o, n) for o, n in self._index))
+            f.seek(0)
+            f.write(self._headers(self._end - self._movi - 4))
+        finally:
+            f.close()
+
+
 class AviMjpegCapture:
     """cv2.VideoCapture look-alike over Motion-JPEG in an AVI container.  The file is memory mapped and walked once:
     hdrl/avih, the first 'vids' stream's strh (fps = dwRate / dwScale) and strf (biCompression or the stream handler must

@@ -15,6 +15,7 @@
 #include "ck_common.h"
 #include "ck_stonegeom.h"
 #include "ck_jpeg.h"
+#include "ck_jpeg_enc.h"
 
 thread_local std::string g_ck_create_error;
 static thread_local const ck_ctx* g_ck_busy_ctx = nullptr;     // the context that refused this thread's last call
@@ -754,6 +755,129 @@ int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame)
     CK_API_BEGIN(ctx)
     if (!frame) return ck_fail(ctx, CK_ERR_ARG, "frame is NULL");
     *frame = ctx->jpeg_bad_frame;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// ---- baseline JPEG encode: the forward kernel (k_jpeg_enc.hip) and the host half (ck_jpeg_enc.cpp) behind the ABI ----
+int ck_jpeg_quant(int quality, uint16_t* quant)
+{
+    if (!quant) return ck_fail(nullptr, CK_ERR_ARG, "quant is NULL");
+    ck_jpeg_enc_quant(quality, quant);
+    return CK_OK;
+}
+
+int ck_jpeg_encode_bound(int h, int w, int sampling, size_t* bytes)
+{
+    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
+    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
+    *bytes = ck_jpeg_enc_bound(h, w, sampling);
+    return CK_OK;
+}
+
+static int check_jpeg_quant(ck_ctx* ctx, const uint16_t* quant)
+{
+    for (int i = 0; i < 192; i++)
+        if (quant[i] < 1 || quant[i] > 255) return ck_fail(ctx, CK_ERR_ARG, "quant entry %d is %d: baseline tables hold 1 .. 255", i, quant[i]);
+    return CK_OK;
+}
+
+static int check_jpeg_out(ck_ctx* ctx, int h, int w, int sampling, int restart_interval, size_t stride)
+{
+    if (restart_interval < 0 || restart_interval > 65535) return ck_fail(ctx, CK_ERR_ARG, "restart interval %d: 0 .. 65535 MCUs", restart_interval);
+    if (stride < ck_jpeg_enc_bound(h, w, sampling))
+        return ck_fail(ctx, CK_ERR_ARG, "output buffer of %zu bytes per frame: smaller than the bound of %zu for a %dx%d frame", stride,
+                       ck_jpeg_enc_bound(h, w, sampling), w, h);
+    return CK_OK;
+}
+
+// the Huffman stage of n frames, in parallel; on failure *bad is the first frame that failed and `why` its message
+static int jpeg_encode_batch(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                             uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why)
+{
+    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64;
+    std::vector<int> rcs((size_t)n, CK_OK);
+    std::vector<std::string> msgs((size_t)n);
+    ck_parallel_for(n, 16, [&](int f) {
+        char msg[CK_JPEG_MSG];
+        rcs[f] = ck_jpeg_enc_entropy(coef + (size_t)f * cframe, quant, h, w, sampling, restart_interval, out + (size_t)f * stride, stride,
+                                     len + f, msg);
+        if (rcs[f] != CK_OK) msgs[f] = msg;
+    });
+    for (int f = 0; f < n; f++)
+        if (rcs[f] != CK_OK) { *bad = f; why = msgs[f]; return rcs[f]; }
+    return CK_OK;
+}
+
+int ck_jpeg_forward(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, const uint16_t* quant, int sampling,
+                    int16_t* coef, int out_space)
+{
+    CK_API_BEGIN(ctx)
+    if (!bgr || !quant || !coef || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
+    CK_TRY(check_jpeg_quant(ctx, quant));
+    const void *d_in, *d_quant;
+    CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
+    CK_TRY(ck_to_device(ctx, quant, 192 * sizeof(uint16_t), CK_HOST, ctx->in_stage2, &d_quant));
+    OutStage<int16_t> o;
+    CK_TRY(o.open(ctx, coef, (size_t)n * (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t), out_space, ctx->out_stage));
+    if ((uintptr_t)o.dev & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
+    CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, n, h, w, sampling, o.dev));
+    CK_TRY(o.deliver(ctx));
+    return finish(ctx);           // (also: the quant tables were read from the caller's memory by the time this returns)
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                           uint8_t* out, size_t stride, size_t* len)
+{
+    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
+    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
+    try {
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_encode_batch(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, why);
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, why.c_str());
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
+                   int restart_interval, uint8_t* out, size_t stride, size_t* len)
+{
+    CK_API_BEGIN(ctx)
+    if (!bgr || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
+    CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
+    uint16_t quant[192];
+    ck_jpeg_enc_quant(quality, quant);
+    const size_t iframe = (size_t)h * w * 3, cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
+    const int pass = jpeg_pass_frames(n, cframe);
+    // per pass: frames up (when they are the host's) -> the kernel -> the coefficients down in one copy into the pinned
+    // block -> the Huffman coder on the worker threads.  The stream is idle while they code, as in ck_jpeg_decode.
+    // The tables go up from the tail of the pinned block, not from this frame: the copy may outlive an early return.
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, (size_t)pass * cframe + sizeof quant));
+    CK_TRY(ck_ensure(ctx, ctx->out_stage, (size_t)pass * cframe));
+    void* pinned_quant = (uint8_t*)ctx->host_pinned.p + (size_t)pass * cframe;
+    memcpy(pinned_quant, quant, sizeof quant);
+    const void* d_quant;
+    CK_TRY(ck_to_device(ctx, pinned_quant, sizeof quant, CK_HOST, ctx->in_stage2, &d_quant));
+    for (int f0 = 0; f0 < n; f0 += pass) {
+        const int m = n - f0 < pass ? n - f0 : pass;
+        const void* d_in;
+        CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
+        CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, m, h, w, sampling, (int16_t*)ctx->out_stage.p));
+        CK_TRY(ck_from_device(ctx, ctx->host_pinned.p, ctx->out_stage.p, (size_t)m * cframe, CK_HOST));
+        CK_TRY(finish(ctx));
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_encode_batch((const int16_t*)ctx->host_pinned.p, quant, m, h, w, sampling, restart_interval,
+                                         out + (size_t)f0 * stride, stride, len + f0, &bad, why);
+        if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+    }
     return CK_OK;
     CK_API_END(ctx)
 }

@@ -279,6 +279,8 @@ int k_pyr_down(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, uint8_t* 
 int k_i420_pyr_down(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uint8_t* d_out);
 // baseline JPEG behind the Huffman decoder (k_jpeg.hip): coefficients + quant tables of n frames on the device -> BGR
 int k_jpeg_reconstruct(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* d_quant, int n, int h, int w, int sampling, uint8_t* d_bgr);
+// baseline JPEG in front of the Huffman coder (k_jpeg_enc.hip): BGR + one set of quant tables on the device -> coefficients
+int k_jpeg_forward(ck_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_quant, int n, int h, int w, int sampling, int16_t* d_coef);
 int k_warp(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, const double* d_minv, int m_count,
            int dsize, uint8_t* d_out);
 int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,

@@ -1,0 +1,24 @@
+// ck_jpeg_enc.h -- the host half of the JPEG encoder (ck_jpeg_enc.cpp): quant tables from a quality, JFIF headers and the
+// Huffman coder of baseline JPEG, byte for byte what libjpeg's default compressor writes.  No HIP and no context in here:
+// tools/sanitize/jpeg_enc_fuzz.cpp links ck_jpeg_enc.cpp and ck_jpeg.cpp on their own.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "ck_jpeg.h"
+
+// jpeg_set_quality(quality, force_baseline) over the tables of Annex K.1 / K.2 -> quant[3][64], natural order, by component
+// (Y, Cb, Cr; the two chroma tables are equal).  quality is clamped to 1 .. 100.
+void ck_jpeg_enc_quant(int quality, uint16_t* quant);
+
+// the largest stream a frame of this geometry can become: 26 bits per coefficient (a 16-bit code and 10 value bits) doubled
+// for byte stuffing, 4 bytes per MCU (padding of a restart interval, its stuffing, the marker), 1024 for the headers.
+// 0 for a geometry the encoder refuses.
+size_t ck_jpeg_enc_bound(int h, int w, int sampling);
+
+// coef (ck_jpeg_blocks * 64 int16, the layout of ck_jpeg_entropy) + quant[3][64] -> one stream at out, *len bytes of at most
+// cap.  CK_OK; CK_ERR_ARG for a geometry, table or restart interval outside baseline JPEG, a coefficient the tables of
+// Annex K.3 have no code for (a DC difference above 11 bits, an AC value above 10) and a buffer that is too small: nothing
+// is written beyond cap, whatever the coefficients are.  msg (CK_JPEG_MSG bytes) says why.
+int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
+                        uint8_t* out, size_t cap, size_t* len, char* msg);

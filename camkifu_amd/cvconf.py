@@ -20,6 +20,6 @@ sfinders = [
     ("camkifu_amd.stone.sf_clustering", "SfClustering"),
     ("None", "None"),
 ]
-snapshot_dir = "."                          # where VManagerBase.snapshot writes snapshot-N.npy / game-N.sgf
+snapshot_dir = "."                          # where VManagerBase.snapshot writes snapshot-N.npy (or .jpg) / game-N.sgf
 bf_loc = None
 sf_loc = None

@@ -157,6 +157,31 @@ int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, i
 /* the frame the context's last ck_jpeg_decode refused with CK_ERR_DATA, -1 when it refused none */
 int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame);
 
+/* ---- compressed output: baseline JPEG encode (.jpg stills, Motion-JPEG frames of an .avi)   core/vmanager.py:309-325 (cv2.imwrite)
+ * The mirror of the calls above, and as exact: the streams are, byte for byte, what libjpeg's default compressor writes
+ * (fixed-point RGB -> YCbCr, box downsampling without smoothing, slow-integer forward DCT, the quant tables of
+ * jpeg_set_quality, the Huffman tables of Annex K.3, JFIF 1.01 headers) -- PIL.Image.save(.., "JPEG", quality=q, subsampling=s).
+ *   GPU:  BGR frames -> per frame int16 quantised coefficient blocks, in the layout ck_jpeg_coefficients writes (one kernel)
+ *   host: headers + Huffman coder -> one stream per frame
+ * No optimised tables, no progressive or arithmetic coding, quality 1 .. 100. */
+/* quant[3][64] uint16 (natural order, by component) of a quality; clamped to 1 .. 100 (host only) */
+int ck_jpeg_quant(int quality, uint16_t* quant);
+/* *bytes: the largest stream a frame of h x w can become (host only) */
+int ck_jpeg_encode_bound(int h, int w, int sampling, size_t* bytes);
+/* n BGR frames of h x w (in `in_space`) + one set of quant tables (HOST memory, entries 1 .. 255) -> coef, n * blocks * 64
+ * int16 (in `out_space`; on the device it must lie on 16 bytes).  CK_JPEG_GREY encodes Y alone. */
+int ck_jpeg_forward(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, const uint16_t* quant, int sampling,
+                    int16_t* coef, int out_space);
+/* coefficients of n frames + one set of quant tables -> n streams: frame f at out + f * stride, len[f] bytes (host only;
+ * the frames are coded in parallel on the library's worker threads).  stride must be at least ck_jpeg_encode_bound;
+ * restart_interval in MCUs, 0: none.  CK_ERR_ARG names a coefficient the baseline Huffman tables cannot code. */
+int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                           uint8_t* out, size_t stride, size_t* len);
+/* both halves in one call: n BGR frames (in `in_space`) -> n streams in HOST memory, laid out as above.  The coefficients
+ * come down in one copy into pinned memory of the context (a large batch in passes of about 256 MB each). */
+int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
+                   int restart_interval, uint8_t* out, size_t stride, size_t* len);
+
 /* ---- frame downsampling: CaptureReaderBase.downsample's cv2.pyrDown(img)   core/vmanager.py:484-498
  * OpenCV 3.1.0 pyrDown of 8-bit 3-channel frames, BORDER_DEFAULT, applied `levels` times: per level h x w becomes
  * (h+1)/2 x (w+1)/2 and dst[y,x] = (sum_{i,j=-2..2} k[i] k[j] src[r(2y+i), r(2x+j)] + 128) >> 8 with k = 1 4 6 4 1 and

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Timing of the Motion-JPEG frame source, in ONE process on one GPU -> profiles/jpeg_timing.json
 
-A filmed game (synth.film) at 1920x1080 is encoded with Pillow as baseline JPEG, 4:2:0, quality 90, and held in host memory.
+A filmed game (synth.film) at 1920x1080 is encoded with the project's encoder (Context.jpeg_encode: the bytes Pillow would
+write) as baseline JPEG, 4:2:0, quality 90, and held in host memory.
 1. host: the Huffman stage alone (capi.jpeg_coefficients), ms per frame -- one frame per call (one thread) and the whole
    batch per call (the library's worker threads, at most 16); warmed up, `--reps` alternating rounds, median / min / max.
 2. kernel: ck_jpeg_reconstruct on a batch of coefficients resident in HBM, output preallocated, HIP-event time
@@ -12,9 +13,8 @@ A filmed game (synth.film) at 1920x1080 is encoded with Pillow as baseline JPEG,
 
     python tools/jpeg_timing.py [--size 1920x1080] [--film 128] [--n 32] [--reps 7] [--inner 8] [--e2e-reps 5]
 
-Needs Pillow (to encode).  There is no CPU fallback: without a GPU the first device call raises."""
+There is no CPU fallback: without a GPU the first device call raises."""
 import argparse
-import io
 import json
 import os
 import sys
@@ -57,7 +57,6 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.reps < 5 or args.e2e_reps < 5:
         raise SystemExit("at least 5 alternating rounds per leg")
-    from PIL import Image
     import torch
     from camkifu_amd import capi, pipeline, synth
     from camkifu_amd.controller import ControllerHeadless
@@ -75,10 +74,7 @@ def main(argv=None):
     for b0 in range(0, F, 8):
         part = film[b0:b0 + 8]
         i420[b0:b0 + 8].copy_(i420_of(part))
-        for fr in part.cpu().numpy():
-            buf = io.BytesIO()
-            Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1]), "RGB").save(buf, "JPEG", quality=args.quality, subsampling=2)
-            jpegs.append(np.frombuffer(buf.getvalue(), np.uint8))
+        jpegs += [np.frombuffer(j, np.uint8) for j in ctx.jpeg_encode(part.contiguous(), quality=args.quality, sampling=capi.CK_JPEG_420)]
     del film
     torch.cuda.empty_cache()
     out["plan"]["jpeg_bytes_per_frame"] = int(np.mean([j.size for j in jpegs]))

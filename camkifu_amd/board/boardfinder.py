@@ -7,6 +7,7 @@ Contract (reference board/boardfinder.py:12-147): a subclass answers `_detect(fr
 import numpy as np
 
 from .. import capi, cvconf
+from ..core import overlay
 from ..core.video import VidProcessor
 
 
@@ -45,8 +46,25 @@ class GobanCorners:
     def clear(self):
         self._xy, self.hull = np.zeros((0, 2), np.int64), None
 
-    def paint(self, canvas):
-        """display only: nothing to draw on in the headless build"""
+    def display_list(self, into=None):
+        """what paint draws (reference board/boardfinder.py:121-134): a radius-5 circle in (255, 255, 0) on every point,
+        and the hull's edges hull[i] -> hull[i + 1] for i = -1 .. 2, the first in (0, 0, 255), the following along the
+        reference's ramp (255 (n - i - 1) / n, 0, 255 (i + 1) / n) with n = 3, truncated to integers"""
+        dl = into if into is not None else overlay.DisplayList()
+        for x, y in self._points:
+            dl.circle(x, y, 5, (255, 255, 0))
+        if self.hull is not None:
+            hull = [tuple(int(v) for v in p) for p in self.hull]
+            nbpts = len(hull) - 1
+            color = (0, 0, 255)
+            for i in range(-1, nbpts):
+                dl.segment(*hull[i], *hull[i + 1], color)
+                color = (255 * (nbpts - i - 1) / nbpts, 0, 255 * (i + 1) / nbpts)
+        return dl
+
+    def paint(self, img):
+        """draw the corner points found so far on `img`, and their convex hull if it exists: one library call"""
+        overlay.draw(img, self.display_list())
 
     def _refresh(self):
         quad = capi.ordered_hull(self._xy) if len(self._xy) > 3 else ()

@@ -20,6 +20,7 @@ CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
+CK_OV_SEGMENT, CK_OV_CIRCLE, CK_OV_DISC, CK_OV_RECT, CK_OV_TEXT = 1, 2, 3, 4, 5
 
 ZONE_LINES = 32        # CK_ZONE_LINES
 
@@ -29,6 +30,7 @@ EXPORTS = [
     "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
     "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_jpeg_probe", "ck_jpeg_coefficients", "ck_jpeg_reconstruct", "ck_jpeg_decode", "ck_jpeg_bad_frame",
     "ck_jpeg_quant", "ck_jpeg_encode_bound", "ck_jpeg_forward", "ck_jpeg_entropy_encode", "ck_jpeg_encode", "ck_get_perspective_transform", "ck_warp_perspective",
+    "ck_overlay_draw", "ck_overlay_plan", "ck_overlay_glyph",
     "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
     "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
     "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
@@ -148,6 +150,9 @@ def lib():
         L.ck_jpeg_forward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.ck_jpeg_entropy_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]
         L.ck_jpeg_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ck_overlay_draw.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int]
+        L.ck_overlay_plan.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        L.ck_overlay_glyph.argtypes = [C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -501,6 +506,42 @@ class Context:
         self._chk(lib().ck_jpeg_encode(self._h, p, n, h, w, sp, int(quality), sampling, int(restart_interval),
                                        out.ctypes.data_as(C.c_void_p), stride, lens))
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+
+    def overlay_draw(self, images, lists):
+        """draw display lists (core.overlay.DisplayList) on uint8 images, in place, and return `images`: one list for one
+        image (h, w) / (h, w, c), or a sequence of n lists for a batch (n, h, w) / (n, h, w, c), c in {1, 3}; a numpy
+        array (C-contiguous, writeable) or a torch tensor in HBM.  One kernel launch for the whole batch
+        (ck_overlay_draw); the rules of every primitive are in include/camkifu_amd.h."""
+        from .core.overlay import DisplayList, pack
+        single = isinstance(lists, DisplayList)
+        lists = [lists] if single else list(lists)
+        shp = tuple(images.shape)
+        name = str(images.dtype).replace("torch.", "")
+        lead = 0 if single else 1
+        if name != "uint8" or len(shp) not in (lead + 2, lead + 3):
+            raise CkError("images: a uint8 array of shape %s is needed, got %s %r" % (
+                "(h, w) or (h, w, c)" if single else "(n, h, w) or (n, h, w, c)", name, shp))
+        n = 1 if single else shp[0]
+        h, w = shp[lead], shp[lead + 1]
+        c = shp[lead + 2] if len(shp) == lead + 3 else 1
+        if len(lists) != n:
+            raise CkError("%d display lists for %d images" % (len(lists), n))
+        if _is_torch(images):
+            if not images.is_contiguous():
+                raise CkError("images: a contiguous tensor is needed")
+            if images.is_cuda:
+                p, sp, keep = self._in(images)
+            else:
+                keep = images.numpy()                            # (shares the tensor's memory)
+                p, sp = keep.ctypes.data_as(C.c_void_p), CK_HOST
+        elif isinstance(images, np.ndarray) and images.flags.c_contiguous and images.flags.writeable:
+            p, sp, keep = images.ctypes.data_as(C.c_void_p), CK_HOST, images
+        else:
+            raise CkError("images: a C-contiguous writeable numpy array or a torch tensor is needed (the drawing is in place)")
+        prims, start, text = pack(lists)
+        self._chk(lib().ck_overlay_draw(self._h, p, n, h, w, c, sp, prims.ctypes.data_as(C.c_void_p), start.ctypes.data_as(C.c_void_p),
+                                        C.c_char_p(text), len(text)))
+        return images
 
     def pyr_down(self, frames, levels=1, out=None):
         """cv2.pyrDown of BGR frames (n, h, w, 3) or one frame (h, w, 3), applied `levels` (>= 1) times -> frames of
@@ -1117,6 +1158,40 @@ def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0):
         raise _host_error(rc)
     streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
     return streams[0] if single else streams
+
+
+def overlay_plan(n, h, w, prims, frame_start, text_len=0):
+    """the plan ck_overlay_draw runs for n images of h x w (host only): prims (P, 8) int32, frame_start (n + 1,) int32 as
+    core.overlay.pack gives them -> (bin_size, bin_start (n * bins + 1,), bin_prims): bin b of the images, cut into squares
+    of bin_size row by row and frame after frame, owns bin_prims[bin_start[b]:bin_start[b + 1]], the indices of the
+    primitives whose bounding box meets it, ascending.  CkError (CK_ERR_ARG) for a list outside the limits."""
+    n, h, w = int(n), int(h), int(w)
+    prims = np.ascontiguousarray(prims, np.int32).reshape(-1, 8)
+    frame_start = np.ascontiguousarray(frame_start, np.int32)
+    if frame_start.shape != (n + 1,) or (n > 0 and int(frame_start.max()) > len(prims)):
+        raise CkError("frame_start: %d + 1 offsets into the %d primitives are needed" % (n, len(prims)))
+    bin_size, n_refs = C.c_int32(0), C.c_int32(0)
+    args = (n, h, w, prims.ctypes.data_as(C.c_void_p), frame_start.ctypes.data_as(C.c_void_p), int(text_len), C.byref(bin_size))
+    rc = lib().ck_overlay_plan(*args, None, None, 0, C.byref(n_refs))
+    if rc != 0:
+        raise _host_error(rc)
+    bins = n * -(-h // bin_size.value) * -(-w // bin_size.value) if n else 0
+    bin_start, bin_prims = np.zeros(bins + 1, np.int32), np.zeros(max(1, n_refs.value), np.int32)
+    rc = lib().ck_overlay_plan(*args, bin_start.ctypes.data_as(C.c_void_p), bin_prims.ctypes.data_as(C.c_void_p), n_refs.value,
+                               C.byref(n_refs))
+    if rc != 0:
+        raise _host_error(rc)
+    return bin_size.value, bin_start, bin_prims[:n_refs.value]
+
+
+def overlay_glyph(ch):
+    """the seven row bytes of the overlay font's glyph of byte `ch`, top row first, bit 4 = leftmost column -> (7,) uint8;
+    a byte outside 32 .. 126 gives the glyph of '?' (host only)"""
+    rows = np.zeros(7, np.uint8)
+    rc = lib().ck_overlay_glyph(int(ch), rows.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise _host_error(rc)
+    return rows
 
 
 def get_perspective_transform(src4, dst4):

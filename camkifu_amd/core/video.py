@@ -6,13 +6,16 @@ and the batch tools.  It offers the attributes SURVEY 8(b) lists as touched by c
 _doframe, interrupt, pause, next, ready_to_read, full_speed, total_f_processed, bindings, _show,
 metadata, _window_name (reference: core/video.py:60-332) -- built on threading.Event objects rather
 than polled flags: a paused loop sleeps on an event, an interrupt wakes every wait at once.
-Display output goes to the manager's image queue if it has one; HighGUI is out of scope."""
+Display output goes to the manager's image queue if it has one; HighGUI is out of scope.  With cvconf.annotate the
+metadata lines of the reference's windows (_draw_metadata, :223-271) are drawn on the image first, on the GPU."""
+import threading
 import time
 from collections import Counter, defaultdict
 from threading import Event, Thread
 from traceback import print_exc
 
 from .. import cvconf
+from . import overlay
 
 
 class VidProcessor:
@@ -100,12 +103,42 @@ class VidProcessor:
         self._one.set()
 
     # ------------------------------------------------------------------ display
-    def _show(self, img, name=None, loc=None, max_frequ=2, **_ignored):
-        """hand `img` to the manager's image queue, at most `max_frequ` times per second per window"""
+    def _draw_metadata(self, img, name, frame, latency, thread):
+        """print the info lines of the reference's windows on the image (reference core/video.py:241-266): from the top,
+        20 pixels apart at x = 40, the frame progression, the latency and the thread's name, each if asked for; from the
+        bottom, one line `k.format(v)` per entry of self.metadata, which is then cleared.  One display list, one library
+        call.  (The reference's "PAUSED" goes onto the windows it keeps; there are none here.)"""
+        from . import capture, imgutil
+        try:
+            x_offset, line_spacing, lines = 40, 20, []
+            if frame:
+                capt = self.vmanager.capt
+                lines.append("Frame {}/{} ({} not shown)".format(int(round(capt.get(capture.CAP_PROP_POS_FRAMES))),
+                                                                 int(round(capt.get(capture.CAP_PROP_FRAME_COUNT))),
+                                                                 self.dropped_images[name]))
+            if latency:
+                lines.append("latency: %.1f ms" % ((time.monotonic() - self._read_at) * 1000))
+            if thread:
+                lines.append("thread: " + threading.current_thread().name)
+            dl = overlay.DisplayList()
+            for k, s in enumerate(lines):
+                imgutil.str_list(img, s, x_offset, (k + 1) * line_spacing, into=dl)
+            for i, (k, v) in enumerate(self.metadata.items()):
+                imgutil.str_list(img, k.format(v), x_offset, img.shape[0] - (i + 1) * line_spacing, into=dl)
+            self.metadata.clear()
+            overlay.draw(img, dl, getattr(self, "ctx", None))
+        except Exception as exc:
+            print("VidProcessor._draw_metadata(): {}".format(exc))
+
+    def _show(self, img, name=None, loc=None, max_frequ=2, frame=True, latency=True, thread=False, **_ignored):
+        """hand `img` to the manager's image queue, at most `max_frequ` times per second per window; with cvconf.annotate
+        the metadata lines are drawn on it first (the default hands the image over as it is)"""
         name = name or self._window_name()
         sink = getattr(self.vmanager, "imqueue", None)
         now = time.monotonic()
         if sink is not None and now - self._shown_at.get(name, float("-inf")) > 1.0 / max_frequ:
+            if cvconf.annotate:
+                self._draw_metadata(img, name, frame, latency, thread)
             try:
                 sink.put_nowait((name, img, self, loc))
                 self._shown_at[name] = now

@@ -16,6 +16,7 @@
 #include "ck_stonegeom.h"
 #include "ck_jpeg.h"
 #include "ck_jpeg_enc.h"
+#include "ck_overlay.h"
 
 thread_local std::string g_ck_create_error;
 static thread_local const ck_ctx* g_ck_busy_ctx = nullptr;     // the context that refused this thread's last call
@@ -879,6 +880,59 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
         if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
     }
     return CK_OK;
+    CK_API_END(ctx)
+}
+
+// ---- overlays: the plan of ck_overlay.cpp, staged, and one launch of k_overlay.hip over its non-empty bins ----
+int ck_overlay_draw(ck_ctx* ctx, uint8_t* img, int n, int h, int w, int c, int space,
+                    const int32_t* prims, const int32_t* frame_start, const uint8_t* text, int text_len)
+{
+    CK_API_BEGIN(ctx)
+    if (c != 1 && c != 3) return ck_fail(ctx, CK_ERR_ARG, "images of %d channels: 1 or 3", c);
+    if (space != CK_HOST && space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", space);
+    char msg[CK_OV_MSG];
+    if (ck_overlay_check(n, h, w, prims, frame_start, text_len, msg) != CK_OK) return ck_fail(ctx, CK_ERR_ARG, "%s", msg);
+    if (n == 0 || frame_start[n] == 0) return CK_OK;
+    if (!img) return ck_fail(ctx, CK_ERR_ARG, "image pointer is NULL");
+    if (text_len > 0 && !text) return ck_fail(ctx, CK_ERR_ARG, "text is NULL");
+    const int total = frame_start[n];
+    const int nbx = (w + CK_OV_BIN - 1) / CK_OV_BIN, nby = (h + CK_OV_BIN - 1) / CK_OV_BIN;
+    const size_t bins = (size_t)n * nbx * nby;
+    int32_t bin_size = 0, n_refs = 0;
+    std::vector<int32_t> bin_start(bins + 1);
+    CK_TRY(ck_overlay_plan(n, h, w, prims, frame_start, text_len, &bin_size, bin_start.data(), nullptr, 0, &n_refs));
+    if (n_refs == 0) return CK_OK;                               // everything lies outside the images
+    size_t n_work = 0;
+    for (size_t b = 0; b < bins; b++) n_work += bin_start[b + 1] > bin_start[b];
+    if (n_work > 0x7fffffffu) return ck_fail(ctx, CK_ERR_ARG, "%zu bins to draw: too many", n_work);
+    // one block of pinned memory goes up in one copy: work items | bin entries | records | text
+    const size_t o_refs = n_work * 8, o_recs = o_refs + (size_t)n_refs, o_text = o_recs + (size_t)total * CK_OV_REC;
+    const size_t bytes = o_text * sizeof(int32_t) + (size_t)text_len;
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, bytes));
+    int32_t* blob = (int32_t*)ctx->host_pinned.p;
+    CK_TRY(ck_overlay_plan(n, h, w, prims, frame_start, text_len, &bin_size, bin_start.data(), blob + o_refs, n_refs, &n_refs));
+    for (int i = 0; i < total; i++) ck_overlay_record(prims + (size_t)i * CK_OV_PRIM, blob + o_recs + (size_t)i * CK_OV_REC);
+    if (text_len > 0) memcpy(blob + o_text, text, (size_t)text_len);
+    size_t k = 0;
+    for (size_t b = 0; b < bins; b++) {
+        const int32_t first = bin_start[b], count = bin_start[b + 1] - first;
+        if (count == 0) continue;
+        int32_t blends = 0;
+        for (int32_t j = 0; j < count && !blends; j++)
+            blends = ((uint32_t)prims[(size_t)blob[o_refs + first + j] * CK_OV_PRIM + 6] >> 24) != 255;
+        const size_t in_frame = b % ((size_t)nbx * nby);
+        int32_t* wk = blob + k++ * 8;
+        wk[0] = (int32_t)(b / ((size_t)nbx * nby)); wk[1] = (int32_t)(in_frame % nbx); wk[2] = (int32_t)(in_frame / nbx);
+        wk[3] = first; wk[4] = count; wk[5] = blends; wk[6] = wk[7] = 0;
+    }
+    const void *d_img, *d_blob;
+    const size_t img_bytes = (size_t)n * h * w * c;
+    CK_TRY(ck_to_device(ctx, img, img_bytes, space, ctx->in_stage, &d_img));
+    CK_TRY(ck_to_device(ctx, blob, bytes, CK_HOST, ctx->in_stage2, &d_blob));
+    const int32_t* d32 = (const int32_t*)d_blob;
+    CK_TRY(k_overlay(ctx, (uint8_t*)d_img, h, w, c, d32, (int)n_work, d32 + o_refs, d32 + o_recs, (const uint8_t*)(d32 + o_text)));
+    if (space == CK_HOST) CK_TRY(ck_from_device(ctx, img, d_img, img_bytes, CK_HOST));
+    return finish(ctx);
     CK_API_END(ctx)
 }
 

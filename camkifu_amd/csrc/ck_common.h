@@ -281,6 +281,9 @@ int k_i420_pyr_down(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uin
 int k_jpeg_reconstruct(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* d_quant, int n, int h, int w, int sampling, uint8_t* d_bgr);
 // baseline JPEG in front of the Huffman coder (k_jpeg_enc.hip): BGR + one set of quant tables on the device -> coefficients
 int k_jpeg_forward(ck_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_quant, int n, int h, int w, int sampling, int16_t* d_coef);
+// overlays (k_overlay.hip): n_work non-empty bins of the plan of ck_overlay.cpp, drawn in place on images of h x w x c
+int k_overlay(ck_ctx* ctx, uint8_t* d_img, int h, int w, int c, const int32_t* d_work, int n_work, const int32_t* d_refs,
+              const int32_t* d_recs, const uint8_t* d_text);
 int k_warp(ck_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, const double* d_minv, int m_count,
            int dsize, uint8_t* d_out);
 int k_board_lines(ck_ctx* ctx, const uint8_t* d_edges, int n, int h, int w, int hough_thresh,

@@ -23,3 +23,5 @@ sfinders = [
 snapshot_dir = "."                          # where VManagerBase.snapshot writes snapshot-N.npy (or .jpg) / game-N.sgf
 bf_loc = None
 sf_loc = None
+annotate = False                            # VidProcessor._show draws the metadata lines on the image before it queues it
+screenw, screenh = 1920, 1080               # what imgutil._factor fits an image into (the reference asks the window system)

@@ -44,6 +44,24 @@ def reference_positions(kifu, rules=False):
     return np.stack(out)
 
 
+def replay(mirror, emitted):
+    """the fold's per-frame requests, replayed on the controller `mirror` -> G_f of the frames (n, 19, 19)"""
+    from .stonesfinder import StoneSink
+    from ..capi import PolicyCore
+    sink = StoneSink(lambda: mirror)
+    out, now = np.empty((len(emitted), 19, 19), np.uint8), _codes(mirror)
+    for f, requests in enumerate(emitted):
+        for kind, moves in requests:
+            if kind == PolicyCore.SUGGEST:
+                sink.suggest(*moves[0], doprint=False)
+            else:
+                sink.bulk_update(moves)
+        if requests:
+            now = _codes(mirror)
+        out[f] = now
+    return out
+
+
 def new_window_state():
     """what label_windows carries from one batch to the next"""
     return dict(last=0, k=0, closed=False)
@@ -114,20 +132,7 @@ class Harvester:
     # ---- per batch -------------------------------------------------------------------------------------------
     def _replay(self, emitted):
         """the fold's per-frame requests -> G_f of the batch's frames (n, 19, 19)"""
-        from .stonesfinder import StoneSink
-        from ..capi import PolicyCore
-        sink = StoneSink(lambda: self._mirror)
-        out, now = np.empty((len(emitted), 19, 19), np.uint8), _codes(self._mirror)
-        for f, requests in enumerate(emitted):
-            for kind, moves in requests:
-                if kind == PolicyCore.SUGGEST:
-                    sink.suggest(*moves[0], doprint=False)
-                else:
-                    sink.bulk_update(moves)
-            if requests:
-                now = _codes(self._mirror)
-            out[f] = now
-        return out
+        return replay(self._mirror, emitted)
 
     def _thin(self, state_of, first):
         out = state_of.copy()

@@ -8,7 +8,8 @@ the batch pipeline folds whole batches with.  This class only moves arrays in an
 suggest() for a single new stone, bulk_update() otherwise."""
 import numpy as np
 
-from .. import capi
+from .. import capi, cvconf
+from ..core import overlay
 from ..core.exceptions import DeletedError
 from ..golib_shim import gsize, E, B, W
 from ..host import stones_finder_base
@@ -85,7 +86,35 @@ class SfNeural(stones_finder_base()):
         labels, conf = self.cache.regions()
         fg = self.get_foreground()
         counts = None if fg is None else zone_counts_host(fg, self._zones())
+        if cvconf.annotate:                                  # the reference's window: the targets as the policy is about to see them
+            canvas = np.array(goban_img, np.uint8, order="C")
+            overlay.draw(canvas, self.targets_list(counts), self.ctx)
+            self._show(canvas)
         self.policy.run(f, labels[None], conf[None], None if counts is None else counts[None], self._board_codes, self._apply)
+
+    def targets_list(self, counts=None, into=None):
+        """the rectangles the reference draws on its canvas: around every intersection under no watch whose target counter
+        is running, in (0, 0, red) with red = min(255, targets / TARGET_INCR * 255 // 4) (mark_targets, sf_neural.py:76-82),
+        then around the classifier's window of every region that holds a target above TARGET_THRESH, green (0, 255, 0)
+        where none of its zones has more than half its pixels in the foreground `counts` (19, 19) and the region would be
+        read, blue (255, 0, 0) where one has (select_targets, :135-153).  The counters are the policy's state as it
+        stands; the policy itself decides, this only shows."""
+        dl = into if into is not None else overlay.DisplayList()
+        st = self.policy.state()
+        targets, zones = st["targets"], self._zones()
+        for r, c in np.argwhere((targets > 0) & (st["heat_color"] == 0)):
+            x0, y0, x1, y1 = (int(v) for v in zones[r, c])
+            dl.rect(y0, x0, y1, x1, (0, 0, min(255, int(targets[r, c]) / TARGET_INCR * 255 // 4)))
+        area = (zones[..., 2] - zones[..., 0]) * (zones[..., 3] - zones[..., 1])
+        busy = np.zeros((gsize, gsize), bool) if counts is None else area * 0.5 < np.asarray(counts).reshape(gsize, gsize)
+        for i in range(self.manager.split):
+            for j in range(self.manager.split):
+                rs, re, cs, ce = self.manager._subregion(i, j)
+                if not (targets[rs:re, cs:ce] > TARGET_THRESH).any():
+                    continue
+                x0, x1, y0, y1 = self.manager._get_rect_nn(rs, re, cs, ce)
+                dl.rect(y0, x0, y1, x1, (255, 0, 0) if busy[rs:re, cs:ce].any() else (0, 255, 0))
+        return dl
 
     def _zones(self):
         grid = getattr(self, "_posgrid", None)

@@ -17,6 +17,7 @@ import queue
 import numpy as np
 
 from .. import capi, cvconf
+from ..core import imgutil, overlay
 from ..core.exceptions import CorrectionWarning, DeletedError
 from ..core.video import VidProcessor
 from ..golib_shim import gsize, E, B, W, Move, NP_TYPE
@@ -372,6 +373,73 @@ class StonesFinder(VidProcessor):
             mask = flat if depth <= 1 else np.repeat(flat[:, :, None], depth, axis=2)
             cached = self._mask_cache = (key, mask)
         return cached[1]
+
+    # ---- display: each builds ONE display list and makes one library call (core/overlay.py) ----------------------
+    def _grid_list(self, into=None):
+        dl = into if into is not None else overlay.DisplayList()
+        if self._posgrid is not None:
+            for p in self._posgrid.mtx.reshape(-1, 2):
+                dl.circle(int(p[1]), int(p[0]), 5, (255, 255, 0))
+        return dl
+
+    def _drawgrid(self, img):
+        """a circle of radius 5 in (255, 255, 0) around each intersection as currently estimated (reference
+        stone/stonesfinder.py:786-790)"""
+        overlay.draw(img, self._grid_list(), getattr(self, "ctx", None))
+
+    def _drawvalues(self, img, values):
+        """one value per goban position, str(value) at (x - 10, y + 2) of mtx[row, col] = (x, y) as the reference writes
+        it (:801-806); None draws nothing"""
+        dl = overlay.DisplayList()
+        for row in range(gsize):
+            for col in range(gsize):
+                if values[row, col] is not None:
+                    x, y = (int(v) for v in self._posgrid.mtx[row, col])
+                    imgutil.str_list(img, str(values[row, col]), x - 10, y + 2, into=dl)
+        overlay.draw(img, dl, getattr(self, "ctx", None))
+
+    def draw_stones(self, stones, canvas=None):
+        """an array of stones (gsize, gsize) as discs of radius 10, black (0, 0, 0) or white (255, 255, 255), on `canvas`
+        -- default: a new brown one, (65, 100, 128) -- then the grid's circles (reference :823-837) -> canvas"""
+        if canvas is None:
+            canvas = np.zeros((self._posgrid.size, self._posgrid.size, 3), np.uint8)
+            canvas[:] = (65, 100, 128)
+        dl = overlay.DisplayList()
+        for x in range(gsize):
+            for y in range(gsize):
+                if stones[x][y] == B or stones[x][y] == W:
+                    p = self._posgrid.mtx[x][y]
+                    dl.disc(int(p[1]), int(p[0]), 10, (0, 0, 0) if stones[x][y] == B else (255, 255, 255))
+        overlay.draw(canvas, self._grid_list(dl), getattr(self, "ctx", None))
+        return canvas
+
+    def display_intersections(self, grid, img):
+        """how the intersection analysis is doing (reference :852-860): a circle of radius 5 in get_display_color(i, j)
+        at every intersection of `grid` (find_intersections' answer: negated positions), over a black one where the
+        position was updated; then the image is shown.  cv2's even thicknesses 2 and 6 become the odd 3 and 7 of the
+        rasteriser, which keep the radius in the middle of the band."""
+        dl = overlay.DisplayList()
+        for i in range(grid.shape[0]):
+            for j in range(grid.shape[1]):
+                inter = grid[i][j]
+                dif = self._posgrid.mtx[i][j] + inter
+                if 0 < abs(int(dif[0])) + abs(int(dif[1])):
+                    dl.circle(-int(inter[1]), -int(inter[0]), 5, (0, 0, 0), thickness=7)
+                dl.circle(-int(inter[1]), -int(inter[0]), 5, self.get_display_color(i, j), thickness=3)
+        overlay.draw(img, dl, getattr(self, "ctx", None))
+        self._show(img, "{} - Intersections".format(self._window_name()))
+
+    @staticmethod
+    def get_display_color(i, j):
+        """the colour of intersection (i, j) in display_intersections (reference :866-870)"""
+        factor = 0.5 if i % 2 else 1
+        return 40 / factor, (230 if j % 2 else 10) * factor, (10 if j % 2 else 200) * factor
+
+    def display_message(self, message, name=None, force=False):
+        """a message in the middle of a black image of the goban image's shape (reference :883-885)"""
+        black = np.zeros(self.goban_img.shape[0:2], np.uint8)
+        imgutil.draw_str(black, message)
+        self._show(black, name=name)
 
     def _window_name(self):
         return "camkifu.stone.stonesfinder.StonesFinder"

@@ -182,6 +182,42 @@ int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, in
 int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
                    int restart_interval, uint8_t* out, size_t stride, size_t* len);
 
+/* ---- overlays: the finders' debug drawing (cv2.line / circle / rectangle / putText)   core/imgutil.py:71-118,
+ * board/boardfinder.py:121-134, stone/stonesfinder.py:779-885, core/video.py:223-271
+ * A display list is an ordered list of primitives per image, drawn in place by one kernel in which pixels own the work.
+ *   prims       int32 [P][8] = {kind, x0, y0, x1, y1, size, colour, aux}; colour = b | g << 8 | r << 16 | alpha << 24
+ *               (on a one-channel image the colour is its b byte)
+ *   frame_start int32 [n + 1], CSR: frame f owns prims[frame_start[f] : frame_start[f + 1]]
+ *   text        the bytes of every CK_OV_TEXT primitive: aux is its offset there, x1 its length
+ * Coordinates are integer pixel positions, may lie outside the image, and the picture is clipped per pixel.  Every rule
+ * is a per-pixel membership test in integer arithmetic ("Overlays", has them in full):
+ *   CK_OV_SEGMENT (x0,y0)-(x1,y1), size = thickness t, odd: the 8-connected Bresenham path with OpenCV's LineIterator
+ *               error rule, taken from the lexicographically smaller endpoint; major position i = 0 .. D visits minor
+ *               offset floor((2 d i + D - 1) / (2 D)), D = max(|dx|, |dy|), d = min; dilated by a t x t square
+ *   CK_OV_DISC  centre (x0,y0), size = radius r: dx^2 + dy^2 <= r^2 + r
+ *   CK_OV_CIRCLE centre (x0,y0), size = r, x1 = thickness t, odd: in disc(r + (t - 1) / 2) and not in disc(r - (t + 1) / 2);
+ *               a negative radius is the empty set
+ *   CK_OV_RECT  corners inclusive, in either order; size = thickness inwards from the outline, 0: filled
+ *   CK_OV_TEXT  (x0,y0) = top-left of the first cell, size = integer scale s: cells of 6s x 8s, the 5 x 7 glyph of the
+ *               project's own font (csrc/ck_font5x7.h) in the cell's top-left; bytes outside 32 .. 126 draw '?'
+ * Painted in list order: alpha 255 replaces the pixel, alpha 1 .. 254 leaves (c alpha + p (255 - alpha) + 127) / 255 per
+ * channel, p as the earlier primitives of the call left it.  CK_ERR_ARG, before anything is launched, for an unknown kind,
+ * |coordinate| > 32767, t even or above 15, r outside 0 .. 4095, s outside 1 .. 8, alpha 0, a text range outside the
+ * byte string, a frame_start that is not monotone from 0, and c outside {1, 3}.  n = 0 and empty lists draw nothing. */
+enum { CK_OV_SEGMENT = 1, CK_OV_CIRCLE = 2, CK_OV_DISC = 3, CK_OV_RECT = 4, CK_OV_TEXT = 5 };
+/* draws on n images of h x w x c (in `space`), in place; prims, frame_start and text are in HOST memory */
+int ck_overlay_draw(ck_ctx* ctx, uint8_t* img, int n, int h, int w, int c, int space,
+                    const int32_t* prims, const int32_t* frame_start, const uint8_t* text, int text_len);
+/* the plan ck_overlay_draw runs (host only): validates the list and bins it.  The image is cut into square bins of
+ * *bin_size pixels, ceil(h / bin_size) rows of ceil(w / bin_size), numbered row by row, frame after frame; bin b owns
+ * bin_prims[bin_start[b] : bin_start[b + 1]]: the indices (into prims) of the primitives of its frame whose bounding box
+ * meets it, ascending.  *n_refs is the length of bin_prims.  bin_start (n * bins + 1 entries) and bin_prims may be NULL:
+ * only the two sizes are returned.  CK_ERR_CAPACITY when bin_prims is given and cap < *n_refs (nothing is written to it). */
+int ck_overlay_plan(int n, int h, int w, const int32_t* prims, const int32_t* frame_start, int text_len,
+                    int32_t* bin_size, int32_t* bin_start, int32_t* bin_prims, int cap, int32_t* n_refs);
+/* the seven row bytes of the glyph of byte ch (bit 4 = leftmost column), '?' for a byte outside 32 .. 126 (host only) */
+int ck_overlay_glyph(int ch, uint8_t rows[7]);
+
 /* ---- frame downsampling: CaptureReaderBase.downsample's cv2.pyrDown(img)   core/vmanager.py:484-498
  * OpenCV 3.1.0 pyrDown of 8-bit 3-channel frames, BORDER_DEFAULT, applied `levels` times: per level h x w becomes
  * (h+1)/2 x (w+1)/2 and dst[y,x] = (sum_{i,j=-2..2} k[i] k[j] src[r(2y+i), r(2x+j)] + 128) >> 8 with k = 1 4 6 4 1 and

@@ -3,7 +3,8 @@
 Huffman coder on the host's worker threads) and appended to an .avi through core.capture.MjpegWriter.
 
     python tools/transcode.py SRC OUT.avi [--quality Q] [--sampling 420|422|444|grey] [--batch N]
-    python tools/transcode.py SRC OUT.avi --gobans [--sgf game.sgf]
+    python tools/transcode.py SRC OUT.avi --gobans [--annotate] [--sgf game.sgf]
+    python tools/transcode.py SRC OUT.avi --annotate [--sgf game.sgf]
 
 SRC is anything core.capture.open_capture takes: a .y4m file, a Motion-JPEG .avi, a .npy file of (n, h, w, 3) BGR frames.
 Every frame of SRC goes into OUT, at SRC's frame rate; a .y4m or .avi is converted / decoded straight into HBM and encoded
@@ -13,7 +14,15 @@ from there.
 cvconf.file_fps, as every run of a file is) and each batch's canonical 380 x 380 goban images are encoded while they are
 still in HBM.  OUT then holds one 380 x 380 frame per processed frame; frames of a batch that had no board transform yet
 (nothing was warped) are black.  With --sgf the record of the run is checked against the reference game and the match line
-of tools/detectiontest.py is printed.  There is no CPU fallback: without a GPU the first device call raises."""
+of tools/detectiontest.py is printed.
+
+--annotate draws what the finders concluded onto the frames before they are encoded, on the GPU, one overlay_draw per batch
+(core/annotate.py builds the lists, csrc/k_overlay.hip rasterises them).  With --gobans each goban image gets the grid, the
+stones of the game position after that frame, the agitated zones in translucent red, "Frame i/N" and the moves the frame
+emitted.  Without --gobans every ANALYSED frame of SRC is written at full size with the board's corners and hull in force
+after its batch, the 361 intersections projected back into the frame, the stones on top and the same two lines of text;
+frames before the first detection carry only the text.  There is no CPU fallback: without a GPU the first device call
+raises."""
 import argparse
 import os
 import sys
@@ -67,13 +76,25 @@ def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None):
     return dict(frames=wr.frames, bytes=os.path.getsize(out), h=int(h), w=int(w), fps=float(fps))
 
 
-def record_gobans(src, out, quality=90, sampling=3, batch=64, ctx=None, controller=None, fps=None, **pipe_args):
+def _own_copy(frames):
+    """a copy the annotation may draw on, in the memory the frames are in"""
+    return frames.clone() if hasattr(frames, "clone") else np.array(frames, np.uint8, order="C")
+
+
+def record_gobans(src, out, quality=90, sampling=3, batch=64, ctx=None, controller=None, fps=None, annotate=False,
+                  full_frames=False, **pipe_args):
     """the film `src` (a path, an open capture, or an array of frames, every one of which is processed) through a one-rank
-    pipeline, its goban images into `out` -> dict(frames, bytes, requests): `requests` is what the fold emitted"""
+    pipeline, its goban images into `out` -> dict(frames, bytes, requests): `requests` is what the fold emitted.
+    annotate: what the finders concluded is drawn onto each batch before it is encoded (module docstring), one
+    overlay_draw per batch on the tensor that goes to the writer.  full_frames (with annotate): the analysed frames
+    themselves are written, annotated, instead of the goban images."""
     from camkifu_amd import capi, cvconf
     from camkifu_amd.controller import ControllerHeadless
-    from camkifu_amd.core.capture import AviMjpegCapture, MjpegWriter, Y4MCapture, open_capture
+    from camkifu_amd.core import annotate as ann
+    from camkifu_amd.core.capture import AviMjpegCapture, MjpegWriter, Y4MCapture, file_frame_indices, open_capture
     from camkifu_amd.pipeline import FastFilePipeline
+    from camkifu_amd.stone.harvest import replay
+    from camkifu_amd.stone.stonesfinder import PosGrid
     ctx = ctx if ctx is not None else capi.get_context()
     controller = controller if controller is not None else ControllerHeadless()
     capture = src
@@ -86,15 +107,37 @@ def record_gobans(src, out, quality=90, sampling=3, batch=64, ctx=None, controll
     h, w = (capture.h, capture.w) if is_file else frames.shape[1:3]
     if fps is None:
         fps = float(getattr(cvconf, "file_fps", 0) or 5.0) if is_file else 30.0
+    if full_frames and not annotate:
+        raise ValueError("full_frames is the annotated film of the analysed frames: it needs annotate=True")
     black = np.zeros((1, GOBAN, GOBAN, 3), np.uint8)
-    wr = MjpegWriter(out, GOBAN, GOBAN, fps=fps, quality=quality, sampling=sampling, encode=ctx.jpeg_encode)
+    oh, ow = (h, w) if full_frames else (GOBAN, GOBAN)
+    wr = MjpegWriter(out, oh, ow, fps=fps, quality=quality, sampling=sampling, encode=ctx.jpeg_encode)
+    total = len(file_frame_indices(len(capture), capture.fps, None)) if is_file else len(frames)
+    mirror = ControllerHeadless(rules=getattr(controller, "rules", None) is not None)     # the requests replayed: the position per frame
+    grid, done = PosGrid(GOBAN), [0]
+
+    def lists_of(pipe, emitted, n_total):
+        """one display list per frame of the batch"""
+        codes = replay(mirror, emitted)
+        fg = pipe.last_fgcount
+        out_lists = []
+        for f in range(n_total):
+            no, said = done[0] + f + 1, ann.moves_text(emitted[f])
+            if full_frames:
+                out_lists.append(ann.frame_list((h, w), pipe.board.finder.corners, pipe.board.mtx, codes[f], grid, no, total, said))
+            else:
+                out_lists.append(ann.goban_list(codes[f], None if fg is None else fg[f], grid, no, total, said))
+        done[0] += n_total
+        return out_lists
 
     class _Pipe(FastFilePipeline):                               # hooked the way stone/harvest.py hooks it
         def process_batch(self, my_frames, n_total):
             emitted = FastFilePipeline.process_batch(self, my_frames, n_total)
-            gobans = self.last_gobans
+            gobans = my_frames if full_frames else self.last_gobans
             if gobans is None:                                   # no transform yet: nothing was warped
                 gobans = np.broadcast_to(black, (n_total, GOBAN, GOBAN, 3))
+            if annotate:                                         # drawn where the images are; pipeline's own stay as they were
+                gobans = ctx.overlay_draw(_own_copy(gobans), lists_of(self, emitted, n_total))
             wr.write(gobans)                                    # (still in HBM when the frames were)
             return emitted
 
@@ -122,12 +165,14 @@ def main(argv=None):
     ap.add_argument("--sampling", choices=sorted(SAMPLINGS), default="420")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--gobans", action="store_true", help="record the 380x380 goban images of a pipeline run instead of the frames")
-    ap.add_argument("--sgf", help="with --gobans: the reference game the run's record is checked against")
+    ap.add_argument("--annotate", action="store_true", help="draw what the finders concluded onto the frames, on the GPU; "
+                    "without --gobans the analysed frames are written at full size")
+    ap.add_argument("--sgf", help="with --gobans or --annotate: the reference game the run's record is checked against")
     args = ap.parse_args(argv)
     if not args.out.lower().endswith(".avi"):
         raise SystemExit("the output is a Motion-JPEG .avi file")
     sampling = SAMPLINGS[args.sampling]
-    if not args.gobans:
+    if not args.gobans and not args.annotate:
         res = transcode(args.src, args.out, args.quality, sampling, args.batch)
         print("%s: %d frames of %dx%d at %.3g fps, %d bytes" % (args.out, res["frames"], res["w"], res["h"], res["fps"], res["bytes"]))
         return res
@@ -137,8 +182,9 @@ def main(argv=None):
     ctx = capi.get_context()
     ctx.cnn_set_weights(NNManager.get_net())
     t0 = time.time()
-    res = record_gobans(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx)
-    print("%s: %d goban images, %d bytes" % (args.out, res["frames"], res["bytes"]))
+    res = record_gobans(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx, annotate=args.annotate,
+                        full_frames=not args.gobans)
+    print("%s: %d %s, %d bytes" % (args.out, res["frames"], "goban images" if args.gobans else "annotated frames", res["bytes"]))
     if args.sgf:
         from camkifu_amd.golib_shim import Kifu
         from camkifu_amd.kifu_checker import KifuChecker, report

@@ -5,6 +5,7 @@ library has not been built, or no HIP device is present, the calls raise.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -23,26 +24,6 @@ CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
 CK_OV_SEGMENT, CK_OV_CIRCLE, CK_OV_DISC, CK_OV_RECT, CK_OV_TEXT = 1, 2, 3, 4, 5
 
 ZONE_LINES = 32        # CK_ZONE_LINES
-
-EXPORTS = [
-    "ck_ctx_create", "ck_ctx_create_prio", "ck_ctx_destroy", "ck_ctx_destroy2", "ck_stream_wait", "ck_last_error", "ck_backend", "ck_version", "ck_stream",
-    "ck_timing_enable", "ck_timing_reset", "ck_timing_get",
-    "ck_median15", "ck_median", "ck_canny", "ck_goban_canny", "ck_board_edges", "ck_board_lines", "ck_board_detect",
-    "ck_i420_to_bgr", "ck_pyr_down", "ck_i420_to_bgr_pyr", "ck_jpeg_probe", "ck_jpeg_coefficients", "ck_jpeg_reconstruct", "ck_jpeg_decode", "ck_jpeg_bad_frame",
-    "ck_jpeg_quant", "ck_jpeg_encode_bound", "ck_jpeg_forward", "ck_jpeg_entropy_encode", "ck_jpeg_encode", "ck_get_perspective_transform", "ck_warp_perspective",
-    "ck_overlay_draw", "ck_overlay_plan", "ck_overlay_glyph",
-    "ck_mog2_create", "ck_mog2_apply", "ck_mog2_destroy", "ck_mog2_get_state",
-    "ck_cnn_set_weights", "ck_cnn_set_mode", "ck_cnn_predict", "ck_cnn_maps", "ck_stones_detect",
-    "ck_train_create", "ck_train_destroy", "ck_train_step", "ck_train_grads", "ck_train_apply", "ck_train_get_weights",
-    "ck_train_get_adam_state", "ck_train_handover",
-    "ck_harvest_patches", "ck_augment_patches",
-    "ck_cnn_regions", "ck_stones_run", "ck_zone_counts", "ck_mog2_band_run",
-    "ck_board_detect_records", "ck_cnn_regions_records",
-    "ck_contour_stones", "ck_cluster_stones", "ck_rng_get", "ck_rng_set", "ck_contours_external", "ck_find_intersections", "ck_update_grid",
-    "ck_ordered_hull", "ck_boardfold_create", "ck_boardfold_destroy", "ck_boardfold_reset", "ck_boardfold_step", "ck_boardfold_run", "ck_round10", "ck_round10_reference",
-    "ck_policy_create", "ck_policy_destroy", "ck_policy_run", "ck_policy_run_records", "ck_policy_get_state", "ck_policy_set_state",
-    "ck_policy_watch",
-]
 
 WEIGHT_ORDER = ("c1w", "c1b", "c2w", "c2b", "c3w", "c3b", "c4w", "c4b", "d1w", "d1b", "d2w", "d2b")
 WEIGHT_SHAPES = dict(c1w=(5, 5, 3, 32), c1b=(32,), c2w=(5, 5, 32, 32), c2b=(32,),
@@ -65,7 +46,8 @@ REC_DTYPE = np.dtype([("status", "<i4"), ("n_contours", "<i4"), ("n_lines", "<i4
                       ("biggest_area", "<f8"), ("lines", "<f4", (REC_LMAX, 2)),
                       ("region_conf", "<f8", (10, 10)), ("region_label", "u1", (10, 10)), ("pad", "u1", (4,))])   # ck_frame_record
 REC_BYTES = REC_DTYPE.itemsize
-assert REC_BYTES == 1440
+if REC_BYTES != 1440:
+    raise ImportError("REC_DTYPE is %d bytes, ck_frame_record is 1440" % REC_BYTES)
 
 
 class CkError(RuntimeError):
@@ -88,6 +70,34 @@ def build(force=False):
     return SO_PATH
 
 
+HEADER = os.path.join(_HERE, os.pardir, "include", "camkifu_amd.h")       # (where csrc/Makefile needs it too)
+_SCALARS = {"int": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "long long": C.c_longlong,
+            "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
+_RETURNS = {"int": C.c_int, "void": None, "double": C.c_double, "const char*": C.c_char_p, "void*": C.c_void_p}
+
+
+def _signatures(header=HEADER):
+    """name -> (restype, argtypes) of every prototype the header declares: the one copy of the ABI on the Python side.
+    A pointer or array parameter is c_void_p, a scalar maps by its C type; a type outside the tables is an error here,
+    never a call with ctypes' defaults."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(header).read(), flags=re.S)
+    sigs = {}
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+[\s*]+)(ck_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        argtypes = []
+        for prm in ([] if params.strip() in ("", "void") else params.split(",")):
+            ctype = " ".join(w for w in prm.split()[:-1] if w != "const")
+            if "*" not in prm and "[" not in prm and ctype not in _SCALARS:
+                raise CkError("%s: no ctypes type for the parameter '%s'" % (name, prm.strip()))
+            argtypes.append(C.c_void_p if "*" in prm or "[" in prm else _SCALARS[ctype])
+        ret = " ".join(ret.replace("*", " * ").split()).replace(" *", "*")
+        if ret not in _RETURNS:
+            raise CkError("%s: no ctypes type for the return type '%s'" % (name, ret))
+        sigs[name] = (_RETURNS[ret], argtypes)
+    return sigs
+
+
+_SIGNATURES = _signatures()
+EXPORTS = sorted(_SIGNATURES)
 _lib = None
 
 
@@ -106,53 +116,9 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(SO_PATH)
-        L.ck_last_error.restype = C.c_char_p
-        L.ck_last_error.argtypes = [C.c_void_p]
-        L.ck_stream.restype = C.c_void_p
-        L.ck_stream.argtypes = [C.c_void_p]
-        L.ck_ctx_destroy.argtypes = [C.c_void_p]
-        L.ck_ctx_destroy.restype = None
-        L.ck_ctx_destroy2.argtypes = [C.c_void_p]
-        L.ck_stream_wait.argtypes = [C.c_void_p, C.c_void_p]
-        for fn in (L.ck_boardfold_destroy, L.ck_policy_destroy):
-            fn.argtypes = [C.c_void_p]
-            fn.restype = None
-        L.ck_boardfold_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_longlong,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ck_policy_run.argtypes = [C.c_void_p, C.c_int, C.c_longlong] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
-        L.ck_policy_run_records.argtypes = [C.c_void_p, C.c_int, C.c_longlong] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
-        for fn in (L.ck_round10, L.ck_round10_reference):
-            fn.argtypes, fn.restype = [C.c_double], C.c_double
-        L.ck_boardfold_run.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
-                                       + [C.c_void_p] * 5)
-        L.ck_policy_get_state.argtypes = [C.c_void_p] * 6
-        L.ck_policy_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.ck_policy_watch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_longlong]
-        L.ck_cluster_stones.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_int] + [C.c_void_p] * 5 + [C.c_longlong] + [C.c_void_p] * 3)
-        L.ck_rng_get.argtypes = [C.c_void_p, C.c_void_p]
-        L.ck_train_step.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
-                                    + [C.c_double, C.c_int, C.c_uint64, C.c_void_p])
-        L.ck_train_grads.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5
-                                     + [C.c_int, C.c_uint64, C.c_longlong] + [C.c_void_p] * 5)
-        L.ck_train_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
-        L.ck_harvest_patches.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-                                         + [C.c_int] * 3 + [C.c_uint32, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
-        L.ck_augment_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.ck_rng_set.argtypes = [C.c_void_p, C.c_uint64]
-        L.ck_jpeg_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ck_jpeg_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-        L.ck_jpeg_reconstruct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
-        L.ck_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.ck_jpeg_bad_frame.argtypes = [C.c_void_p, C.c_void_p]
-        L.ck_jpeg_quant.argtypes = [C.c_int, C.c_void_p]
-        L.ck_jpeg_encode_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.ck_jpeg_forward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.ck_jpeg_entropy_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ck_jpeg_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ck_overlay_draw.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int]
-        L.ck_overlay_plan.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-        L.ck_overlay_glyph.argtypes = [C.c_int, C.c_void_p]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -178,12 +144,36 @@ def _in(a, dtype=np.uint8):
     """-> (pointer, space, keepalive) for a numpy array or a torch tensor.  A DEVICE tensor must go through Context._in /
     Context._out instead (they order the context's stream behind torch's): this function refuses it."""
     if _is_torch(a):
-        assert a.is_contiguous()
         if a.is_cuda:
             raise CkError("a device tensor is handed to the library through Context._in / Context._out (stream-ordered hand-over)")
         a = a.numpy()
     a = np.ascontiguousarray(a, dtype)
     return a.ctypes.data_as(C.c_void_p), CK_HOST, a
+
+
+def _check_array(a, shape, dtypes, what, writeable=False):
+    """a numpy array or torch tensor the library reads or writes in place: shape (None: any), element type, contiguity (and
+    for an array it writes, that numpy lets it) -- else CkError.  The library cannot know how much memory lies behind its pointers:
+    sizes and element types are held on this side."""
+    dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+    if _is_torch(a):                 # (np.uint8.__name__ is the dtype's name too, and np.dtype.name takes microseconds)
+        ok = a.is_contiguous() and str(a.dtype).replace("torch.", "") in [getattr(d, "__name__", None) or np.dtype(d).name for d in dtypes]
+    elif isinstance(a, np.ndarray):
+        ok = a.flags.c_contiguous and a.dtype in dtypes and (a.flags.writeable or not writeable)
+    else:
+        raise CkError("%s: a numpy array or a torch tensor is needed, got %s" % (what, type(a).__name__))
+    if not ok or (shape is not None and tuple(a.shape) != tuple(shape)):
+        raise CkError("%s: a contiguous%s %s array%s is needed, got %s %r" % (
+            what, " writeable" if writeable else "", "/".join(np.dtype(d).name for d in dtypes),
+            "" if shape is None else " of shape %r" % (tuple(shape),), str(a.dtype).replace("torch.", ""), tuple(a.shape)))
+
+
+def _batch_of(a, tail, what):
+    """n of `a`, n images of shape `tail` or one without the batch axis: the library reads n of exactly that size"""
+    shp = tuple(a.shape)
+    if shp[-len(tail):] != tail or len(shp) - len(tail) not in (0, 1):
+        raise CkError("%s: shape (n,) + %r or %r is needed, got %r" % (what, tail, tail, shp))
+    return 1 if len(shp) == len(tail) else shp[0]
 
 
 class Context:
@@ -237,10 +227,9 @@ class Context:
         shp = tuple(img.shape)
         if len(shp) == 2 + (cn > 1):
             shp = (1,) + shp
-        n, h, w = shp[0], shp[1], shp[2]
-        if cn > 1:
-            assert shp[3] == cn, shp
-        return n, h, w
+        if len(shp) != 3 + (cn > 1) or (cn > 1 and shp[3] != cn):
+            raise CkError("images of shape (n, h, w%s) or one without n are needed, got %r" % (", %d" % cn if cn > 1 else "", tuple(img.shape)))
+        return shp[0], shp[1], shp[2]
 
     # Hand-over of DEVICE memory (torch tensors) -- the ONE place where it happens.  The library launches on the context's
     # own HIP stream; torch queues its kernels on the calling thread's current stream and reuses a freed block at once for
@@ -253,16 +242,32 @@ class Context:
         import torch
         self._chk(lib().ck_stream_wait(self._h, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 
-    def _in(self, a, dtype=np.uint8):
-        """-> (pointer, space, keepalive) for a numpy array or a torch tensor"""
+    def _in(self, a, dtype=np.uint8, shape=None, what="array"):
+        """an array the library reads -> (pointer, space, keepalive).  Host memory is converted to a C-contiguous array of
+        `dtype` (a copy where it has to be); a device tensor is taken as it lies, so it must be contiguous and of exactly
+        `dtype` (or one of a tuple of them, host memory being converted to the first).  `shape`: what the library will read,
+        where the call does not tell it -- compared in both memory spaces."""
         if _is_torch(a) and a.is_cuda:
-            assert a.is_contiguous()
+            _check_array(a, shape, dtype, what)
             self._order_behind_torch(a.device)
             return C.c_void_p(a.data_ptr()), CK_DEVICE, a
-        return _in(a, dtype)
+        p, sp, a = _in(a, dtype[0] if isinstance(dtype, tuple) else dtype)
+        if shape is not None and a.shape != tuple(shape):
+            raise CkError("%s: shape %r is needed, got %r" % (what, tuple(shape), a.shape))
+        return p, sp, a
 
-    def _out(self, like, shape, dtype):
-        """allocate an output in the same memory space as `like`"""
+    def _out(self, like, shape, dtype, out=None, to_device=None):
+        """the array the library writes -> (array, pointer, space): the caller's `out`, which is never copied (so it must
+        be contiguous, writeable and of exactly this shape and dtype: the pointer handed over is its own), or else a fresh
+        one on `to_device`, or else in the memory space of `like`"""
+        if out is not None:
+            if _is_torch(out) and out.is_cuda:
+                return (out,) + self._in(out, dtype, shape, "out")[:2]
+            _check_array(out, shape, dtype, "out", writeable=True)
+            mem = out.numpy() if _is_torch(out) else out                # (a host tensor's array shares its memory)
+            return out, mem.ctypes.data_as(C.c_void_p), CK_HOST
+        if to_device is not None:
+            return self._out_on(to_device, shape, dtype)
         if _is_torch(like) and like.is_cuda:
             return self._out_on(like.device, shape, dtype)
         a = np.empty(shape, dtype)
@@ -366,7 +371,7 @@ class Context:
         """-> (pointer, space, keepalive) of n records: a C-contiguous numpy array of REC_DTYPE, or a contiguous torch uint8
         tensor (n, REC_BYTES) in HBM"""
         if _is_torch(rec):
-            if tuple(rec.shape) != (n, REC_BYTES) or not rec.is_contiguous() or rec.element_size() != 1:
+            if tuple(rec.shape) != (n, REC_BYTES) or not rec.is_contiguous() or "uint8" not in str(rec.dtype):
                 raise ValueError("records: expected a contiguous uint8 tensor of shape (%d, %d), got %r" % (n, REC_BYTES, tuple(rec.shape)))
             if rec.is_cuda:
                 return self._in(rec)
@@ -383,11 +388,14 @@ class Context:
         self._chk(lib().ck_board_detect_records(self._h, p, n, h, w, sp, int(hough_thresh), rp, rsp))
         return rec
 
+    def _goban(self, goban):
+        """n goban images (n, 380, 380, 3), or one (380, 380, 3), whose size the library takes for granted -> (n,) + _in()"""
+        n = _batch_of(goban, (380, 380, 3), "goban")
+        return (n,) + self._in(goban, what="goban")
+
     def cnn_regions_records(self, goban, rec):
         """K10..K12 of the goban images -> the stones half of their records, in place (ck_cnn_regions_records)"""
-        shp = tuple(goban.shape)
-        n = 1 if len(shp) == 3 else shp[0]
-        p, sp, keep = self._in(goban)
+        n, p, sp, keep = self._goban(goban)
         rp, rsp, keep2 = self._rec(rec, n)
         self._chk(lib().ck_cnn_regions_records(self._h, p, n, sp, rp, rsp))
         return rec
@@ -399,27 +407,18 @@ class Context:
         fast-file path uploads 1.5 B/px and converts on the GPU); `out`: a preallocated BGR tensor / array to fill.
         `levels` > 0: the frames come out pyrDown-ed that many times, of shape pyr_shape(h, w, levels) -- bit for bit
         pyr_down(i420_to_bgr(..), levels), but the full-size BGR frames are never written (ck_i420_to_bgr_pyr)."""
-        fsz = h * w * 3 // 2
+        h, w, levels = int(h), int(w), int(levels)
         single = len(i420.shape) == 1
-        n = 1 if single else int(i420.shape[0])
-        assert int(i420.shape[-1]) == fsz, (tuple(i420.shape), fsz)
-        levels = int(levels)
+        n = _batch_of(i420, (h * w * 3 // 2,), "i420")
         if levels and ((h | w) & 1):
             raise CkError("I420 needs even dimensions, got %dx%d" % (w, h))
         oh, ow = pyr_shape(h, w, levels)
-        p, sp, keep = self._in(i420)
-        oshape = (oh, ow, 3) if single else (n, oh, ow, 3)
-        if out is not None:
-            assert tuple(out.shape) == oshape
-            op, osp, _ = self._in(out)
-        elif to_device is not None and sp == CK_HOST:
-            out, op, osp = self._out_on(to_device, oshape, np.uint8)
-        else:
-            out, op, osp = self._out(i420, oshape, np.uint8)
+        p, sp, keep = self._in(i420, what="i420")
+        out, op, osp = self._out(i420, (oh, ow, 3) if single else (n, oh, ow, 3), np.uint8, out, to_device if sp == CK_HOST else None)
         if levels:
-            self._chk(lib().ck_i420_to_bgr_pyr(self._h, p, n, int(h), int(w), levels, sp, op, osp))
+            self._chk(lib().ck_i420_to_bgr_pyr(self._h, p, n, h, w, levels, sp, op, osp))
         else:
-            self._chk(lib().ck_i420_to_bgr(self._h, p, n, int(h), int(w), sp, op, osp))
+            self._chk(lib().ck_i420_to_bgr(self._h, p, n, h, w, sp, op, osp))
         return out
 
     def jpeg_decode(self, streams, to_device=None, out=None):
@@ -435,14 +434,7 @@ class Context:
             err = CkError("libck_hip error %d: frame 0: %s" % (rc, why))
             err.code, err.bad_frame = rc, 0
             raise err
-        oshape = (n, info["h"], info["w"], 3)
-        if out is not None:
-            _check_array(out, oshape, np.uint8, "out")
-            op, osp, _ = self._in(out)
-        elif to_device is not None:
-            out, op, osp = self._out_on(to_device, oshape, np.uint8)
-        else:
-            out, op, osp = self._out(None, oshape, np.uint8)
+        out, op, osp = self._out(None, (n, info["h"], info["w"], 3), np.uint8, out, to_device)
         rc = lib().ck_jpeg_decode(self._h, ptrs, lens, n, op, osp)
         if rc == CK_ERR_DATA:
             bad = C.c_int32(-1)
@@ -458,19 +450,14 @@ class Context:
         """the GPU half alone: coefficients (n, blocks * 64) int16 and quant tables (n, 3, 64) uint16 as jpeg_coefficients
         gives them (numpy arrays, or torch tensors in HBM) -> BGR (n, h, w, 3) in the memory space of the input"""
         n, h, w, sampling = int(coef.shape[0]), int(h), int(w), int(sampling)
-        # the library cannot know how much memory lies behind its pointers: sizes and element types are held here
         _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
         _check_array(quant, (n, 3, 64), (np.uint16, np.int16), "quant")          # (torch below 2.3 has no uint16: the bits count)
         cp, sp, keep = self._in(coef, np.int16)
-        qp, qsp, keep2 = self._in(quant, np.asarray(quant).dtype if not _is_torch(quant) else np.uint16)
+        qp, qsp, keep2 = self._in(quant, (np.uint16, np.int16))
         if sp != qsp:
             raise CkError("coef and quant must lie in the same memory space")
-        if out is None:
-            out, op, osp = self._out(coef, (n, h, w, 3), np.uint8)
-        else:
-            _check_array(out, (n, h, w, 3), np.uint8, "out")
-            op, osp, _ = self._in(out)
-        self._chk(lib().ck_jpeg_reconstruct(self._h, cp, qp, n, int(h), int(w), int(sampling), sp, op, osp))
+        out, op, osp = self._out(coef, (n, h, w, 3), np.uint8, out)
+        self._chk(lib().ck_jpeg_reconstruct(self._h, cp, qp, n, h, w, sampling, sp, op, osp))
         return out
 
     def jpeg_forward(self, frames, quant, sampling=CK_JPEG_420, out=None):
@@ -482,12 +469,7 @@ class Context:
         sampling = int(sampling)
         quant = _quant_tables(quant)
         p, sp, keep = self._in(frames)
-        shape = (n, jpeg_blocks(h, w, sampling) * 64)
-        if out is None:
-            out, op, osp = self._out(frames, shape, np.int16)
-        else:
-            _check_array(out, shape, np.int16, "out")
-            op, osp, _ = self._in(out, np.int16)
+        out, op, osp = self._out(frames, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, out)
         self._chk(lib().ck_jpeg_forward(self._h, p, n, h, w, sp, quant.ctypes.data_as(C.c_void_p), sampling, op, osp))
         return out
 
@@ -552,12 +534,7 @@ class Context:
             raise CkError("pyramid levels %d: at least 1" % levels)
         oh, ow = pyr_shape(h, w, levels)
         p, sp, keep = self._in(frames)
-        oshape = (oh, ow, 3) if len(frames.shape) == 3 else (n, oh, ow, 3)
-        if out is None:
-            out, op, osp = self._out(frames, oshape, np.uint8)
-        else:
-            assert tuple(out.shape) == oshape and (out.is_contiguous() if _is_torch(out) else out.flags.c_contiguous)
-            op, osp, _ = self._in(out)
+        out, op, osp = self._out(frames, (oh, ow, 3) if len(frames.shape) == 3 else (n, oh, ow, 3), np.uint8, out)
         self._chk(lib().ck_pyr_down(self._h, p, n, h, w, levels, sp, op, osp))
         return out
 
@@ -567,13 +544,9 @@ class Context:
         n, h, w = self._shape(bgr, 3)
         p, sp, keep = self._in(bgr)
         M = np.ascontiguousarray(M, np.float64).reshape(-1, 9)
-        oshape = (dsize, dsize, 3) if len(bgr.shape) == 3 else (n, dsize, dsize, 3)
-        if out is None:
-            out, op, osp = self._out(bgr, oshape, np.uint8)
-        else:
-            assert tuple(out.shape) == oshape and (out.is_contiguous() if _is_torch(out) else out.flags.c_contiguous)
-            op, osp, _ = self._in(out)
-            assert osp == sp, "out must live where the frames live"
+        out, op, osp = self._out(bgr, (dsize, dsize, 3) if len(bgr.shape) == 3 else (n, dsize, dsize, 3), np.uint8, out)
+        if osp != sp:
+            raise CkError("out must live where the frames live")
         self._chk(lib().ck_warp_perspective(self._h, p, n, h, w, sp, M.ctypes.data_as(C.c_void_p), len(M),
                                             int(dsize), op, osp))
         return out
@@ -585,18 +558,29 @@ class Context:
         self._mog2_shape[hd.value] = (int(h), int(w))
         return hd.value
 
+    def _mog2_hw(self, handle):
+        """(h, w) of a model this context created: the size of what the library reads and writes for it.  Any other handle
+        is refused in the library's own words, before a size is taken on trust"""
+        st = self._mog2_shape.get(int(handle))
+        if st is None:
+            err = CkError("libck_hip error %d: bad mog2 handle %d" % (CK_ERR_ARG, int(handle)))
+            err.code = CK_ERR_ARG
+            raise err
+        return st
+
     def mog2_apply(self, handle, img3, learning_rate):
-        p, sp, keep = self._in(img3)
+        h, w = self._mog2_hw(handle)
+        if _batch_of(img3, (h, w, 3), "img3") != 1:
+            raise CkError("img3: one image of the model's %dx%d is needed, got %r" % (w, h, tuple(img3.shape)))
+        p, sp, keep = self._in(img3, what="img3")
         fg, fp_, osp = self._out(img3, tuple(img3.shape[:-1]), np.uint8)
-        self._chk(lib().ck_mog2_apply(self._h, int(handle), p, sp, C.c_double(learning_rate), fp_, osp))
+        self._chk(lib().ck_mog2_apply(self._h, int(handle), p, sp, learning_rate, fp_, osp))
         return fg
 
     def mog2_state(self, handle):
         """the model's mixture on the host: dict(weight (5, npx) f32, variance (5, npx) f32, mean (5, 3, npx) f32,
         nmodes (npx,) u8), npx = h * w; slots k >= nmodes[px] are unspecified"""
-        st = self._mog2_shape.get(int(handle))
-        if st is None:
-            raise CkError("bad mog2 handle %d" % int(handle))
+        st = self._mog2_hw(handle)
         npx = st[0] * st[1]
         out = dict(weight=np.empty((5, npx), np.float32), variance=np.empty((5, npx), np.float32),
                    mean=np.empty((5, 3, npx), np.float32), nmodes=np.empty(npx, np.uint8))
@@ -611,28 +595,14 @@ class Context:
     # ---- K10..K12 ----------------------------------------------------------------------------
     def cnn_set_weights(self, weights):
         """weights: dict name -> float32 array (numpy, or torch tensors all on cuda / all on cpu)."""
-        ptrs = (C.c_void_p * 12)()
-        keep, space = [], None
-        for i, k in enumerate(WEIGHT_ORDER):
-            a = weights[k]
-            assert tuple(a.shape) == WEIGHT_SHAPES[k], (k, tuple(a.shape))
-            if _is_torch(a):
-                import torch
-                assert a.dtype == torch.float32
-            p, sp, ka = self._in(a, np.float32)
-            assert space in (None, sp), "weights must live in one memory space"
-            space = sp
-            ptrs[i] = p
-            keep.append(ka)
+        ptrs, space, keep = self._weight_ptrs(weights, "weights")
         self._chk(lib().ck_cnn_set_weights(self._h, ptrs, space))
 
     def cnn_set_mode(self, mode):
         self._chk(lib().ck_cnn_set_mode(self._h, int(mode)))
 
     def cnn_predict(self, goban, want_y=True):
-        shp = tuple(goban.shape)
-        n = 1 if len(shp) == 3 else shp[0]
-        p, sp, keep = self._in(goban)
+        n, p, sp, keep = self._goban(goban)
         y, yp = None, None
         if want_y:
             y, yp, _ = self._out(goban, (n, 100, 81), np.float32)
@@ -645,9 +615,7 @@ class Context:
         """the classifier's pooled filter maps as the context's mode computes them (host float32, channels-last):
         (pool2 (n, 100, 16, 16, 32), pool4 (n, 100, 6, 6, 90)) -- the outputs of the two MaxPooling2D layers of
         create_net (stone/nn_manager.py:280-292); n <= 128"""
-        shp = tuple(goban.shape)
-        n = 1 if len(shp) == 3 else shp[0]
-        p, sp, keep = self._in(goban)
+        n, p, sp, keep = self._goban(goban)
         p2 = np.empty((n, 100, 16, 16, 32), np.float32)
         p4 = np.empty((n, 100, 6, 6, 90), np.float32)
         self._chk(lib().ck_cnn_maps(self._h, p, n, sp, p2.ctypes.data_as(C.c_void_p), p4.ctypes.data_as(C.c_void_p)))
@@ -655,15 +623,14 @@ class Context:
 
     # ---- training of the classifier (k_cnn_train.hip) -----------------------------------------
     def _weight_ptrs(self, arrays, what):
-        """12 float32 arrays under the WEIGHT_ORDER names -> (pointer table, memory space, keepalive)"""
+        """12 float32 arrays under the WEIGHT_ORDER names -> (pointer table, memory space, keepalive).  Host arrays of another
+        element type are cast; a device tensor has to be float32 (CkError)"""
         ptrs, keep, space = (C.c_void_p * 12)(), [], None
         for i, k in enumerate(WEIGHT_ORDER):
             a = arrays[k]
             if tuple(a.shape) != WEIGHT_SHAPES[k]:
                 raise ValueError("%s %s: shape %r, expected %r" % (what, k, tuple(a.shape), WEIGHT_SHAPES[k]))
-            if _is_torch(a) and "float32" not in str(a.dtype):
-                a = a.float()
-            p, sp, ka = self._in(a.contiguous() if _is_torch(a) else a, np.float32)
+            p, sp, ka = self._in(a.contiguous() if _is_torch(a) else a, np.float32, what="%s %s" % (what, k))
             if space not in (None, sp):
                 raise ValueError("%s must live in one memory space" % what)
             space, ptrs[i] = sp, p
@@ -707,7 +674,7 @@ class Context:
         raw BGR patches, host or device; labels: n class indices 0..80 (or one-hot rows)"""
         p, sp, n, h, w, c, lp, keep = self._train_batch(x, labels)
         loss = C.c_float(0)
-        self._chk(lib().ck_train_step(self._h, int(handle), p, lp, n, h, w, c, sp, float(lr), int(bool(dropout)),
+        self._chk(lib().ck_train_step(self._h, int(handle), p, lp, n, h, w, c, sp, lr, int(bool(dropout)),
                                       int(seed) & 0xffffffffffffffff, C.byref(loss)))
         return float(loss.value)
 
@@ -729,7 +696,7 @@ class Context:
         """one Adam update from 12 given gradient arrays (host)"""
         host = {k: (grads[k].detach().cpu().numpy() if _is_torch(grads[k]) else grads[k]) for k in WEIGHT_ORDER}
         ptrs, space, keep = self._weight_ptrs(host, "gradients")
-        self._chk(lib().ck_train_apply(self._h, int(handle), ptrs, float(lr)))
+        self._chk(lib().ck_train_apply(self._h, int(handle), ptrs, lr))
 
     def train_weights(self, handle):
         out, ptrs = self._weight_outs()
@@ -774,8 +741,8 @@ class Context:
         x, xp, osp = self._out(goban, (room, 40, 40, 3), np.uint8)
         lab, lp, _ = self._out(goban, (room,), np.uint8)
         src, sp_, _ = self._out(goban, (room, 2), np.int32)
-        p, sp, keep = self._in(goban)
-        fp, fsp, fkeep = self._in(fgcount, np.int32)
+        p, sp, keep = self._in(goban, what="goban")
+        fp, fsp, fkeep = self._in(fgcount, np.int32, what="fgcount")
         found = C.c_int32(0)
         self._chk(lib().ck_harvest_patches(self._h, p, n, sp, fp, fsp, state.ctypes.data_as(C.c_void_p),
                                            pos.ctypes.data_as(C.c_void_p), len(pos), int(calm_max), int(empty_keep),
@@ -799,17 +766,10 @@ class Context:
         codes = np.ascontiguousarray(np.where((t < 0) | (t > 255), 255, t), np.uint8)       # out of range: the library says so
         if _is_torch(x):
             x = x.contiguous()
-        if out is not None:
-            if tuple(out.shape) != shp:
-                raise ValueError("out %r for patches %r" % (tuple(out.shape), shp))
-            assert out.is_contiguous() if _is_torch(out) else (out.dtype == np.uint8 and out.flags.c_contiguous)
-            op, osp, _ = self._in(out)
-            res = out
-        elif to_device is not None:
-            res, op, osp = self._out_on(to_device, shp, np.uint8)
-        else:
-            res, op, osp = self._out(x, shp, np.uint8)
-        p, sp, keep = self._in(x)
+        if out is not None and tuple(out.shape) != shp:
+            raise ValueError("out %r for patches %r" % (tuple(out.shape), shp))
+        res, op, osp = self._out(x, shp, np.uint8, out, to_device)
+        p, sp, keep = self._in(x, what="x")
         self._chk(lib().ck_augment_patches(self._h, p, n, sp, codes.ctypes.data_as(C.c_void_p), op, osp))
         return res
 
@@ -825,9 +785,7 @@ class Context:
     # ---- ordered stones path (feeds PolicyCore) ---------------------------------------------------
     def cnn_regions(self, goban):
         """-> (region_label (n, 10, 10) uint8, region_conf (n, 10, 10) float64)"""
-        shp = tuple(goban.shape)
-        n = 1 if len(shp) == 3 else shp[0]
-        p, sp, keep = self._in(goban)
+        n, p, sp, keep = self._goban(goban)
         rl, rlp, osp = self._out(goban, (n, 10, 10), np.uint8)
         rc, rcp, _ = self._out(goban, (n, 10, 10), np.float64)
         self._chk(lib().ck_cnn_regions(self._h, p, n, sp, rlp, rcp, osp))
@@ -856,10 +814,11 @@ class Context:
 
     def mog2_band_run(self, handle, band, learning_rates, last_band):
         """band (n, band_h, 380, 3) of consecutive goban images -> int32 (n, zone rows, 19) foreground counts"""
-        n, bh = int(band.shape[0]), int(band.shape[1])
-        p, sp, keep = self._in(band)
+        h, w = self._mog2_hw(handle)                 # (the library reads n bands of the MODEL's size and writes its zone rows)
+        n = int(band.shape[0])
+        p, sp, keep = self._in(band, np.uint8, (n, h, w, 3), "band")
         lr = np.ascontiguousarray(learning_rates, np.float64).reshape(n)
-        out, op, osp = self._out(band, (n, (bh + 19) // 20, 19), np.int32)
+        out, op, osp = self._out(band, (n, (h + 19) // 20, 19), np.int32)
         self._chk(lib().ck_mog2_band_run(self._h, int(handle), p, n, sp, lr.ctypes.data_as(C.c_void_p), int(bool(last_band)),
                                          op, osp))
         return out
@@ -867,8 +826,8 @@ class Context:
     def zone_counts(self, mask):
         """(n, 380, 380) or (380, 380) mask -> int32 (n, 19, 19) / (19, 19) foreground pixels per intersection zone"""
         single = len(mask.shape) == 2
-        n = 1 if single else int(mask.shape[0])
-        p, sp, keep = self._in(mask)
+        n = _batch_of(mask, (380, 380), "mask")
+        p, sp, keep = self._in(mask, what="mask")
         out, op, osp = self._out(mask, (19, 19) if single else (n, 19, 19), np.int32)
         self._chk(lib().ck_zone_counts(self._h, p, n, sp, op, osp))
         return out
@@ -966,7 +925,7 @@ class Context:
 
     @rng_state.setter
     def rng_state(self, state):
-        self._chk(lib().ck_rng_set(self._h, C.c_uint64(int(state) & 0xffffffffffffffff)))
+        self._chk(lib().ck_rng_set(self._h, int(state) & 0xffffffffffffffff))
 
     def contours_external(self, edges, want_points=False):
         """cv2.findContours(edges, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) as SfContours reads it: for one (h, w) edge map or a
@@ -1035,20 +994,6 @@ def jpeg_blocks(h, w, sampling):
         raise CkError("bad JPEG geometry %dx%d sampling %r" % (w, h, sampling))
     hs, vs = (2 if sampling >= CK_JPEG_422 else 1), (2 if sampling == CK_JPEG_420 else 1)
     return -(-w // (8 * hs)) * -(-h // (8 * vs)) * (hs * vs + (0 if sampling == CK_JPEG_GREY else 2))
-
-
-def _check_array(a, shape, dtypes, what):
-    """a numpy array or torch tensor the library reads or writes in place: shape, element type, contiguity -- else CkError"""
-    dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
-    if _is_torch(a):
-        name, contiguous = str(a.dtype).replace("torch.", ""), a.is_contiguous()
-    elif isinstance(a, np.ndarray):
-        name, contiguous = a.dtype.name, a.flags.c_contiguous
-    else:
-        raise CkError("%s: a numpy array or a torch tensor is needed, got %s" % (what, type(a).__name__))
-    if tuple(a.shape) != tuple(shape) or name not in [np.dtype(d).name for d in dtypes] or not contiguous:
-        raise CkError("%s: a contiguous %s array of shape %r is needed, got %s %r" % (
-            what, "/".join(np.dtype(d).name for d in dtypes), tuple(shape), name, tuple(a.shape)))
 
 
 def _jpeg_streams(streams):
@@ -1229,6 +1174,15 @@ def ordered_hull(points):
     return [(int(x), int(y)) for x, y in out[:n.value]]
 
 
+def _gathered(recs, order):
+    """the records a fold reads where they lie, frame f at recs[order[f]] (or recs[f]) -> the number of frames"""
+    _check_array(recs, None, REC_DTYPE, "records")
+    if order is None:
+        return len(recs)
+    _check_array(order, None, np.int32, "order")
+    return len(order)
+
+
 class BoardFoldCore:
     """ck_boardfold: the ordered half of the automatic board finder (host only, no GPU needed)."""
 
@@ -1272,11 +1226,7 @@ class BoardFoldCore:
         """ck_boardfold_run over the REC_DTYPE array `recs` (frame f at recs[order[f]], or recs[f]) from frame k ->
         (k, counter, hold, seen, looked, found, update, centers, stats): stops after the first frame that changes the corners
         (with hold_after_same_hit < 0: after every hit), or at the end of the batch"""
-        assert recs.dtype == REC_DTYPE and recs.flags.c_contiguous
-        n = len(recs)
-        if order is not None:
-            assert order.dtype == np.int32 and order.flags.c_contiguous
-            n = len(order)
+        n = _gathered(recs, order)
         hull = None if cur_hull is None else np.ascontiguousarray(cur_hull, np.int32).reshape(8)
         io32, io64 = self._io32, self._io64
         io32[:] = (k, hold)
@@ -1327,14 +1277,13 @@ class PolicyCore:
         then ignored: ck_policy_run_records, no copy of the two strided fields), frame f at records[order[f]] when `order`
         (int32) is given"""
         if records is not None:
-            assert records.dtype == REC_DTYPE and records.flags.c_contiguous
-            assert order is None or (order.dtype == np.int32 and order.flags.c_contiguous)
-            n = len(records) if order is None else len(order)
+            n = _gathered(records, order)
         else:
             rl = np.ascontiguousarray(region_label, np.uint8).reshape(-1, 100)
             rc = np.ascontiguousarray(region_conf, np.float64).reshape(-1, 100)
             n = len(rl)
-            assert len(rc) == n
+            if len(rc) != n:
+                raise CkError("region_conf of %d frames for region_label of %d" % (len(rc), n))
         fg = None
         if fgcount is not None:
             fg = np.ascontiguousarray(fgcount, np.int32).reshape(n, 361)
@@ -1374,7 +1323,7 @@ class PolicyCore:
 
     def watch(self, r, c, color, confidence=0.0, stamp=0):
         """start (or with color 0: drop) the watch on a prediction, as a fresh HeatPoint would"""
-        if lib().ck_policy_watch(self._h, int(r), int(c), int(color), float(confidence), int(stamp)) != 0:
+        if lib().ck_policy_watch(self._h, int(r), int(c), int(color), confidence, int(stamp)) != 0:
             raise CkError("ck_policy_watch: bad arguments")
 
 

@@ -24,6 +24,51 @@ def test_header_symbols_are_exported():
     assert sorted(capi.EXPORTS) == names
 
 
+def _declared_params():
+    """name -> number of parameters, by this file's own reading of the header"""
+    src = open(os.path.join(ROOT, "include", "camkifu_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(ck_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)}
+
+
+def test_every_export_is_called_with_the_types_the_header_declares():
+    """capi.lib() reads the signatures from the header: no export is left to ctypes' defaults (an int for everything, which
+    cuts a pointer passed as a Python int to 32 bits and cannot pass a double)"""
+    from camkifu_amd import capi
+    capi.build()
+    L = capi.lib()
+    counts = _declared_params()
+    assert sorted(counts) == _declared()
+    for name, n in counts.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+    c = ctypes
+    assert L.ck_mog2_apply.argtypes[4] is c.c_double
+    assert L.ck_jpeg_probe.argtypes[1] is c.c_size_t
+    assert L.ck_rng_set.argtypes[1] is c.c_uint64
+    assert tuple(L.ck_policy_watch.argtypes[4:6]) == (c.c_double, c.c_longlong)
+    harvest = list(L.ck_harvest_patches.argtypes)
+    assert harvest.count(c.c_uint32) == 1 and harvest.count(c.c_longlong) == 1
+    assert L.ck_round10.restype is c.c_double
+    assert L.ck_last_error.restype is c.c_char_p
+    assert L.ck_stream.restype is c.c_void_p
+    assert L.ck_ctx_destroy.restype is None
+    assert L.ck_version.restype is c.c_int and len(L.ck_version.argtypes) == 0
+
+
+def test_a_prototype_the_parser_cannot_map_is_an_error(tmp_path):
+    from camkifu_amd import capi
+    import pytest
+    h = tmp_path / "odd.h"
+    h.write_text("int ck_fine(int a, const float* b);\nint ck_odd(int a, float scale);\n")
+    with pytest.raises(capi.CkError, match="ck_odd.*float scale"):
+        capi._signatures(str(h))
+    h.write_text("float ck_odd(int a);\n")
+    with pytest.raises(capi.CkError, match="ck_odd.*float"):
+        capi._signatures(str(h))
+
+
 def test_header_constants_equal_the_python_side():
     """the enums of include/camkifu_amd.h (status codes, memory spaces, classifier modes) and their mirrors in capi.py"""
     from camkifu_amd import capi

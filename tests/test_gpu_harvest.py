@@ -248,6 +248,8 @@ def test_augment_against_numpy(ck):
     assert out.is_cuda and np.array_equal(out.cpu().numpy(), ref)
     into = np.zeros_like(x)
     assert ck.augment_patches(tx, t, out=into) is into and np.array_equal(into, ref)
+    into = torch.zeros_like(tx)
+    assert ck.augment_patches(tx, t, out=into) is into and np.array_equal(into.cpu().numpy(), ref)
     assert np.array_equal(ck.augment_patches(x[:1], [6]), hr.augment_ref(x[:1], [6]))
     assert ck.augment_patches(x[:0], []).shape == (0, 40, 40, 3)
 

@@ -43,6 +43,8 @@ def test_the_batch_of_five_decodes_in_one_call(ck):
     assert dev.is_cuda and np.array_equal(dev.cpu().numpy(), exp)
     out = np.zeros_like(exp)
     assert ck.jpeg_decode([np.frombuffer(s, np.uint8) for s in streams], out=out) is out and np.array_equal(out, exp)
+    out = torch.zeros_like(dev)
+    assert ck.jpeg_decode(streams, out=out) is out and np.array_equal(out.cpu().numpy(), exp)
     ck.timing_enable(True)
     ck.timing_reset()
     ck.jpeg_decode(streams)

@@ -80,6 +80,8 @@ def test_forward_of_a_batch_from_host_memory_and_from_hbm(ck, s):
     # into a preallocated output
     out = np.empty_like(exp)
     assert ck.jpeg_forward(frames, q, s, out=out) is out and np.array_equal(out, exp)
+    out = torch.zeros_like(d)
+    assert ck.jpeg_forward(torch.from_numpy(frames).to(dev), q, s, out=out) is out and np.array_equal(out.cpu().numpy(), exp)
 
 
 def test_a_batch_equals_per_frame_calls(ck):

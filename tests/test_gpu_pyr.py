@@ -49,6 +49,8 @@ def test_pyr_down_equals_the_reference(ck, case):
     assert np.array_equal(ck.pyr_down(img, levels), want), "after a call of another size"
     out = np.empty_like(want)
     assert ck.pyr_down(img, levels, out=out) is out and np.array_equal(out, want)
+    out = _dev(np.zeros_like(want))
+    assert ck.pyr_down(_dev(img), levels, out=out) is out and np.array_equal(out.cpu().numpy(), want)
 
 
 def test_pyr_down_of_an_offset_device_pointer(ck):

@@ -12,61 +12,13 @@ import numpy as np
 import pytest
 
 from camkifu_amd import capi, pipeline
-
-
-class _FakeStream:
-    def __init__(self, log, handle=0x5157):
-        self.log, self.cuda_stream = log, handle
-
-    def synchronize(self):
-        self.log.append("stream.synchronize")
-
-
-class _FakeTensor:
-    is_cuda, device = True, "cuda:0"
-    __module__ = "torch"
-
-    def __init__(self, log, shape=(2, 4, 4, 3), name="tensor"):
-        self.log, self.shape, self.name = log, shape, name
-
-    def is_contiguous(self):
-        return True
-
-    def data_ptr(self):
-        return 0x1000
-
-    def __del__(self):
-        self.log.append("free " + self.name)
-
-
-_FakeTensor.__module__ = "torch"
-
-
-class _FakeLib:
-    def __init__(self, log, destroy_rc=0):
-        self.log, self.destroy_rc = log, destroy_rc
-
-    def ck_stream_wait(self, h, stream):
-        self.log.append("ck_stream_wait(0x%x)" % stream.value)
-        return 0
-
-    def ck_ctx_destroy2(self, h):
-        self.log.append("ck_ctx_destroy2")
-        return self.destroy_rc
-
-    def ck_last_error(self, h):
-        return b""
+from tests.capi_fakes import FakeLib as _FakeLib, FakeStream as _FakeStream, FakeTensor as _FakeTensor, stub_context
 
 
 @pytest.fixture
 def stub(monkeypatch):
-    import torch
     log = []
-    monkeypatch.setattr(capi, "lib", lambda: _FakeLib(log))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: _FakeStream(log))
-    monkeypatch.setattr(torch, "empty", lambda shape, dtype=None, device=None: (log.append("torch.empty"), _FakeTensor(log, shape, "output"))[1])
-    ctx = capi.Context.__new__(capi.Context)
-    ctx._h, ctx.device = C.c_void_p(1), 0
+    ctx, lib = stub_context(monkeypatch, log)
     yield ctx, log
     ctx._h = C.c_void_p()
 

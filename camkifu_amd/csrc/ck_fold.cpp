@@ -390,7 +390,7 @@ int ck_boardfold_run(ck_boardfold* bf, int h, int w, const ck_frame_record* recs
         const ck_frame_record& r = recs[order ? order[k] : k];
         const int kept = std::max(0, std::min(r.n_lines, (int32_t)CK_REC_LMAX));
         seen_looked_io[0]++; seen_looked_io[1]++;
-        *k_io = k;                                           // (where an error leaves the fold: this frame is not counted)
+        *k_io = k;                                           // (where an error leaves the fold: seen / looked hold this frame, the counter does not)
         const int rc = ck_boardfold_step(bf, h, w, r.status, &r.lines[0][0], kept, *counter_io, cur_hull, found, update,
                                          centers, n_centers, stats);
         if (rc != CK_OK) return rc;

@@ -25,6 +25,8 @@ A failed batch (finish() raises on every rank) leaves a gap: the board fold on r
 records are missing as frames without a contour, so the running frame count -- which places the every-4th-frame grouping
 and, in hold-off-aware mode, every rank's plan of the next batch -- stays that of the film."""
 import os
+import time
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -290,7 +292,6 @@ class _Group:
 def rccl_group_options():
     """What a host passes as `pg_options=` to `init_process_group("nccl", ...)` for the group it hands to
     FastFilePipeline: the communicator's own stream at high priority, like the exchange thread's (see _exchange)."""
-    import os
     import torch.distributed as dist
     opts = dist.ProcessGroupNCCL.Options()
     opts.is_high_priority_stream = os.environ.get("CK_EXCHANGE_PRIORITY") != "0"
@@ -770,6 +771,41 @@ class _Ticket:
         self.have_mtx = mtx is not None
 
 
+class Wire:
+    """What rank 0 broadcasts to keep the ranks in step: SIZE doubles, in the hold-off-aware rounds followed by room for
+    a batch's frame numbers (`room` = the batch size, the same on every rank).  [0] the kind, one of the five below (a kind
+    below zero ends the batch on every rank); [1:10] TRANSFORM: the 3 x 3 transform, row by row -- REQUEST: [1] = how many
+    frames are asked for; [10:14] BoardFold.state() after the batch (every kind but REQUEST); [14:16] unused; [16:] REQUEST:
+    the frames asked for."""
+    SIZE = 16
+    CORE_FAILED, FOLD_FAILED, NO_TRANSFORM, TRANSFORM, REQUEST = -2.0, -1.0, 0.0, 1.0, 2.0
+
+    @staticmethod
+    def outcome(state, mtx=None, failed=None, room=0):
+        """a batch's outcome: `failed` (CORE_FAILED / FOLD_FAILED), else the transform or its absence"""
+        wire = np.zeros(Wire.SIZE + room)
+        wire[0] = failed if failed is not None else (Wire.NO_TRANSFORM if mtx is None else Wire.TRANSFORM)
+        if wire[0] == Wire.TRANSFORM:
+            wire[1:10] = np.asarray(mtx, np.float64).reshape(9)
+        wire[10:14] = state
+        return wire
+
+    @staticmethod
+    def request(idx, room):
+        wire = np.zeros(Wire.SIZE + room)
+        wire[0], wire[1], wire[Wire.SIZE:Wire.SIZE + len(idx)] = Wire.REQUEST, len(idx), idx
+        return wire
+
+    @staticmethod
+    def read(wire):
+        """-> (kind, transform or None, fold state or None, requested frames or None)"""
+        kind = float(wire[0])
+        if kind == Wire.REQUEST:
+            return kind, None, None, [int(f) for f in wire[Wire.SIZE:Wire.SIZE + int(wire[1])]]
+        mtx = wire[1:10].reshape(3, 3).copy() if kind == Wire.TRANSFORM else None
+        return kind, mtx, tuple(int(v) for v in wire[10:14]), None
+
+
 class FastFilePipeline:
     """process_batch(my_frames, n_total): this rank's shard of a batch -> (on rank 0) the requests the fold emitted.
 
@@ -843,13 +879,14 @@ class FastFilePipeline:
                                  gather=0.0, bcast=0.0, band_exchange=0.0, counts_gather=0.0, flags=0.0, unpack=0.0)
         # hold-off-aware mode: the GPU core leaves the board path out and the board fold computes, through the lanes' board
         # contexts (on their own threads), only the records it looks at.  One rank: the fold runs on a thread of its own and
-        # asks as it goes (_lazy_fold).  Frames dealt across ranks: every rank works out the batch's first request from the
-        # fold's state, which travels with the transform broadcast, and computes the planned frames it owns; the records are
-        # gathered, rank 0 folds, and every deviation costs one more (broadcast, gather) round (_lazy_board_exchange).
+        # asks as it goes (_lazy_fold).  Frames dealt across ranks: rounds of (broadcast, gather), see _lazy_board_exchange.
         self._board_state = (0, 0, 0, 0)                      # BoardFold.state() at the start of the next batch, on every rank
         if board_lazy and not hasattr(self.compute, "lanes"):
             raise ValueError("board_lazy needs a GPU core with lanes (their board contexts compute the requested records)")
         self.board_lazy = bool(board_lazy)
+        # how `compute` is called, decided once: a core that deals tickets also takes the batch's turn (and board=False in
+        # hold-off-aware mode); a plain callable (the CPU tests' stand-ins) takes the three arguments only
+        self._ticketed, self._core_kw = hasattr(compute, "ticket"), (dict(board=False) if self.board_lazy else {})
 
     # ---- pixel-sharded background model (world > 1) -------------------------------------------------------
     def _band_counts(self, gobans, n_total, rates):
@@ -857,9 +894,18 @@ class FastFilePipeline:
         (n_total, band rows, 19) int32, left where the model put them (HBM with real contexts: they are gathered from there).
         Stream-ordered: the scatter into frame order is queued behind the collective on this thread's torch stream and the
         model's context is ordered behind that stream when it takes the tensor (capi.Context._in) -- no host wait."""
-        import time
+        with self._clock("band_exchange"):
+            full = self._band_of_every_frame(gobans, n_total)
+        with self._clock("band_model"):
+            counts = self._band_model()(full, rates)
+        a, b = self.band
+        if hasattr(counts, "reshape") and hasattr(counts, "is_cuda"):
+            return counts.reshape(n_total, b - a, gsize).int()
+        return np.asarray(counts).astype(np.int32).reshape(n_total, b - a, gsize)
+
+    def _band_of_every_frame(self, gobans, n_total):
+        """the all-to-all of _band_counts -> this rank's band of the batch's goban images (n_total, rows, 380, 3) in frame order"""
         import torch
-        t0 = time.perf_counter()
         bands = band_rows(self.world)
         px = [(20 * a, min(20 * b, 380)) for a, b in bands]
         if gobans is None:
@@ -893,15 +939,7 @@ class FastFilePipeline:
             full = torch.empty((n_total, hi - lo, 380, 3), dtype=torch.uint8, device=parts[0].device)
             for src, part in enumerate(parts):                    # frame f of the batch came from rank f mod world
                 full[src::self.world] = part.reshape(-1, hi - lo, 380, 3)
-        t1 = time.perf_counter()
-        counts = self._band_model()(full, rates)
-        t2 = time.perf_counter()
-        self.host_seconds["band_exchange"] += t1 - t0
-        self.host_seconds["band_model"] += t2 - t1
-        rows = bands[self.rank][1] - bands[self.rank][0]
-        if hasattr(counts, "reshape") and hasattr(counts, "is_cuda"):
-            return counts.reshape(n_total, rows, gsize).to(torch.int32)
-        return np.asarray(counts).astype(np.int32).reshape(n_total, rows, gsize)
+        return full
 
     def _band_model(self):
         """this rank's band of the background model on ITS OWN context: a lane's context belongs to that lane's thread,
@@ -923,30 +961,33 @@ class FastFilePipeline:
         return self.band_model
 
     # ---- one batch --------------------------------------------------------------------------------------
+    @contextmanager
+    def _clock(self, key):
+        """the one way host time is booked: what the block took is added to host_seconds[key]"""
+        t0 = time.perf_counter()
+        try:
+            yield
+        finally:
+            self.host_seconds[key] = self.host_seconds.get(key, 0.0) + time.perf_counter() - t0
+
     def _as_shard(self, out, n_mine):
         """what a GPU core returns -> (record buffer, counts, gobans).  The built-in core hands over the buffer the library
         wrote; a `compute` of the old form (board, region_label, region_conf, counts, gobans) -- the stand-ins of the CPU
         tests -- is packed here"""
         if len(out) == 3:
             return out
-        import time
-        t0 = time.perf_counter()
-        board, rl, rc, fg, gobans = out
-        recs = shard_buffer(n_mine)
-        packed = pack_records(board, rl, rc)
-        if len(packed) != n_mine:
-            raise RuntimeError("the GPU core handed back %d records for a shard of %d frames" % (len(packed), n_mine))
-        recs[1:1 + n_mine] = packed
-        self.host_seconds["pack"] += time.perf_counter() - t0
+        with self._clock("pack"):
+            board, rl, rc, fg, gobans = out
+            recs = shard_buffer(n_mine)
+            packed = pack_records(board, rl, rc)
+            if len(packed) != n_mine:
+                raise RuntimeError("the GPU core handed back %d records for a shard of %d frames" % (len(packed), n_mine))
+            recs[1:1 + n_mine] = packed
         return recs, fg, gobans
 
-    def _guarded(self, frames, mtx, rates, n_mine, seq):
+    def _guarded(self, frames, mtx, rates, n_mine, *turn):
         try:
-            if self.board_lazy:
-                return self._as_shard(self.compute(frames, mtx, rates, seq, board=False), n_mine), None
-            if seq is not None:
-                return self._as_shard(self.compute(frames, mtx, rates, seq), n_mine), None
-            return self._as_shard(self.compute(frames, mtx, rates), n_mine), None
+            return self._as_shard(self.compute(frames, mtx, rates, *turn, **self._core_kw), n_mine), None
         except Exception as why:                              # never leave the other ranks alone in a collective
             return (shard_buffer(n_mine), None, None), why    # (host memory: the GPU may be what failed)
 
@@ -958,13 +999,12 @@ class FastFilePipeline:
             self.stone_frames += n_total
         mine = shard_indices(n_total, self.rank, self.world)
         rates_for_core = rates if not self.exchange else rates[mine]
-        seq = self.compute.ticket() if hasattr(self.compute, "ticket") else None
-        t = _Ticket(self._runner.submit(self._guarded, my_frames, mtx, rates_for_core, len(mine), seq), mtx, rates, n_total, my_frames)
+        turn = (self.compute.ticket(),) if self._ticketed else ()
+        t = _Ticket(self._runner.submit(self._guarded, my_frames, mtx, rates_for_core, len(mine), *turn), mtx, rates, n_total, my_frames)
         if self.board_lazy and self.rank == 0 and not self.exchange:
-            # hold-off-aware mode: the board fold needs nothing of the GPU core's results -- it asks the lanes' BOARD contexts
-            # (idle in this mode) for the few records it looks at, a chain of small round trips that depends only on the
-            # fold before it.  It runs on a thread of its own, batch after batch, as far ahead of the cores as the batches
-            # in flight allow.
+            # hold-off-aware mode: the board fold needs nothing of the GPU core's results -- a chain of small round trips to
+            # the lanes' BOARD contexts (idle in this mode) that depends only on the fold before it.  It runs on a thread of
+            # its own, batch after batch, as far ahead of the cores as the batches in flight allow.
             if self._board_thread is None:
                 self._board_thread = _pool(1, self.gpu)
             t.lazy_fold = self._board_thread.submit(self._lazy_fold, t)
@@ -972,19 +1012,12 @@ class FastFilePipeline:
         return t
 
     def _lazy_fold(self, t):
-        import time
-        t0 = time.perf_counter()
-        try:
+        with self._clock("fold_board"):
             self._fold_board(np.zeros(t.n_total, REC), t.frames, t.keep)
-            return self.board.mtx, None
-        except Exception as why:
-            return None, why
-        finally:
-            self.host_seconds["fold_board"] += time.perf_counter() - t0
+            return self.board.mtx
 
     def _exchange(self, t):
         """stage 2 on this rank's exchange thread, with that thread's own torch stream current (see __init__)"""
-        import os
         if self.gpu is None or not self.exchange or os.environ.get("CK_EXCHANGE_DEFAULT_STREAM"):   # (developer A/B knob)
             return self._exchange_on_stream(t)
         import torch
@@ -1012,181 +1045,173 @@ class FastFilePipeline:
                 recs[0, FLAGS_AT] = FLAG_FAILED               # (little-endian int32, the flag fits its first byte)
         return recs[:rows]
 
-    def _fold_gap(self, n):
-        """rank 0, a batch whose records never arrived: the board fold advances over its frames as frames without a contour
+    def _fold_gap(self, n, lazy=False):
+        """rank 0, n frames whose records never arrived: the board fold advances over them as frames without a contour
         (no detection can come of them), so the running count stays the film's"""
-        blank = np.zeros(n, REC)
-        blank["status"] = capi.CK_BOARD_NO_CONTOUR
+        def blank(idx):
+            rows = np.zeros(len(idx), REC)
+            rows["status"] = capi.CK_BOARD_NO_CONTOUR
+            return rows, rows["lines"]
         try:
-            self.board.run(blank)
+            self.board.run_lazy(n, blank, plan_ahead=True) if lazy else self.board.run(blank(range(n))[0])
         except Exception as why:
             self.errors.append(why)
 
     def _exchange_on_stream(self, t):
         """-> (records of the whole batch in frame order -- rank 0 only, None elsewhere --, foreground counts (rank 0) or None,
-        transform after this batch, failure seen by any rank).
-
-        Collectives of a batch, the same on every rank in the same order: gather of the record buffers to rank 0 ->
-        broadcast of the wire (outcome, transform, fold state: 16 doubles) -> all-to-all of goban bands -> one-word
-        all-reduce (did a band of the background model fail?) -> gather of the counts to rank 0.  Ranks != 0 bring the
-        wire and the flag word to the host, nothing else."""
-        import time
-        hs = self.host_seconds
-        lazy_x = None
-        if self.board_lazy and self.exchange:
-            # hold-off-aware board path across ranks: its rounds and the transform broadcast come FIRST -- they need nothing
-            # of this batch's GPU core (the board contexts are idle in this mode), so they run under the stones path
-            lazy_x = self._lazy_board_exchange(t)
+        transform after this batch, failure seen by any rank).  Collectives of a batch, the same on every rank in the same
+        order: gather of the record buffers to rank 0 -> broadcast of the wire (outcome, transform, fold state: see Wire) ->
+        all-to-all of goban bands -> one-word all-reduce (did a band of the background model fail?) -> gather of the counts
+        to rank 0.  Ranks != 0 bring the wire and the flag word to the host, nothing else."""
+        # hold-off-aware across ranks: the board rounds come FIRST -- they need nothing of this batch's GPU core, so they run under it
+        lazy_x = self._lazy_board_exchange(t) if self.board_lazy and self.exchange else None
         (recs, fg, gobans), failure = t.core.result()
-        lazy_fold = t.lazy_fold.result() if t.lazy_fold is not None else None
         if failure is not None:
             self.errors.append(failure)
         if lazy_x is not None and lazy_x[1]:                   # the board path failed somewhere: every rank leaves here,
             return None, None, self.mtx, True                  # before the records gather
-        n_total, W = t.n_total, self.world
         if not self.exchange:
-            if failure is not None:
-                if lazy_fold is None:
-                    self._fold_gap(n_total)
-                return None, None, self.board.mtx, True
-            full = records_view(recs)[1:1 + n_total]
-            t3 = time.perf_counter()
-            if lazy_fold is not None:
-                new, fold_error = lazy_fold
-                if fold_error is not None:
-                    raise fold_error
+            return self._fold_here(t, recs, fg, failure)
+        full, wire = self._records_to_rank0(t, recs, failure, lazy_x)
+        # In hold-off-aware mode too, although transform and state went round already: _lazy_board_exchange knows nothing of
+        # the GPU cores' results, and this wire is how ranks != 0 learn that some rank's core failed (Wire.CORE_FAILED) --
+        # before the band all-to-all, whose sizes a failed rank cannot honour.
+        with self._clock("bcast"):
+            wire = self.group.broadcast_array(wire, 0)
+        kind, new, _, _ = Wire.read(wire)
+        if kind < 0:                                           # every rank leaves the batch here, before the band exchange
+            if self.rank != 0:
+                self.errors.append(RuntimeError("the GPU core of a rank failed" if kind == Wire.CORE_FAILED else "the board fold failed on rank 0"))
+            return full, None, self.mtx, True
+        counts, failed = self._counts_to_rank0(t, gobans) if t.have_mtx else (None, False)
+        return (full, None, self.mtx, True) if failed else (full, counts, new, False)
+
+    def _fold_here(self, t, recs, fg, failure):
+        """one rank, no exchange: the board fold here, or the answer of the fold that ran ahead (_lazy_fold)"""
+        if failure is not None:
+            if t.lazy_fold is None:
+                self._fold_gap(t.n_total)
             else:
-                self._fold_board(full, None)
-                new = self.board.mtx
-            hs["fold_board"] += time.perf_counter() - t3
-            return full, fg, new, False
-        # ---- records to rank 0
-        t1 = time.perf_counter()
-        per = (n_total + W - 1) // W
-        got = self.group.gather_rows(self._wire_rows(recs, per + 1, failure is not None), t.landing)
-        t2 = time.perf_counter()
-        hs["gather"] += t2 - t1
-        wire, full, fold_error = np.zeros(self.WIRE), None, None
-        if self.rank == 0:
+                t.lazy_fold.exception()                        # (only waited for: whatever it did, the batch has failed)
+            return None, None, self.board.mtx, True
+        full = records_view(recs)[1:1 + t.n_total]
+        if t.lazy_fold is not None:
+            return full, fg, t.lazy_fold.result(), False       # (raises what the fold raised)
+        with self._clock("fold_board"):
+            self._fold_board(full, None)
+        return full, fg, self.board.mtx, False
+
+    def _records_to_rank0(self, t, recs, failure, lazy_x):
+        """the records gather and rank 0's decision -> (rank 0: the records where the gather left them, the outcome to broadcast)"""
+        n_total, W = t.n_total, self.world
+        with self._clock("gather"):
+            per = (n_total + W - 1) // W
+            got = self.group.gather_rows(self._wire_rows(recs, per + 1, failure is not None), t.landing)
+        if self.rank != 0:
+            return None, np.zeros(self.WIRE)                   # (what a receiving rank posts)
+        with self._clock("unpack"):
             bad = [int(r) for r in np.nonzero(got[:, 0, FLAGS_AT] & FLAG_FAILED)[0]]
-            if bad:
-                wire[0] = -2.0
-                if failure is None:
-                    self.errors.append(RuntimeError("the GPU core failed on rank(s) %s" % bad))
-                if lazy_x is None:
-                    self._fold_gap(n_total)
-            else:
+            if not bad:
                 # frame f of the batch is row 1 + f // W of rank f mod W: the folds read the records where the gather left them
                 f_all = np.arange(n_total, dtype=np.int32)
                 full = Gathered(got.view(REC).reshape(W * (per + 1)), (f_all % W) * (per + 1) + 1 + f_all // W)
-                t3 = time.perf_counter()
-                hs["unpack"] += t3 - t2
-                # ordered board fold: it needs the records only, so the transform is known -- and on its way to the other
-                # ranks -- before the background model's exchange starts
-                new = None
-                if lazy_x is not None:
-                    new = lazy_x[0]                            # folded (and broadcast) already
-                else:
-                    try:
-                        self._fold_board(full, None)
-                        new = self.board.mtx
-                    except Exception as why:                   # e.g. the IndexError the reference raises on a 3-vertex hull
-                        fold_error = why                       # the other ranks are about to wait in the broadcast: tell them
-                        self.errors.append(why)
-                hs["fold_board"] += time.perf_counter() - t3
-                if fold_error is not None:
-                    wire[0] = -1.0
-                elif new is not None:
-                    wire[0], wire[1:10] = 1.0, np.asarray(new, np.float64).reshape(9)
-            wire[10:14] = self.board.state()
-        t4 = time.perf_counter()
-        wire = self.group.broadcast_array(wire, 0)
-        hs["bcast"] += time.perf_counter() - t4
-        if wire[0] < 0:                                        # every rank leaves the batch here, before the band exchange
-            if self.rank != 0:                                 # whose sizes a failed rank could not honour
-                self.errors.append(RuntimeError("the GPU core of a rank failed" if wire[0] == -2.0 else "the board fold failed on rank 0"))
-            return full, None, self.mtx, True
-        new = wire[1:10].reshape(3, 3).copy() if wire[0] == 1.0 else None
-        counts = None
-        if t.have_mtx:
-            # A rank whose band model fails (a library error, out of memory for the band tensor ...) must not leave the
-            # others waiting: it has joined the all-to-all (with blank bands if need be), the flag word says so to
-            # everyone, and every rank leaves the batch together, before the counts gather.
-            band_error, mine_counts = None, None
-            try:
-                mine_counts = self._band_counts(gobans, n_total, t.rates)                # (n_total, rows, 19) int32
-            except _BandExchangeBroken:
-                raise                                         # could not even join the all-to-all: nothing left to keep in step
-            except Exception as why:
-                band_error = why
-            # the flag word and the counts are queued one behind the other and read with ONE host wait (rank 0: the counts'
-            # copy to the host; the others: the flag); a rank whose band failed contributes zeros nobody will read
-            import torch
-            t5 = time.perf_counter()
+        if bad:
+            if failure is None:
+                self.errors.append(RuntimeError("the GPU core failed on rank(s) %s" % bad))
+            if lazy_x is None:
+                self._fold_gap(n_total)
+            return None, Wire.outcome(self.board.state(), failed=Wire.CORE_FAILED)
+        new, fold_failed = None, None      # the fold needs the records only: the transform is on its way before the bands are
+        with self._clock("fold_board"):
+            if lazy_x is not None:
+                new = lazy_x[0]                                # folded (and broadcast) already
+            else:
+                try:
+                    self._fold_board(full, None)
+                    new = self.board.mtx
+                except Exception as why:                       # e.g. the IndexError the reference raises on a 3-vertex hull
+                    fold_failed = Wire.FOLD_FAILED             # the other ranks are about to wait in the broadcast: tell them
+                    self.errors.append(why)
+        return full, Wire.outcome(self.board.state(), new, fold_failed)
+
+    def _counts_to_rank0(self, t, gobans):
+        """The band model's counts to rank 0 -> (counts (n_total, 19, 19) int32 on rank 0, None elsewhere; failed).
+        A rank whose band model fails (a library error, no memory for the band tensor ...) has still joined the all-to-all
+        (with blank bands if need be); the flag word tells everyone, its zeros go into the gather unread, every rank leaves
+        the batch together.  Flag word and counts are queued one behind the other and read with ONE host wait."""
+        import torch
+        n_total, bands = t.n_total, band_rows(self.world)
+        band_error, mine = None, None
+        try:
+            mine = self._band_counts(gobans, n_total, t.rates)                           # (n_total, rows, 19) int32
+        except _BandExchangeBroken:
+            raise                                             # could not even join the all-to-all: nothing left to keep in step
+        except Exception as why:
+            band_error = why
+        with self._clock("flags"):
             flag = self.group.max_flag_start(self.rank + 1 if band_error is not None else 0)
-            t6 = time.perf_counter()
-            hs["flags"] += t6 - t5
-            bands = band_rows(W)
+        with self._clock("counts_gather"):
             widest = max(b - a for a, b in bands)
-            if mine_counts is None:
-                mine_counts = np.zeros((n_total, bands[self.rank][1] - bands[self.rank][0], gsize), np.int32)
-            src = self.group.on_wire(mine_counts).reshape(-1)
-            slab = src
+            if mine is None:
+                mine = np.zeros((n_total, self.band[1] - self.band[0], gsize), np.int32)
+            src = slab = self.group.on_wire(mine).reshape(-1)
             if src.numel() != n_total * widest * gsize:        # a narrower band: padded to the widest (equal contributions)
                 slab = torch.zeros(n_total * widest * gsize, dtype=torch.int32, device=src.device)
                 slab[:src.numel()] = src
             got = self.group.gather_rows(slab.reshape(1, -1), t.landing)
-            t7 = time.perf_counter()
-            hs["counts_gather"] += t7 - t6
+        with self._clock("flags"):
             bad = self.group.max_flag_read(flag)
-            hs["flags"] += time.perf_counter() - t7
-            if bad:
-                self.errors.append(band_error if band_error is not None
-                                   else RuntimeError("the background model's band failed on rank %d" % (bad - 1)))
-                return full, None, self.mtx, True
-            if self.rank == 0:
-                got = got.view(np.int32).reshape(W, -1)
-                counts = np.concatenate([got[r, :n_total * (b - a) * gsize].reshape(n_total, b - a, gsize)
-                                         for r, (a, b) in enumerate(bands)], 1)
-        return full, counts, new, False
+        if bad:
+            self.errors.append(band_error or RuntimeError("the background model's band failed on rank %d" % (bad - 1)))
+            return None, True
+        if self.rank != 0:
+            return None, False
+        got = got.view(np.int32).reshape(self.world, -1)
+        return np.concatenate([got[r, :n_total * (b - a) * gsize].reshape(n_total, b - a, gsize)
+                               for r, (a, b) in enumerate(bands)], 1), False
 
     # ---- hold-off-aware board path with the frames dealt across ranks ------------------------------------------------
-    WIRE = 16                                                 # doubles in front of a request's frame list: kind, 9 transform / count, 4 state
+    WIRE = Wire.SIZE                                          # doubles in front of a request's frame list
 
     def _detect_frames(self, frames, idx, rows, keep=None):
         """K1-K6 of frames[idx] on the lanes' board contexts, each driven from its own lane thread (a context is
-        single-threaded) -> the board half of the record rows `rows` (len(idx) of them, host memory or HBM), in idx order"""
-        import time
+        single-threaded) -> the board half of the record rows `rows` (len(idx) of them, host memory or HBM), in idx order.
+        The hand-over rule: device memory a lane thread is handed here -- the frames (a slice, or what _take gathered) or
+        the record rows (zero-filled by the caller) -- was produced on the CALLING thread's current torch stream, of which
+        the library's own ordering (capi.Context._in: behind the lane thread's current stream) knows nothing.  The lane's
+        context is first ordered behind the caller's stream (Context.wait_stream), whether or not _take had to gather (its
+        stream is this same one).  Nothing waits on the host."""
         lanes, pools = self.compute.lanes, self.compute.pools
+        producer, on_gpu = None, [x.device for x in (rows, frames) if getattr(x, "is_cuda", False)]
+        if on_gpu:
+            import torch
+            producer = torch.cuda.current_stream(on_gpu[0])
 
-        def timed_detect(ctx, part, producer, out):
+        def timed_detect(ctx, part, out):
             t0 = time.perf_counter()
-            if producer is not None and hasattr(ctx, "wait_stream"):
-                ctx.wait_stream(producer)                     # the gather of `part` was queued on another thread's stream
+            if producer is not None:
+                ctx.wait_stream(producer)
             board_into(ctx, part, out)
             return time.perf_counter() - t0
-        t0 = time.perf_counter()
-        idx = list(idx)
-        k = len(lanes) if len(idx) >= 8 * len(lanes) else 1
-        cuts = [round(i * len(idx) / k) for i in range(k + 1)]
-        futs = [pools[i][0].submit(timed_detect, lanes[i][0], *_take(frames, idx[cuts[i]:cuts[i + 1]], keep), rows[cuts[i]:cuts[i + 1]])
-                for i in range(k)]
-        got = [f.result() for f in futs]
-        hs = self.host_seconds                               # diagnostics: the requests' wall time and the library calls inside
-        hs["lazy_fetch"] = hs.get("lazy_fetch", 0.0) + time.perf_counter() - t0
-        hs["lazy_detect"] = hs.get("lazy_detect", 0.0) + max(got)
+        with self._clock("lazy_fetch"):                       # diagnostics: the requests' wall time and the library calls inside
+            idx = list(idx)
+            k = len(lanes) if len(idx) >= 8 * len(lanes) else 1
+            cuts = [round(i * len(idx) / k) for i in range(k + 1)]
+            futs = [pools[i][0].submit(timed_detect, lanes[i][0], _take(frames, idx[cuts[i]:cuts[i + 1]], keep)[0], rows[cuts[i]:cuts[i + 1]])
+                    for i in range(k)]
+            got = [f.result() for f in futs]
+        self.host_seconds["lazy_detect"] = self.host_seconds.get("lazy_detect", 0.0) + max(got)     # (the slowest lane's share)
         return rows
 
     def _board_round(self, t, idx):
         """One round of the hold-off-aware board path across ranks: frame f of the batch lives on rank f mod world (at
         index f // world of its shard); this rank computes K1-K6 of the requested frames it owns straight into a record
         buffer, ONE gather brings the buffers to rank 0 -> there (rows in idx order, their lines), None elsewhere.  A rank
-        whose board path raises still joins the gather, with a header row that says so: rank 0 then raises, i.e. ends the
-        fold and tells everyone."""
+        whose board path raises still joins, its header row says so: rank 0 then raises, i.e. ends the fold and tells everyone."""
         W, r = self.world, self.rank
         per = max(sum(1 for f in idx if f % W == q) for q in range(W))
         mine = [f // W for f in idx if f % W == r]
-        buf, failed = record_buffer(per + 1, self.records_device), False
+        buf, failed, lease = record_buffer(per + 1, self.records_device), False, []
         try:
             if mine:
                 self._detect_frames(t.frames, mine, buf[1:1 + len(mine)], t.keep)
@@ -1194,7 +1219,6 @@ class FastFilePipeline:
             failed = True
             self.errors.append(why)
             buf = record_buffer(per + 1)                       # (host memory: the GPU may be what failed)
-        lease = []
         got = self.group.gather_rows(self._wire_rows(buf, per + 1, failed), lease)
         if r != 0:
             return None
@@ -1216,85 +1240,66 @@ class FastFilePipeline:
         after a hit, board/bf_auto.py:43-49).  Every rank knows the fold's state at the start of the batch (it came with
         the previous batch's transform) and therefore the batch's FIRST request -- the frames the fold looks at if every
         window hits on its first opportunity (BoardFold.first_request): each rank computes the ones it owns, one all-gather.
-        Rank 0 folds; whenever the fold needs a frame outside what it has, it broadcasts the next request (a hypothesis for
-        the rest of the batch again) and another round follows.  The closing broadcast carries the transform and the state
-        the next batch starts from.  Every rank issues the same collectives in the same order: round 0 (unless the whole
-        batch lies in the hold-off), then (broadcast, gather) until a broadcast is not a request.
-        -> (transform after this batch or None, failed)"""
-        import time
-        t0 = time.perf_counter()
-        n, H, WIRE = t.n_total, self.board.refresh_frames, self.WIRE
-        first = BoardFold.first_request(self._board_state, n, H)
-        wire = np.zeros(WIRE + n)
-        if self.rank == 0:
-            rounds, err, new = [0], None, None
+        Rank 0 folds (_lazy_fold_rounds); whenever the fold needs a frame outside what it has, it broadcasts the next request
+        (a hypothesis for the rest of the batch again) and another round follows (_lazy_follow_rounds on the other ranks).
+        The closing broadcast carries the transform and the state the next batch starts from.  Every rank issues the same
+        collectives in the same order: round 0 (unless the whole batch lies in the hold-off), then (broadcast, gather) until
+        a broadcast is not a request.  -> (transform after this batch or None, failed)"""
+        with self._clock("fold_board"):
+            first = BoardFold.first_request(self._board_state, t.n_total, self.board.refresh_frames)
+            wire = self._lazy_fold_rounds(t, first) if self.rank == 0 else self._lazy_follow_rounds(t, first)
+        kind, new, self._board_state, _ = Wire.read(wire)
+        if kind < 0 and self.rank != 0:
+            self.errors.append(RuntimeError("the board fold failed (rank 0, or the board path of a rank it asked)"))
+        return new, kind < 0
 
-            def fetch(idx):
-                idx = [int(f) for f in idx]
-                if rounds[0] == 0:
-                    if idx != first:                           # (the same pure function on the same state: cannot happen)
-                        raise RuntimeError("the fold's first request differs from the plan every rank made from its state")
-                else:
-                    req = np.zeros(WIRE + n)
-                    req[0], req[1], req[WIRE:WIRE + len(idx)] = 2.0, len(idx), idx
-                    self.group.broadcast_array(req, 0)
-                rounds[0] += 1
-                return self._board_round(t, idx)
-            count0 = self.board.finder.total_f_processed
-            try:
-                if self.board.state() != self._board_state:
-                    raise RuntimeError("the board fold's state %s is not the one this batch was planned from %s" % (self.board.state(), self._board_state))
-                self.board.run_lazy(n, fetch, plan_ahead=True)
-                new = self.board.mtx
-            except Exception as why:
-                err = why
-                # the fold stopped at some frame k < n: it advances over the rest of the batch as frames without a contour, so
-                # that the state broadcast below -- what every rank plans the next batch from -- is that of a film with a
-                # gap, not of a film that is n - k frames short (ADVICE r5)
-                rest = max(0, n - (self.board.finder.total_f_processed - count0))
+    def _lazy_follow_rounds(self, t, first):
+        """ranks != 0 in _lazy_board_exchange: round 0, then a round per request -> the closing wire"""
+        if first:
+            self._board_round(t, first)
+        while True:
+            wire = self.group.broadcast_array(np.zeros(self.WIRE + t.n_total), 0)
+            asked = Wire.read(wire)[3]
+            if asked is None:
+                return wire
+            self._board_round(t, asked)
 
-                def blank(idx):
-                    rows = np.zeros(len(idx), REC)
-                    rows["status"] = capi.CK_BOARD_NO_CONTOUR
-                    return rows, rows["lines"]
-                try:
-                    self.board.run_lazy(rest, blank, plan_ahead=True)
-                except Exception as again:
-                    self.errors.append(again)
-            if first and rounds[0] == 0:                       # the fold ended before its first request: the other ranks are
-                try:                                           # in round 0's gather already
-                    self._board_round(t, first)
-                except Exception:
-                    pass
-            if err is not None:
-                self.errors.append(err)
-                wire[0] = -1.0
-            else:
-                wire[0] = 1.0 if new is not None else 0.0
-                if new is not None:
-                    wire[1:10] = np.asarray(new, np.float64).reshape(9)
-            wire[10:14] = self.board.state()                   # also after a failure: the fold then stands at the end of the batch
-            wire = self.group.broadcast_array(wire, 0)
-        else:
-            if first:
+    def _lazy_fold_rounds(self, t, first):
+        """rank 0 in _lazy_board_exchange: the fold, a round per request it makes -> the closing wire, broadcast"""
+        n, rounds, err = t.n_total, 0, None
+
+        def fetch(idx):
+            nonlocal rounds
+            idx = [int(f) for f in idx]
+            if rounds > 0:
+                self.group.broadcast_array(Wire.request(idx, n), 0)
+            elif idx != first:                                 # (the same pure function on the same state: cannot happen)
+                raise RuntimeError("the fold's first request differs from the plan every rank made from its state")
+            rounds += 1
+            return self._board_round(t, idx)
+        count0 = self.board.finder.total_f_processed
+        try:
+            if self.board.state() != self._board_state:
+                raise RuntimeError("the board fold's state %s is not the one this batch was planned from %s" % (self.board.state(), self._board_state))
+            self.board.run_lazy(n, fetch, plan_ahead=True)
+        except Exception as why:
+            err = why
+            # the fold stopped at some frame k < n: it advances over the rest of the batch, so that the state broadcast below
+            # -- what every rank plans the next batch from -- is that of a film with a gap, not of one n - k frames short
+            self._fold_gap(max(0, n - (self.board.finder.total_f_processed - count0)), lazy=True)
+        if first and rounds == 0:                              # the fold ended before its first request: the other ranks are
+            try:                                               # in round 0's gather already
                 self._board_round(t, first)
-            while True:
-                wire = self.group.broadcast_array(np.zeros(WIRE + n), 0)
-                if wire[0] != 2.0:
-                    break
-                self._board_round(t, [int(f) for f in wire[WIRE:WIRE + int(wire[1])]])
-        self.host_seconds["fold_board"] += time.perf_counter() - t0
-        self._board_state = tuple(int(v) for v in wire[10:14])
-        if wire[0] < 0:
-            if self.rank != 0:
-                self.errors.append(RuntimeError("the board fold failed (rank 0, or the board path of a rank it asked)"))
-            return None, True
-        return (wire[1:10].reshape(3, 3).copy() if wire[0] == 1.0 else None), False
+            except Exception:
+                pass
+        if err is not None:
+            self.errors.append(err)
+        wire = Wire.outcome(self.board.state(), self.board.mtx, Wire.FOLD_FAILED if err is not None else None, room=n)
+        return self.group.broadcast_array(wire, 0)             # (the state also after a failure: the fold stands at the batch's end)
 
     def finish(self, ticket):
         """wait for the batch's exchange, publish the transform, stones fold (rank 0) -> the fold's per-frame request
         lists on rank 0, None elsewhere"""
-        import time
         try:
             try:
                 full, counts, new, failed = ticket.exchange.result()
@@ -1304,19 +1309,16 @@ class FastFilePipeline:
                 raise RuntimeError("a rank failed in this batch (GPU core, the board fold on rank 0, or a band of the background "
                                    "model): %s" % (self.errors[-1:] or "see its log"))
             self.mtx = new
-            t0 = time.perf_counter()
             emitted = None
-            if self.rank == 0:
-                if not ticket.have_mtx:
+            with self._clock("fold_stones"):
+                if self.rank == 0 and not ticket.have_mtx:
                     emitted = [()] * len(full)
-                elif isinstance(full, Gathered):
-                    emitted = self.stones.run(None, None, counts, records=full.rows, order=full.order)
-                else:
-                    emitted = self.stones.run(None, None, counts, records=full)
+                elif self.rank == 0:
+                    rows, order = (full.rows, full.order) if isinstance(full, Gathered) else (full, None)
+                    emitted = self.stones.run(None, None, counts, records=rows, order=order)
         finally:
             self.group.release(ticket.landing)                 # nothing reads the gathered records after the folds
         hs = self.host_seconds
-        hs["fold_stones"] += time.perf_counter() - t0
         hs["fold"] = hs["fold_board"] + hs["fold_stones"]
         hs["collectives"] = hs["gather"] + hs["bcast"] + hs["band_exchange"] + hs["flags"] + hs["counts_gather"]
         self.frames_done += ticket.n_total
@@ -1381,7 +1383,6 @@ class FastFilePipeline:
         full-size BGR frames are never written) and everything after that sees ordinary frames of capi.pyr_shape(h, w, N);
         the pipeline must have been built for that size."""
         import torch
-        from . import capi
         from .core.capture import file_frame_indices
         downsample = int(downsample)
         fh, fw = capi.pyr_shape(capture.h, capture.w, downsample)
@@ -1417,7 +1418,6 @@ class FastFilePipeline:
         number in the file -- on EVERY rank (the ranks exchange one word per batch before any of them enters the batch's
         collectives), with the cause on the rank that owns the frame.  Returns the concatenated request lists (rank 0)."""
         import torch
-        from . import capi
         from .core.capture import file_frame_indices
         downsample = int(downsample)
         fh, fw = capi.pyr_shape(capture.h, capture.w, downsample)

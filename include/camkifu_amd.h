@@ -479,8 +479,9 @@ double ck_round10_reference(double x);
  * ck_boardfold_step's): the caller replaces its corners, derives the transform, sets *hold_io after a hit and calls
  * again with the new hull.  A hit WITHOUT update leaves the corners -- hence the transform -- as they are: the fold then
  * starts the hold-off itself (*hold_io = hold_after_same_hit) and goes on; hold_after_same_hit < 0 returns such hits too.
- * seen_looked_io[2]: frames offered / looked at (running totals).  On an error *k_io is the frame that raised it (not
- * counted), as an exception out of _detect leaves total_f_processed. */
+ * seen_looked_io[2]: frames offered / looked at (running totals).  On an error *k_io is the frame that raised it: that
+ * frame IS in seen_looked_io (both counts, like the reference's step), only *counter_io is not advanced over it, as an
+ * exception out of _detect leaves total_f_processed. */
 int  ck_boardfold_run(ck_boardfold* bf, int h, int w, const ck_frame_record* recs, const int32_t* order, int n, int32_t* k_io,
                       long long* counter_io, int32_t* hold_io, long long* seen_looked_io, const int32_t* cur_hull,
                       int hold_after_same_hit, int32_t* found, int32_t* update, int32_t* centers, int32_t* n_centers,

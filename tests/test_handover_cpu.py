@@ -100,6 +100,53 @@ def test_take_keeps_its_index_tensor_until_the_gather_has_run(monkeypatch):
     assert part.tolist() == [2, 3, 4] and stream is None and log == []
 
 
+def test_a_lane_is_ordered_behind_the_callers_stream_whether_or_not_take_gathered(monkeypatch):
+    """The hand-over rule of FastFilePipeline._detect_frames.  One lane, three consecutive frames (_take gathers nothing and
+    names no stream), record rows in HBM that the caller allocated on ITS current stream (the exchange thread's): the lane's
+    context is ordered behind that stream -- not behind the lane thread's own -- before the library writes the rows.  The
+    same for device frames with host rows; with host rows and host frames nothing is ordered at all."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    log, callers = [], []
+    xstream, other = _FakeStream(log, handle=0xE8), _FakeStream(log, handle=0xD0)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: xstream if threading.get_ident() in callers else other)
+
+    class Lane:
+        def wait_stream(self, stream):
+            log.append("wait_stream(0x%x)" % stream.cuda_stream)
+
+        def board_detect_records(self, frames, rows):
+            log.append("board_detect_records")
+            return rows
+
+    class OnDevice(_FakeTensor):
+        def __getitem__(self, key):
+            return self
+
+        def __len__(self):
+            return self.shape[0]
+    lane_thread, exchange_thread = ThreadPoolExecutor(1), ThreadPoolExecutor(1)
+    pipe = pipeline.FastFilePipeline.__new__(pipeline.FastFilePipeline)
+    pipe.compute, pipe.host_seconds = types.SimpleNamespace(lanes=[(Lane(), None)], pools=[(lane_thread, None)]), {}
+
+    def detect(frames, rows):
+        callers.append(threading.get_ident())
+        pipe._detect_frames(frames, [4, 5, 6], rows)
+        seen = [entry for entry in log if not entry.startswith("free")]
+        log.clear()
+        return seen
+    host_frames, host_rows = np.zeros((10, 4, 4, 3), np.uint8), np.zeros(3, pipeline.REC)
+    try:
+        for frames, rows in ((host_frames, OnDevice(log, (3, pipeline.REC_BYTES), "rows")),
+                             (OnDevice(log, (10, 4, 4, 3), "frames"), host_rows)):
+            assert exchange_thread.submit(detect, frames, rows).result() == ["wait_stream(0xe8)", "board_detect_records"]
+        assert exchange_thread.submit(detect, host_frames, host_rows).result() == ["board_detect_records"]
+    finally:
+        lane_thread.shutdown()
+        exchange_thread.shutdown()
+
+
 def test_no_host_wait_is_left_in_the_pipeline():
     """the only synchronize() in pipeline.py is the exchange thread's final drain of its own stream"""
     import inspect

@@ -131,6 +131,31 @@ def test_record_roundtrip_and_line_cap():
     assert pipeline.band_rows(1) == [(0, 19)]
 
 
+def test_every_kind_of_wire_survives_a_round_trip():
+    """the 16 doubles that keep the ranks in step (16 + n in the hold-off-aware rounds): each kind is built and read back by
+    pipeline.Wire alone, and the layout is the one the ranks have always exchanged"""
+    Wire = pipeline.Wire
+    assert pipeline.FastFilePipeline.WIRE == Wire.SIZE == 16
+    assert (Wire.CORE_FAILED, Wire.FOLD_FAILED, Wire.NO_TRANSFORM, Wire.TRANSFORM, Wire.REQUEST) == (-2.0, -1.0, 0.0, 1.0, 2.0)
+    mtx = np.random.default_rng(5).normal(size=(3, 3))
+    state = (1234, 17, 3, 250)
+    for n in (0, 7):
+        for mtx_in, failed, kind in ((mtx, None, Wire.TRANSFORM), (None, None, Wire.NO_TRANSFORM),
+                                     (None, Wire.FOLD_FAILED, Wire.FOLD_FAILED), (mtx, Wire.FOLD_FAILED, Wire.FOLD_FAILED),
+                                     (None, Wire.CORE_FAILED, Wire.CORE_FAILED)):
+            wire = Wire.outcome(state, mtx_in, failed, room=n)
+            assert wire.dtype == np.float64 and wire.shape == (16 + n,)
+            got_kind, got_mtx, got_state, asked = Wire.read(wire)
+            assert got_kind == kind and got_state == state and asked is None
+            assert np.array_equal(got_mtx, mtx) if kind == Wire.TRANSFORM else got_mtx is None
+            assert wire[0] == kind and wire[10:14].tolist() == list(state) and not wire[14:].any()
+            assert wire[1:10].tolist() == (mtx.reshape(9).tolist() if kind == Wire.TRANSFORM else [0.0] * 9)
+        for idx in ([], [n - 1] if n else [], list(range(0, n, 3)), list(range(n))):      # the empty and the full batch included
+            wire = Wire.request(idx, n)
+            assert wire.shape == (16 + n,) and wire[0] == 2.0 and wire[1] == len(idx) and wire[16:16 + len(idx)].tolist() == idx
+            assert Wire.read(wire) == (Wire.REQUEST, None, None, idx)
+
+
 def test_grid_of_regions_matches_the_oracle(ora):
     rng = np.random.default_rng(3)
     y = rng.random((100, 81)).astype(np.float32)
@@ -530,14 +555,18 @@ def _board_table(seed, sizes, h, w, bump_at=300, steady=False):
 LAZY_SIZES = [96, 128, 64, 128, 128, 96, 128, 128, 5, 128]            # a batch smaller than the world is in there
 
 
-def _drive_lazy(rank, world, lazy, fail=None, steady=False):
+def _drive_lazy(rank, world, lazy, fail=None, steady=False, sizes=None, trace=None, cnn_fail=None):
     """the pipeline over a table of board records, frames dealt to `world` ranks; the GPU core is a real GpuCore over
     stand-in contexts whose "frames" are indices into the table.  -> (transforms after every batch, fold counters, frames
-    this rank ran K1-K6 on, what finish() raised per batch)"""
+    this rank ran K1-K6 on, what finish() raised per batch).  `sizes`: the batches (default LAZY_SIZES); `trace`: a list
+    that gets "|" at the start of every batch's exchange and "bands" where the band exchange would run; `cnn_fail` =
+    (rank, k): that rank's classifier raises on its k-th call (a GPU-core failure)"""
+    import threading
     from camkifu_amd.pipeline import FastFilePipeline, GpuCore, shard_indices
     h, w = 1080, 1920
-    res, lines = _board_table(21, LAZY_SIZES, h, w, steady=steady)
-    log = []
+    sizes = LAZY_SIZES if sizes is None else sizes
+    res, lines = _board_table(21, sizes, h, w, steady=steady)
+    log, cnn_calls, cnn_lock = [], [0], threading.Lock()
 
     class Ctx(_TableCtx):
         def board_detect(self, frames, thresh, cap, raw):
@@ -545,13 +574,27 @@ def _drive_lazy(rank, world, lazy, fail=None, steady=False):
                 fail[1] = 1 << 30                                       # once
                 raise RuntimeError("board path down on rank %d" % rank)
             return _TableCtx.board_detect(self, frames, thresh, cap, raw)
+
+        def cnn_regions(self, view):
+            with cnn_lock:                                              # (one call per lane, each on its lane's thread)
+                cnn_calls[0] += 1
+                if cnn_fail is not None and cnn_fail[0] == rank and cnn_calls[0] == cnn_fail[1]:
+                    raise RuntimeError("classifier down on rank %d" % rank)
+            return _TableCtx.cnn_regions(self, view)
     lanes = [(Ctx(res, lines, log), Ctx(res, lines, log)) for _ in range(2)]
     core = GpuCore(lanes, bg_ctx=Ctx(res, lines, log), local_model=world == 1)
     pipe = FastFilePipeline(h, w, ControllerHeadless(), rank=rank, world=world, compute=core, board_lazy=lazy)
     assert pipe.board_lazy == lazy
     a, b = pipe.band
     # (the goban bands are not what is under test: 128 blank goban images per batch through gloo on loopback)
-    pipe._band_counts = lambda gobans, n, rates: np.zeros((n, b - a, 19), np.int32)
+    def band_counts(gobans, n, rates):
+        if trace is not None:
+            trace.append("bands")
+        return np.zeros((n, b - a, 19), np.int32)
+    pipe._band_counts = band_counts
+    if trace is not None:
+        exchange = pipe._exchange
+        pipe._exchange = lambda t: (trace.append("|"), exchange(t))[1]
     tickets, mtxs, raised, first = [], [], [], 0
 
     def finish(tk):
@@ -561,7 +604,7 @@ def _drive_lazy(rank, world, lazy, fail=None, steady=False):
         except RuntimeError as why:
             raised.append(str(why))
         mtxs.append(None if pipe.mtx is None else pipe.mtx.tolist())
-    for n in LAZY_SIZES:
+    for n in sizes:
         tickets.append(pipe.submit(first + shard_indices(n, rank, world), n))
         first += n
         if len(tickets) == 2:                                            # two batches in flight
@@ -576,23 +619,40 @@ def _drive_lazy(rank, world, lazy, fail=None, steady=False):
     return out
 
 
-def _run_lazy(rank, world, port, q, lazy, fail, steady):
+def _traced(trace):
+    """torch.distributed's collectives as the pipeline calls them, each appending its name to `trace` first"""
+    def wrap(name, fn):
+        def call(*args, **kw):
+            trace.append(name)
+            return fn(*args, **kw)
+        return call
+    for name in ("gather", "broadcast", "all_reduce", "all_to_all_single"):
+        setattr(dist, name, wrap(name, getattr(dist, name)))
+
+
+def _run_lazy(rank, world, port, q, lazy, fail, steady, more=None):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        q.put((rank, _drive_lazy(rank, world, lazy, fail, steady)))
+        more = dict(more or {})
+        if more.pop("traced", False):
+            more["trace"] = []
+            _traced(more["trace"])
+        out = _drive_lazy(rank, world, lazy, fail, steady, **more)
+        out["trace"] = " ".join(more.get("trace") or [])
+        q.put((rank, out))
     finally:
         dist.destroy_process_group()
 
 
-def _spawn_lazy(world, lazy, fail=None, steady=False):
+def _spawn_lazy(world, lazy, fail=None, steady=False, **more):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_run_lazy, args=(r, world, port, q, lazy, fail, steady)) for r in range(world)]
+    procs = [ctx.Process(target=_run_lazy, args=(r, world, port, q, lazy, fail, steady, more)) for r in range(world)]
     for p in procs:
         p.start()
     res = [r[1] for r in sorted((q.get(timeout=240) for _ in range(world)), key=lambda r: r[0])]
@@ -645,6 +705,40 @@ def test_a_board_path_failure_on_one_rank_reaches_every_rank():
     # the failed batch leaves a GAP, not a shorter film -- the fold advanced over the frames whose records never
     # came as frames without a contour, so the running count every rank plans the next batches from is the film's
     assert res[0]["state"][0] == sum(LAZY_SIZES) and res[0]["seen"] == sum(LAZY_SIZES)
+
+
+SEQUENCE = {
+    False: """| gather broadcast
+              | gather broadcast
+              | gather broadcast bands all_reduce gather
+              | gather broadcast bands all_reduce gather""",
+    True: """| gather broadcast gather broadcast gather broadcast gather broadcast gather broadcast gather broadcast gather broadcast
+             | gather broadcast gather broadcast gather broadcast gather broadcast
+             | gather broadcast gather broadcast bands all_reduce gather
+             | gather broadcast gather broadcast gather broadcast bands all_reduce gather"""}
+
+
+@pytest.mark.parametrize("lazy", [False, True])
+def test_the_sequence_of_collectives_is_pinned(lazy):
+    """what every rank issues, batch by batch ("|" = a batch's exchange starts), recorded on the commit before the exchange
+    stage was split into named steps: both ranks the same string, and that string this literal"""
+    res = _spawn_lazy(2, lazy, sizes=[96, 128, 5, 64], traced=True)
+    assert res[0]["raised"] == [None] * 4
+    assert res[0]["trace"] == res[1]["trace"]
+    assert res[0]["trace"] == " ".join(SEQUENCE[lazy].split()), res[0]["trace"]
+
+
+@pytest.mark.parametrize("lazy", [False, True])
+def test_a_gpu_core_failure_reaches_every_rank_in_both_board_modes(lazy):
+    """The outcome broadcast is how ranks other than 0 learn that some rank's GPU core failed, before the band all-to-all
+    whose sizes the failed rank cannot honour -- in hold-off-aware mode too, where the board rounds before it know nothing of
+    the cores' results.  Rank 1's classifier raises on its third call: every rank's finish() raises for batch 3 and no
+    other, the next batch goes through, and the ranks agree on the fold's state."""
+    res = _spawn_lazy(2, lazy, sizes=[96, 128, 64, 64, 64], cnn_fail=(1, 3))
+    for r in res:
+        assert [i for i, x in enumerate(r["raised"]) if x is not None] == [3], r["raised"]
+        assert r["raised"][3].startswith("a rank failed")
+    assert res[0]["state"] == res[1]["state"]
 
 
 def test_hold_off_aware_pipeline_equals_the_eager_one_and_computes_a_fraction_of_the_records():

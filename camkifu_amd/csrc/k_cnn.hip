@@ -494,7 +494,9 @@ __host__ __device__ constexpr int lds_stride_b(int n, int rem, int mod) { return
 // Split-precision mode (CK_CNN_F16X2): f32-accurate convolutions on the fp16 matrix pipe.
 // Every f32 operand x is carried as two halves, hi = fp16(x) and lo = fp16(x - hi) (22 mantissa bits
 // together); a product is the three MFMAs lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_f16 with f32
-// accumulation (the lo*lo term is below 2^-22 of the product).  Three fp16 MFMAs of 16 cycles replace
+// accumulation (the lo*lo term is below 2^-22 of the product).  The 22 bits hold for |x| >= 2^-3.  Only the weights
+// are pre-scaled, so below 2^-3 an activation's lo is an fp16 subnormal and hi + lo = x to 2^-24 absolute.  Subnormal
+// lo halves are kept by the conversion and by the fp16 MFMA (tests/test_gpu_cnn_exact.py, case alo_sub).  Three fp16 MFMAs of 16 cycles replace
 // eight f32 MFMAs of 32 cycles per 16x16x32 block: the ceiling moves from 155 to ~830 TFLOP/s-equivalent.
 // Weights are pre-scaled by 2^8 so that their lo halves stay normal fp16 numbers (undone on the accumulator,
 // exact).  Results agree with the f32 kernels to ~1e-6 (tests), not bit for bit: the k-ordered f32 chain

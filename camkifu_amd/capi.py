@@ -18,6 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 CK_OK, CK_ERR_ARG, CK_ERR_HIP, CK_ERR_CAPACITY, CK_ERR_STATE, CK_ERR_DATA = 0, 1, 2, 3, 4, 5
 CK_HOST, CK_DEVICE = 0, 1
 CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
+CK_JPEG_ENTROPY_HOST, CK_JPEG_ENTROPY_DEVICE = 0, 1
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
@@ -445,6 +446,41 @@ class Context:
             raise err
         self._chk(rc)
         return out
+
+    def jpeg_set_entropy(self, mode):
+        """where jpeg_decode runs the Huffman stage from now on: "host" (the default: the library's worker threads) or
+        "device" (one GPU lane per restart interval; the compressed bytes go up instead of the coefficients)"""
+        modes = {"host": CK_JPEG_ENTROPY_HOST, "device": CK_JPEG_ENTROPY_DEVICE}
+        if mode not in modes:
+            raise CkError("jpeg entropy mode: 'host' or 'device' is needed, got %r" % (mode,))
+        self._chk(lib().ck_jpeg_set_entropy(self._h, modes[mode]))
+
+    def jpeg_uploaded_bytes(self):
+        """the bytes the last jpeg_decode or jpeg_coefficients_device of this context copied from host to device"""
+        b = C.c_longlong(0)
+        self._chk(lib().ck_jpeg_uploaded_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def jpeg_coefficients_device(self, streams, to_device=None):
+        """jpeg_coefficients with the Huffman stage on the GPU: streams of one geometry in host memory -> (info of the
+        first, coef (n, blocks * 64) int16, quant (n, 3, 64)) as numpy arrays (quant uint16), or with `to_device` as torch
+        tensors in HBM (quant int16: the bits count).  CkError (CK_ERR_DATA) names the frame that failed; its index is
+        the error's `bad_frame`."""
+        ptrs, lens, keep = _jpeg_streams(streams)
+        n = len(keep)
+        info = jpeg_probe(keep[0])
+        geom = JpegInfo(info["h"], info["w"], info["sampling"], info["restart_interval"], info["blocks"])
+        coef, cp, sp = self._out(None, (n, info["blocks"] * 64), np.int16, None, to_device)
+        quant, qp, _ = self._out(None, (n, 3, 64), np.uint16 if to_device is None else np.int16, None, to_device)
+        bad = C.c_int32(-1)
+        rc = lib().ck_jpeg_coefficients_device(self._h, ptrs, lens, n, C.byref(geom), cp, qp, sp, C.byref(bad))
+        if rc != 0:
+            err = CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(self._h) or b"").decode()))
+            err.code = rc
+            if bad.value >= 0:
+                err.bad_frame = bad.value
+            raise err
+        return info, coef, quant
 
     def jpeg_reconstruct(self, coef, quant, h, w, sampling, out=None):
         """the GPU half alone: coefficients (n, blocks * 64) int16 and quant tables (n, 3, 64) uint16 as jpeg_coefficients
@@ -1041,6 +1077,50 @@ def jpeg_coefficients(streams):
     bad = C.c_int32(-1)
     rc = lib().ck_jpeg_coefficients(ptrs, lens, n, C.byref(geom), coef.ctypes.data_as(C.c_void_p),
                                     quant.ctypes.data_as(C.c_void_p), C.byref(bad))
+    if rc != 0:
+        err = _host_error(rc)
+        err.bad_frame = bad.value
+        raise err
+    return info, coef, quant
+
+
+def jpeg_plan(streams):
+    """the plan of the strand decoder (host only): streams of one geometry -> (rows (strands, 6) int64 of {frame, begin, end,
+    first_mcu, n_mcu, table_set}, the number of table sets).  A strand is one restart interval of one frame, begin / end
+    byte offsets into its stream.  CkError (CK_ERR_DATA) names the frame that was refused."""
+    ptrs, lens, keep = _jpeg_streams(streams)
+    n = len(keep)
+    info = jpeg_probe(keep[0])
+    geom = JpegInfo(info["h"], info["w"], info["sampling"], info["restart_interval"], info["blocks"])
+    count, sets, bad = C.c_longlong(0), C.c_int32(0), C.c_int32(-1)
+    rows = np.empty((0, 6), np.int64)
+    for _ in range(2):                                   # (the first call sizes the array)
+        _check_array(rows, (rows.shape[0], 6), np.int64, "strands", writeable=True)
+        rc = lib().ck_jpeg_plan(ptrs, lens, n, C.byref(geom), rows.ctypes.data_as(C.c_void_p), rows.shape[0],
+                                C.byref(count), C.byref(sets), C.byref(bad))
+        if rc != CK_ERR_CAPACITY:
+            break
+        rows = np.empty((count.value, 6), np.int64)
+    if rc != 0:
+        err = _host_error(rc)
+        if bad.value >= 0:
+            err.bad_frame = bad.value
+        raise err
+    return rows[:count.value], sets.value
+
+
+def jpeg_coefficients_strands(streams):
+    """jpeg_coefficients through the plan and the strand decoder the GPU kernel runs, on the host (host only): the same
+    results, the same accept / refuse decisions"""
+    ptrs, lens, keep = _jpeg_streams(streams)
+    n = len(keep)
+    info = jpeg_probe(keep[0])
+    geom = JpegInfo(info["h"], info["w"], info["sampling"], info["restart_interval"], info["blocks"])
+    coef = np.empty((n, info["blocks"] * 64), np.int16)
+    quant = np.empty((n, 3, 64), np.uint16)
+    bad = C.c_int32(-1)
+    rc = lib().ck_jpeg_coefficients_strands(ptrs, lens, n, C.byref(geom), coef.ctypes.data_as(C.c_void_p),
+                                            quant.ctypes.data_as(C.c_void_p), C.byref(bad))
     if rc != 0:
         err = _host_error(rc)
         err.bad_frame = bad.value

@@ -282,15 +282,17 @@ def _default_encode():
     return capi.get_context().jpeg_encode
 
 
-def write_jpeg(path, bgr, quality=90, sampling=None, encode=None):
+def write_jpeg(path, bgr, quality=90, sampling=None, encode=None, restart_interval=0):
     """one BGR image (h, w, 3), a numpy array or a tensor in HBM, as a baseline JPEG still: the bytes libjpeg's default
     compressor writes (cv2.imwrite, PIL.Image.save).  sampling: capi.CK_JPEG_* (4:2:0 when None); encode: a callable
-    (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context.  -> bytes written"""
+    (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context; restart_interval: MCUs
+    between restart markers (0: none; handed to `encode` as restart_interval= only when set).  -> bytes written"""
     from .. import capi
     if len(bgr.shape) != 3 or bgr.shape[2] != 3:
         raise ValueError("write_jpeg takes one (h, w, 3) image, got %r" % (tuple(bgr.shape),))
     encode = encode or _default_encode()
-    data = encode(bgr[None], quality=quality, sampling=capi.CK_JPEG_420 if sampling is None else sampling)[0]
+    extra = dict(restart_interval=int(restart_interval)) if restart_interval else {}
+    data = encode(bgr[None], quality=quality, sampling=capi.CK_JPEG_420 if sampling is None else sampling, **extra)[0]
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
@@ -301,13 +303,16 @@ class MjpegWriter:
     tensor in HBM -- and appends one '00dc' chunk per frame; close() patches the RIFF, movi, avih and strh fields that depend
     on the frame count and appends the 'idx1' index.  The layout is write_mjpeg_avi's, so AviMjpegCapture reads it back.
     `encode`: a callable (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context.
+    `restart_interval`: MCUs between restart markers (0: none; handed to `encode` as restart_interval= only when set) -- a
+    film with them decodes in parallel pieces in the device entropy mode (Context.jpeg_set_entropy).
     A batch that would take the file past AVI_MAX_BYTES raises AviError before any of it is written (the reader stops
     there: no OpenDML); the file can still be closed and holds the batches before.  Use as a context manager, or close()."""
 
-    def __init__(self, path, h, w, fps=30.0, quality=90, sampling=None, encode=None):
+    def __init__(self, path, h, w, fps=30.0, quality=90, sampling=None, encode=None, restart_interval=0):
         from .. import capi
         self.path, self.h, self.w = path, int(h), int(w)
         self.quality = int(quality)
+        self.restart_interval = int(restart_interval)
         self.sampling = capi.CK_JPEG_420 if sampling is None else int(sampling)
         self.encode = encode
         self.rate, self.scale = (int(fps[0]), int(fps[1])) if isinstance(fps, (tuple, list)) else (int(round(float(fps) * 1000)), 1000)
@@ -355,7 +360,8 @@ class MjpegWriter:
             return 0
         if self.encode is None:
             self.encode = _default_encode()
-        streams = self.encode(frames, quality=self.quality, sampling=self.sampling)
+        extra = dict(restart_interval=self.restart_interval) if self.restart_interval else {}
+        streams = self.encode(frames, quality=self.quality, sampling=self.sampling, **extra)
         if len(streams) != shp[0]:
             raise AviError("the encoder gave %d streams for %d frames" % (len(streams), shp[0]))
         sizes = [len(s) for s in streams]

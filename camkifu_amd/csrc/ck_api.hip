@@ -15,6 +15,7 @@
 #include "ck_common.h"
 #include "ck_stonegeom.h"
 #include "ck_jpeg.h"
+#include "ck_jpeg_strand.h"
 #include "ck_jpeg_enc.h"
 #include "ck_overlay.h"
 
@@ -708,10 +709,186 @@ static int jpeg_pass_frames(int n, size_t frame_bytes)
     return fit < 1 ? 1 : (fit < (size_t)n ? (int)fit : n);
 }
 
+// frames per pass in the device entropy mode: the same rule applied to what that mode stages.  Its pinned block and device
+// twin hold the COMPRESSED bytes of a pass (plan rows, table sets and quant tables are small beside them), so the budget
+// buys many more frames -- and the kernel needs them: one lane per strand, so a pass is as fast as its longest strand
+// however many strands it has.  The coefficients of a pass exist in HBM only; they are held to 2 GiB.
+static int jpeg_pass_frames_device(int n, const size_t* len, size_t cframe)
+{
+    size_t sum = 0;
+    for (int f = 0; f < n; f++) sum += len[f];
+    const int fit = jpeg_pass_frames(n, sum / (size_t)n + 192 * sizeof(uint16_t) + 16);
+    const size_t hbm = ((size_t)2 << 30) / (cframe ? cframe : 1);
+    return hbm < 1 ? 1 : (hbm < (size_t)fit ? (int)hbm : fit);
+}
+
+// The Huffman stage of m frames on the GPU (CK_JPEG_ENTROPY_DEVICE), one pass: the plan on the host, then the entropy-coded
+// segments (each starting on 16 bytes, zeroed slack behind the last), the plan rows, the table sets and the quant tables in
+// the context's pinned block -> one upload -> k_jpeg_huff -> the status words down.  d_coef: m * geom.blocks * 64 int16 on
+// the device.  *d_quant: the m * 192 quant tables in HBM (inside in_stage2, 16-byte aligned), h_quant (nullable): the same
+// on the host.  Returns with the stream idle.  On a refusal *bad is the lowest frame with a failed strand (or the frame
+// the planner refused, when no frame before it failed) and `why` the cause at its lowest MCU; a failure that is no frame's
+// fault (HIP, memory) leaves *bad at -1 and its message in the context.
+static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int m, const ck_jpeg_info& geom,
+                          int16_t* d_coef, const uint16_t** d_quant, uint16_t* h_quant, int* bad, std::string& why)
+{
+    CkJpegPlan plan;
+    const int prc = ck_jpeg_plan_build(data, len, m, geom, &plan);
+    if (prc != CK_OK && prc != CK_ERR_DATA) { *bad = plan.frames; why = plan.msg; return prc; }
+    const int frames = plan.frames;
+    const size_t ns = plan.strands.size();
+    if (ns > 0x7fffffff) return ck_fail(ctx, CK_ERR_ARG, "%zu strands in one pass", ns);
+    if (ns) {
+        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        std::vector<size_t> seg((size_t)frames);                   // where each frame's entropy-coded segment is staged
+        size_t at = 0;
+        for (int f = 0; f < frames; f++) { seg[f] = at; at = up16(at + (len[f] - plan.scan[f])); }
+        const size_t n_bytes = at + 16;                            // (zeroed slack: a wide load at the last byte stays inside)
+        const size_t rows_at = up16(n_bytes), sets_at = up16(rows_at + ns * sizeof(CkStrand));
+        const size_t quant_at = up16(sets_at + plan.sets.size() * sizeof(CkHuffSet));
+        const size_t total = quant_at + (size_t)frames * 192 * sizeof(uint16_t);
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
+        uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
+        for (int f = 0; f < frames; f++) {
+            const size_t sl = len[f] - plan.scan[f], gap = (f + 1 < frames ? seg[f + 1] : n_bytes) - seg[f] - sl;
+            memcpy(hp + seg[f], data[f] + plan.scan[f], sl);
+            memset(hp + seg[f] + sl, 0, gap);
+        }
+        memset(hp + n_bytes, 0, rows_at - n_bytes);
+        CkStrand* rows = (CkStrand*)(hp + rows_at);
+        for (size_t s = 0; s < ns; s++) {
+            rows[s] = plan.strands[s];
+            const int64_t shift = (int64_t)seg[(size_t)rows[s].frame] - (int64_t)plan.scan[(size_t)rows[s].frame];
+            rows[s].begin += shift;
+            rows[s].end += shift;
+        }
+        memcpy(hp + sets_at, plan.sets.data(), plan.sets.size() * sizeof(CkHuffSet));
+        memcpy(hp + quant_at, plan.quant.data(), (size_t)frames * 192 * sizeof(uint16_t));
+        const void* d_in;
+        CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage2, &d_in));
+        ctx->jpeg_uploaded += (long long)total;
+        const uint8_t* d = (const uint8_t*)d_in;
+        CK_TRY(ck_ensure(ctx, ctx->misc, ns * sizeof(uint32_t)));
+        CK_TRY(k_jpeg_huff(ctx, d, (long long)n_bytes, (const CkStrand*)(d + rows_at), (int)ns, (const CkHuffSet*)(d + sets_at),
+                           (int)plan.sets.size(), plan.g, (long long)geom.blocks * 64, frames, d_coef, (uint32_t*)ctx->misc.p));
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ns * sizeof(uint32_t)));
+        uint32_t* status = (uint32_t*)ctx->host_pinned2.p;
+        CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t s = 0; s < ns; s++)
+            if (status[s]) {
+                char msg[CK_JPEG_MSG];
+                *bad = (int)plan.strands[s].frame;
+                ck_strand_message(status[s], plan.ri[(size_t)*bad], msg);
+                why = msg;
+                return CK_ERR_DATA;
+            }
+        *d_quant = (const uint16_t*)(d + quant_at);
+        if (h_quant) memcpy(h_quant, plan.quant.data(), (size_t)frames * 192 * sizeof(uint16_t));
+    }
+    if (prc != CK_OK) { *bad = plan.frames; why = plan.msg; return prc; }
+    return CK_OK;
+}
+
+int ck_jpeg_set_entropy(ck_ctx* ctx, int mode)
+{
+    CK_API_BEGIN(ctx)
+    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
+    ctx->jpeg_entropy = mode;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                                int16_t* coef, uint16_t* quant, int out_space, int32_t* bad_frame)
+{
+    CK_API_BEGIN(ctx)
+    if (bad_frame) *bad_frame = -1;
+    ctx->jpeg_bad_frame = -1;
+    ctx->jpeg_uploaded = 0;
+    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(ctx, geom->h, geom->w, geom->sampling, geom->blocks));
+    if (out_space != CK_HOST && (((uintptr_t)coef | (uintptr_t)quant) & 15))
+        return ck_fail(ctx, CK_ERR_ARG, "coefficients and quant tables must lie on 16 bytes");
+    const size_t cframe = (size_t)geom->blocks * 64 * sizeof(int16_t), qframe = 192 * sizeof(uint16_t);
+    const int pass = jpeg_pass_frames_device(n, len, cframe);
+    if (out_space == CK_HOST) CK_TRY(ck_ensure(ctx, ctx->in_stage, (size_t)pass * cframe));
+    for (int f0 = 0; f0 < n; f0 += pass) {
+        const int m = n - f0 < pass ? n - f0 : pass;
+        int16_t* d_coef = out_space == CK_HOST ? (int16_t*)ctx->in_stage.p : coef + (size_t)f0 * (cframe / sizeof(int16_t));
+        const uint16_t* d_quant = nullptr;
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, *geom, d_coef, &d_quant, out_space == CK_HOST ? quant + (size_t)f0 * 192 : nullptr,
+                                      &bad, why);
+        if (rc != CK_OK && bad < 0) return rc;                    // no frame's fault (HIP, memory): the message is stored
+        if (rc != CK_OK) {
+            if (bad_frame) *bad_frame = f0 + bad;
+            ctx->jpeg_bad_frame = f0 + bad;
+            (void)hipStreamSynchronize(ctx->stream);
+            return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+        }
+        if (out_space == CK_HOST) {
+            CK_TRY(ck_from_device(ctx, coef + (size_t)f0 * (cframe / sizeof(int16_t)), d_coef, (size_t)m * cframe, CK_HOST));
+        } else {
+            CK_TRY(ck_from_device(ctx, quant + (size_t)f0 * 192, d_quant, (size_t)m * qframe, CK_DEVICE));
+        }
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));            // the next pass stages into the same blocks
+    }
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_plan(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                 int64_t* strands, long long cap, long long* n_strands, int32_t* n_table_sets, int32_t* bad_frame)
+{
+    if (bad_frame) *bad_frame = -1;
+    if (!data || !len || !geom || !n_strands || !n_table_sets || n <= 0 || cap < 0 || (cap > 0 && !strands))
+        return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer, n <= 0 or cap < 0");
+    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
+    try {
+        CkJpegPlan plan;
+        const int rc = ck_jpeg_plan_build(data, len, n, *geom, &plan);
+        if (rc != CK_OK) {
+            if (bad_frame) *bad_frame = plan.frames;
+            return ck_fail(nullptr, rc, "frame %d: %s", plan.frames, plan.msg);
+        }
+        *n_strands = (long long)plan.strands.size();
+        *n_table_sets = (int32_t)plan.sets.size();
+        if (*n_strands > cap) return ck_fail(nullptr, CK_ERR_CAPACITY, "%lld strands where the array holds %lld", *n_strands, cap);
+        static_assert(sizeof(CkStrand) == 6 * sizeof(int64_t), "a plan row is 6 int64");
+        if (*n_strands) memcpy(strands, plan.strands.data(), plan.strands.size() * sizeof(CkStrand));
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_jpeg_coefficients_strands(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                                 int16_t* coef, uint16_t* quant, int32_t* bad_frame)
+{
+    if (bad_frame) *bad_frame = -1;
+    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
+    try {
+        int bad = -1;
+        char msg[CK_JPEG_MSG] = {0};
+        const int rc = ck_jpeg_strands_host(data, len, n, *geom, coef, quant, false, &bad, msg);
+        if (rc != CK_OK) {
+            if (bad_frame) *bad_frame = bad;
+            return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
+        }
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
 int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space)
 {
     CK_API_BEGIN(ctx)
     ctx->jpeg_bad_frame = -1;
+    ctx->jpeg_uploaded = 0;
     if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
     auto first = std::make_unique<CkJpegFrame>();
     char msg[CK_JPEG_MSG];
@@ -724,6 +901,29 @@ int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, i
     const int pass = jpeg_pass_frames(n, cframe + qframe);
     OutStage<uint8_t> o;
     CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
+    if (ctx->jpeg_entropy == CK_JPEG_ENTROPY_DEVICE) {
+        // per pass: the compressed bytes up, the Huffman kernel, the reconstruct kernel: the coefficients stay in HBM
+        const int pass = jpeg_pass_frames_device(n, len, cframe);
+        CK_TRY(ck_ensure(ctx, ctx->in_stage, (size_t)pass * cframe));
+        for (int f0 = 0; f0 < n; f0 += pass) {
+            const int m = n - f0 < pass ? n - f0 : pass;
+            const uint16_t* d_quant = nullptr;
+            int bad = -1;
+            std::string why;
+            const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, geom, (int16_t*)ctx->in_stage.p, &d_quant, nullptr, &bad, why);
+            if (rc != CK_OK && bad < 0) return rc;                // no frame's fault (HIP, memory): the message is stored
+            if (rc != CK_OK) {
+                ctx->jpeg_bad_frame = f0 + bad;
+                (void)hipStreamSynchronize(ctx->stream);
+                return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+            }
+            CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)ctx->in_stage.p, d_quant, m, geom.h, geom.w, geom.sampling,
+                                      o.dev + (size_t)f0 * oframe));
+            if (f0 + pass < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        CK_TRY(o.deliver(ctx));
+        return finish(ctx);
+    }
     // per pass: coefficients, then quant tables, in one pinned block -> one upload -> the kernel.  The stream is waited
     // for before the next pass decodes into the same block.
     CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, (size_t)pass * (cframe + qframe)));
@@ -742,12 +942,22 @@ int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, i
         }
         const void* d_in;
         CK_TRY(ck_to_device(ctx, coef, cbytes + qbytes, CK_HOST, ctx->in_stage, &d_in));
+        ctx->jpeg_uploaded += (long long)(cbytes + qbytes);
         CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)d_in, (const uint16_t*)((const uint8_t*)d_in + cbytes), m, geom.h, geom.w,
                                   geom.sampling, o.dev + (size_t)f0 * oframe));
         if (f0 + pass < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     CK_TRY(o.deliver(ctx));
     return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_uploaded_bytes(ck_ctx* ctx, long long* bytes)
+{
+    CK_API_BEGIN(ctx)
+    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
+    *bytes = ctx->jpeg_uploaded;
+    return CK_OK;
     CK_API_END(ctx)
 }
 

@@ -139,6 +139,8 @@ struct ck_ctx {
     std::vector<Mog2State> mog2;
     std::vector<CkTrainer> trainers;
     int jpeg_bad_frame = -1;         // ck_jpeg_decode: the frame its last CK_ERR_DATA is about (-1: none)
+    long long jpeg_uploaded = 0;     // bytes the last ck_jpeg_decode / ck_jpeg_coefficients_device copied to the device
+    int jpeg_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_decode runs the Huffman stage (ck_jpeg_set_entropy)
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
@@ -281,6 +283,13 @@ int k_i420_pyr_down(ck_ctx* ctx, const uint8_t* d_i420, int n, int h, int w, uin
 int k_jpeg_reconstruct(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* d_quant, int n, int h, int w, int sampling, uint8_t* d_bgr);
 // baseline JPEG in front of the Huffman coder (k_jpeg_enc.hip): BGR + one set of quant tables on the device -> coefficients
 int k_jpeg_forward(ck_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_quant, int n, int h, int w, int sampling, int16_t* d_coef);
+// the Huffman stage on the device (k_jpeg_huff.hip): staged entropy-coded bytes + plan rows + table sets -> coefficients
+// (zeroed here first) and one status word per strand
+struct CkStrand;
+struct CkHuffSet;
+struct CkStrandGeom;
+int k_jpeg_huff(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const CkStrand* d_rows, int n_strands, const CkHuffSet* d_sets,
+                int n_sets, const CkStrandGeom& g, long long cframe, int n_frames, int16_t* d_coef, uint32_t* d_status);
 // overlays (k_overlay.hip): n_work non-empty bins of the plan of ck_overlay.cpp, drawn in place on images of h x w x c
 int k_overlay(ck_ctx* ctx, uint8_t* d_img, int h, int w, int c, const int32_t* d_work, int n_work, const int32_t* d_refs,
               const int32_t* d_recs, const uint8_t* d_text);

@@ -1407,19 +1407,23 @@ class FastFilePipeline:
                 emitted.extend(out)
         return emitted
 
-    def process_mjpeg(self, capture, batch=256, file_fps=None, torch_device=None, downsample=0):
+    def process_mjpeg(self, capture, batch=256, file_fps=None, torch_device=None, downsample=0, entropy=None):
         """process_y4m for a Motion-JPEG file (core.capture.AviMjpegCapture): the same frame selection and the same deal of
         the frames to the ranks; each rank decodes ITS frames straight into HBM (ck_jpeg_decode: the Huffman stage on the
         host's worker threads, the coefficients uploaded in passes of about 256 MB, one kernel per pass) and the batch goes
         through process_batch.
         `downsample` = N > 0: the decoded frames go through N levels of pyrDown on the device first (no fusion with the
         decoder); the pipeline must have been built for capi.pyr_shape(h, w, N).
+        `entropy` = "host" | "device": set the context's JPEG entropy mode first (Context.jpeg_set_entropy; "device" runs the
+        Huffman stage on the GPU, one lane per restart interval, and uploads the compressed bytes); None leaves it as it is.
         A frame whose entropy-coded data is damaged, or that has no good frame before it, raises CkError naming the frame's
         number in the file -- on EVERY rank (the ranks exchange one word per batch before any of them enters the batch's
         collectives), with the cause on the rank that owns the frame.  Returns the concatenated request lists (rank 0)."""
         import torch
         from .core.capture import file_frame_indices
         downsample = int(downsample)
+        if entropy is not None:
+            self.ctx.jpeg_set_entropy(entropy)
         fh, fw = capi.pyr_shape(capture.h, capture.w, downsample)
         idx = file_frame_indices(len(capture), capture.fps, file_fps)
         dev = torch_device if torch_device is not None else torch.device("cuda", getattr(self.ctx, "device", 0))

@@ -156,6 +156,34 @@ int ck_jpeg_reconstruct(ck_ctx* ctx, const int16_t* coef, const uint16_t* quant,
 int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space);
 /* the frame the context's last ck_jpeg_decode refused with CK_ERR_DATA, -1 when it refused none */
 int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame);
+/* the bytes the context's last ck_jpeg_decode or ck_jpeg_coefficients_device copied from host to device, all passes: the
+ * coefficients and quant tables in host entropy mode; the entropy-coded segments, plan rows, table sets and quant tables in
+ * device entropy mode */
+int ck_jpeg_uploaded_bytes(ck_ctx* ctx, long long* bytes);
+
+/* The Huffman stage on the GPU, opt-in.  A strand is one restart interval of one frame (the whole scan of a frame that has
+ * none): it starts byte-aligned with the DC predictors at zero, so one GPU lane decodes it without knowing the others.
+ * The host parses the headers and finds the restart markers by a byte scan (the plan); the compressed bytes go up as
+ * they are, and one kernel decodes them into the coefficient layout above.  Both modes accept and refuse the same
+ * streams and give the same coefficients.  A frame without restart intervals is decoded by one lane alone: correct, and slow.
+ * A large batch goes through in passes under ck_jpeg_decode's rule, applied to what this mode stages: about 256 MB of
+ * compressed bytes per pass, and at most 2 GiB of coefficients in HBM. */
+enum { CK_JPEG_ENTROPY_HOST = 0, CK_JPEG_ENTROPY_DEVICE = 1 };
+/* what ck_jpeg_decode does from now on; a new context has CK_JPEG_ENTROPY_HOST */
+int ck_jpeg_set_entropy(ck_ctx* ctx, int mode);
+/* ck_jpeg_coefficients with the Huffman stage on the GPU: streams in HOST memory -> coef and quant in `out_space` (on the
+ * device both must lie on 16 bytes).  On CK_ERR_DATA *bad_frame (nullable) is the first frame that failed. */
+int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                                int16_t* coef, uint16_t* quant, int out_space, int32_t* bad_frame);
+/* host only: the plan of n streams of the geometry *geom -> rows of 6 int64 {frame, begin, end, first_mcu, n_mcu, table_set};
+ * begin / end are offsets into stream `frame`.  Table sets (DC and AC of each component, selectors resolved) are de-duplicated by content
+ * across the call.  A `cap` (in rows) too small is CK_ERR_CAPACITY with *n_strands set, so a caller can size the array and
+ * call again; strands may be NULL with cap 0. */
+int ck_jpeg_plan(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                 int64_t* strands, long long cap, long long* n_strands, int32_t* n_table_sets, int32_t* bad_frame);
+/* host only: the plan, then every strand through the GPU kernel's decoder ON THE HOST -> what ck_jpeg_coefficients gives */
+int ck_jpeg_coefficients_strands(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
+                                 int16_t* coef, uint16_t* quant, int32_t* bad_frame);
 
 /* ---- compressed output: baseline JPEG encode (.jpg stills, Motion-JPEG frames of an .avi)   core/vmanager.py:309-325 (cv2.imwrite)
  * The mirror of the calls above, and as exact: the streams are, byte for byte, what libjpeg's default compressor writes

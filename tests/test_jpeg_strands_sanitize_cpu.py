@@ -1,0 +1,40 @@
+"""AddressSanitizer + UBSan over the planner and the strand decoder the GPU kernel runs: tools/sanitize/jpeg_strand_fuzz.cpp, a
+stand-alone program that links csrc/ck_jpeg.cpp, csrc/ck_jpeg_plan.cpp and csrc/ck_jpeg_strand.h alone, fed with the committed
+cases of test_jpeg_sanitize_cpu extracted into tmp_path (whole, truncated at every offset, mutated at every offset of the
+scan).  The program also holds every decode against the host decoder.  Nothing is loaded into python."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from . import jpeg_cases
+from .test_jpeg_sanitize_cpu import CASES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_strand_decoder_is_clean_under_asan_ubsan_and_equals_the_host_decoder(tmp_path):
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no host compiler")
+    files = []
+    for name in CASES + ["bare"]:
+        data = jpeg_cases.file_cases()[name][0] if name != "bare" else jpeg_cases.strip_dht(jpeg_cases.file_cases()[CASES[0]][0])
+        files.append(str(tmp_path / (name + ".jpg")))
+        with open(files[-1], "wb") as f:
+            f.write(data)
+    exe = str(tmp_path / "jpeg_strand_fuzz")
+    csrc = os.path.join(ROOT, "camkifu_amd", "csrc")
+    res = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                          "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "sanitize", "jpeg_strand_fuzz.cpp"),
+                          os.path.join(csrc, "ck_jpeg.cpp"), os.path.join(csrc, "ck_jpeg_plan.cpp"), "-o", exe],
+                         capture_output=True, text=True)
+    if res.returncode != 0 and ("cannot find -lasan" in res.stderr or "cannot find -lubsan" in res.stderr
+                                or ("libasan" in res.stderr and "No such file" in res.stderr)):
+        pytest.skip("sanitizer runtime not installed")
+    assert res.returncode == 0, res.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    run = subprocess.run([exe] + files, capture_output=True, text=True, env=env, timeout=600)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "jpeg strand decoder: %d cases" % len(files) in run.stdout and "equal to the host decoder" in run.stdout

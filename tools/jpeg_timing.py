@@ -10,6 +10,11 @@ write) as baseline JPEG, 4:2:0, quality 90, and held in host memory.
    (int16 coefficients in, BGR out) and the HBM peak.
 3. end to end: FastFilePipeline.process_mjpeg on the JPEG film against process_y4m on the same film held as I420 (the path
    that existed before), frames/s in alternating rounds, and the game record of each against the film's moves.
+4. device entropy mode (Context.jpeg_set_entropy("device")), on two films from the same frames: one with a restart interval
+   of one MCU row, one without restart intervals.  Per frame: the planner on one thread, the bytes uploaded, the Huffman
+   kernel and the reconstruct kernel (HIP events); jpeg_decode frames/s in device mode against host mode (16 threads) in
+   alternating rounds, for the whole film per call and for smaller calls (the strands per call at which the device mode
+   starts to win); process_mjpeg in both modes against process_y4m, with the three game records.
 
     python tools/jpeg_timing.py [--size 1920x1080] [--film 128] [--n 32] [--reps 7] [--inner 8] [--e2e-reps 5]
 
@@ -70,11 +75,14 @@ def main(argv=None):
                          kernel_calls_per_round=args.inner, e2e_rounds=args.e2e_reps, pipeline_batch=args.batch))
     film, corners, truth, moves, hands = synth.film(F, h, w, seed=synth.SEED, device=dev, quiet=52, move_every=32, hand_frames=12)
     i420 = torch.empty((F, h * w * 3 // 2), dtype=torch.uint8).pin_memory()
-    jpegs = []
+    jpegs, jpegs_row = [], []
+    mcux = -(-w // 16)
     for b0 in range(0, F, 8):
         part = film[b0:b0 + 8]
         i420[b0:b0 + 8].copy_(i420_of(part))
         jpegs += [np.frombuffer(j, np.uint8) for j in ctx.jpeg_encode(part.contiguous(), quality=args.quality, sampling=capi.CK_JPEG_420)]
+        jpegs_row += [np.frombuffer(j, np.uint8) for j in ctx.jpeg_encode(part.contiguous(), quality=args.quality,
+                                                                          sampling=capi.CK_JPEG_420, restart_interval=mcux)]
     del film
     torch.cuda.empty_cache()
     out["plan"]["jpeg_bytes_per_frame"] = int(np.mean([j.size for j in jpegs]))
@@ -147,6 +155,94 @@ def main(argv=None):
         res["host_entropy_frames_per_s"] = round(host_fps, 1)
         res["host_entropy_bounds_the_rate"] = bool(host_fps < 1.5 * res["mjpeg"]["frames_per_s"]["median"])
         out["end_to_end"] = res
+        print("host entropy, kernel, end to end: done", flush=True)
+        # 4. the device entropy mode on both films
+        bgr = torch.empty((F, h, w, 3), dtype=torch.uint8, device=dev)
+        dev_out = {}
+        for film_name, js in (("restart_row", jpegs_row), ("no_restart", jpegs)):
+            rows, sets = capi.jpeg_plan(js)
+            plan_ms = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                capi.jpeg_plan(js)
+                plan_ms.append((time.perf_counter() - t0) * 1e3 / F)
+            leg = dict(strands_per_frame=rows.shape[0] / F, table_sets=sets, jpeg_bytes_per_frame=int(np.mean([j.size for j in js])),
+                       planner_one_thread_ms_per_frame=spread_of(plan_ms))
+            ctx.jpeg_set_entropy("host")
+            want = ctx.jpeg_decode(js[:2])
+            ctx.jpeg_decode(js, out=bgr)
+            leg["bytes_uploaded_per_frame_host_mode"] = ctx.jpeg_uploaded_bytes() // F
+            ctx.jpeg_set_entropy("device")
+            leg["equal_to_host_mode"] = bool(np.array_equal(ctx.jpeg_decode(js[:2]), want))
+            ctx.jpeg_decode(js, out=bgr)
+            leg["bytes_uploaded_per_frame"] = ctx.jpeg_uploaded_bytes() // F          # (what the call staged: ck_jpeg_uploaded_bytes)
+            ctx.timing_enable(True)
+            huff, recon = [], []
+            for _ in range(args.reps):
+                ctx.timing_reset()
+                ctx.jpeg_decode(js, out=bgr)
+                huff.append(ctx.timing_get("jpeg_huff")[0] / F)
+                recon.append(ctx.timing_get("jpeg")[0] / F)
+            ctx.timing_enable(False)
+            leg["entropy_kernel_ms_per_frame"] = spread_of(huff)
+            leg["reconstruct_kernel_ms_per_frame"] = spread_of(recon)
+
+            def decode_fps(mode, count):
+                ctx.jpeg_set_entropy(mode)
+                t0 = time.perf_counter()
+                for b0 in range(0, F, count):
+                    ctx.jpeg_decode(js[b0:b0 + count], out=bgr[:len(js[b0:b0 + count])])
+                torch.cuda.synchronize()
+                return F / (time.perf_counter() - t0)
+            by_batch = []
+            # (a film without restart intervals has one strand per frame: one lane each, so only the ends of the range)
+            for count in [c for c in ((1, 2, 4, 8, 16, 32, 64) if film_name == "restart_row" else (1,)) if c < F] + [F]:
+                fps = dict(host=[], device=[])
+                for mode in fps:
+                    decode_fps(mode, count)
+                for _ in range(args.e2e_reps):
+                    for mode in fps:
+                        fps[mode].append(decode_fps(mode, count))
+                hm, dm = float(np.median(fps["host"])), float(np.median(fps["device"]))
+                by_batch.append(dict(frames_per_call=count, strands_per_call=int(round(count * rows.shape[0] / F)),
+                                     host_frames_per_s=round(hm, 1), device_frames_per_s=round(dm, 1), device_over_host=round(dm / hm, 3)))
+            leg["jpeg_decode_by_frames_per_call"] = by_batch
+            leg["jpeg_decode_whole_film_device_over_host"] = by_batch[-1]["device_over_host"]
+            wins = [b["strands_per_call"] for b in by_batch if b["device_over_host"] > 1.0]
+            leg["device_wins_from_strands_per_call"] = min(wins) if wins else None
+            # process_mjpeg in both modes against process_y4m
+            clips = dict(host=MjpegClip(js, h, w), device=MjpegClip(js, h, w), y4m=I420Clip(i420.numpy(), h, w))
+
+            def run2(kind):
+                p = pipeline.FastFilePipeline(h, w, ControllerHeadless(), ctx=ctx)
+                try:
+                    t0 = time.perf_counter()
+                    if kind == "y4m":
+                        reqs = p.process_y4m(clips[kind], batch=args.batch)
+                    else:
+                        reqs = p.process_mjpeg(clips[kind], batch=args.batch, entropy=kind)
+                    torch.cuda.synchronize()
+                    return time.perf_counter() - t0, reqs
+                finally:
+                    p.close()
+            first2 = {k: run2(k) for k in clips}
+            secs2 = {k: [] for k in clips}
+            for _ in range(args.e2e_reps):
+                for k in clips:
+                    secs2[k].append(run2(k)[0])
+            e2e = {}
+            for k in clips:
+                fps = sorted(F / t for t in secs2[k])
+                e2e[k] = dict(frames_per_s=dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1),
+                                                rounds=len(fps)), game_record=game_quality(first2[k][1], truth, moves, F))
+            e2e["device_over_y4m"] = round(e2e["device"]["frames_per_s"]["median"] / e2e["y4m"]["frames_per_s"]["median"], 3)
+            e2e["host_over_y4m"] = round(e2e["host"]["frames_per_s"]["median"] / e2e["y4m"]["frames_per_s"]["median"], 3)
+            e2e["device_over_host"] = round(e2e["device"]["frames_per_s"]["median"] / e2e["host"]["frames_per_s"]["median"], 3)
+            leg["process_mjpeg"] = e2e
+            ctx.jpeg_set_entropy("host")
+            dev_out[film_name] = leg
+            print("device entropy, %s: done" % film_name, flush=True)
+        out["device_entropy"] = dev_out
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

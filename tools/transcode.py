@@ -57,8 +57,20 @@ def _frames_of(capture, ctx, batch):
             yield np.ascontiguousarray(frames[b0:b0 + batch])
 
 
-def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None):
-    """-> dict(frames, bytes, h, w, fps)"""
+def restart_mcus(restart, w, sampling):
+    """--restart as MCUs between restart markers: a number, or "row" for one MCU row of a film of width w"""
+    if restart in (None, "", 0, "0"):
+        return 0
+    if restart == "row":
+        return -(-int(w) // (16 if sampling >= 2 else 8))          # (4:2:2 and 4:2:0 have MCUs of 16 pixels across)
+    n = int(restart)
+    if not 0 <= n <= 65535:
+        raise SystemExit("--restart: 0 .. 65535 MCUs, or 'row'")
+    return n
+
+
+def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None, restart=0):
+    """restart: MCUs between restart markers, or "row" -> dict(frames, bytes, h, w, fps)"""
     from camkifu_amd import capi
     from camkifu_amd.core.capture import CAP_PROP_FPS, MjpegWriter, open_capture
     ctx = ctx if ctx is not None else capi.get_context()
@@ -70,7 +82,8 @@ def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None):
     else:
         h, w = capture.h, capture.w
     fps = capture.get(CAP_PROP_FPS) or 30.0
-    with MjpegWriter(out, h, w, fps=fps, quality=quality, sampling=sampling, encode=ctx.jpeg_encode) as wr:
+    with MjpegWriter(out, h, w, fps=fps, quality=quality, sampling=sampling, encode=ctx.jpeg_encode,
+                     restart_interval=restart_mcus(restart, w, sampling)) as wr:
         for frames in _frames_of(capture, ctx, batch):
             wr.write(frames)
     return dict(frames=wr.frames, bytes=os.path.getsize(out), h=int(h), w=int(w), fps=float(fps))
@@ -164,6 +177,8 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--sampling", choices=sorted(SAMPLINGS), default="420")
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--restart", default="0", metavar="N|row", help="restart markers every N MCUs, or every MCU row: the pieces "
+                    "the device entropy mode decodes in parallel (plain transcoding only)")
     ap.add_argument("--gobans", action="store_true", help="record the 380x380 goban images of a pipeline run instead of the frames")
     ap.add_argument("--annotate", action="store_true", help="draw what the finders concluded onto the frames, on the GPU; "
                     "without --gobans the analysed frames are written at full size")
@@ -173,7 +188,7 @@ def main(argv=None):
         raise SystemExit("the output is a Motion-JPEG .avi file")
     sampling = SAMPLINGS[args.sampling]
     if not args.gobans and not args.annotate:
-        res = transcode(args.src, args.out, args.quality, sampling, args.batch)
+        res = transcode(args.src, args.out, args.quality, sampling, args.batch, restart=args.restart)
         print("%s: %d frames of %dx%d at %.3g fps, %d bytes" % (args.out, res["frames"], res["w"], res["h"], res["fps"], res["bytes"]))
         return res
     import time

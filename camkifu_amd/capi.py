@@ -512,8 +512,9 @@ class Context:
     def jpeg_encode(self, frames, quality=90, sampling=CK_JPEG_420, restart_interval=0):
         """BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM -> a list of n `bytes`: baseline
         JPEG streams, byte for byte what PIL.Image.save(.., "JPEG", quality=quality, subsampling=..) writes.  The forward
-        kernel runs on the GPU, the Huffman coder on the host (the frames of a batch in parallel).  restart_interval in
-        MCUs, 0: none."""
+        kernel runs on the GPU; the Huffman coder on the host (the frames of a batch in parallel), or, after
+        jpeg_set_encode_entropy("device"), on the GPU as well: then the coefficients stay in HBM and only the streams come
+        down.  The bytes are the same in both modes.  restart_interval in MCUs, 0: none."""
         _check_frames(frames)
         n, h, w = self._shape(frames, 3)
         sampling = int(sampling)
@@ -523,6 +524,37 @@ class Context:
         lens = (C.c_size_t * n)()
         self._chk(lib().ck_jpeg_encode(self._h, p, n, h, w, sp, int(quality), sampling, int(restart_interval),
                                        out.ctypes.data_as(C.c_void_p), stride, lens))
+        return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+
+    def jpeg_set_encode_entropy(self, mode):
+        """where jpeg_encode runs the Huffman stage from now on: "host" (the default: the library's worker threads) or
+        "device" (every block sizes its own code, prefix sums place the blocks and the stuffed bytes; only the streams
+        come down)"""
+        modes = {"host": CK_JPEG_ENTROPY_HOST, "device": CK_JPEG_ENTROPY_DEVICE}
+        if mode not in modes:
+            raise CkError("jpeg entropy mode: 'host' or 'device' is needed, got %r" % (mode,))
+        self._chk(lib().ck_jpeg_set_encode_entropy(self._h, modes[mode]))
+
+    def jpeg_downloaded_bytes(self):
+        """the bytes the last jpeg_encode or jpeg_entropy_encode_device of this context copied from device to host"""
+        b = C.c_longlong(0)
+        self._chk(lib().ck_jpeg_downloaded_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def jpeg_entropy_encode_device(self, coef, quant, h, w, sampling, restart_interval=0):
+        """jpeg_entropy_encode with the Huffman stage on the GPU: coefficients (n, blocks * 64) int16, a numpy array or a
+        torch tensor in HBM, + one set of quant tables (3, 64) -> a list of n `bytes`, those of the host coder.  CkError
+        (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code, in the host coder's words."""
+        h, w, sampling = int(h), int(w), int(sampling)
+        n = int(coef.shape[0]) if len(coef.shape) == 2 else -1
+        _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
+        quant = _quant_tables(quant)
+        stride = jpeg_encode_bound(h, w, sampling)
+        p, sp, keep = self._in(coef, np.int16)
+        out = np.empty(max(1, n) * stride, np.uint8)
+        lens = (C.c_size_t * max(1, n))()
+        self._chk(lib().ck_jpeg_entropy_encode_device(self._h, p, sp, quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+                                                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens))
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
     def overlay_draw(self, images, lists):
@@ -1183,6 +1215,37 @@ def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0):
         raise _host_error(rc)
     streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
     return streams[0] if single else streams
+
+
+def jpeg_entropy_encode_staged(coef, quant, h, w, sampling, restart_interval=0):
+    """jpeg_entropy_encode through the steps the GPU kernels run (size, scan, put, stuff), on the host (host only): the same
+    streams, the same refusals"""
+    h, w, sampling = int(h), int(w), int(sampling)
+    coef = np.ascontiguousarray(coef, np.int16)
+    single = coef.ndim == 1
+    coef = coef.reshape(1, -1) if single else coef
+    n = coef.shape[0]
+    _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
+    quant = _quant_tables(quant)
+    stride = jpeg_encode_bound(h, w, sampling)
+    out = np.empty(max(1, n) * stride, np.uint8)
+    lens = (C.c_size_t * max(1, n))()
+    rc = lib().ck_jpeg_entropy_encode_staged(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+                                             int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
+    if rc != 0:
+        raise _host_error(rc)
+    streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+    return streams[0] if single else streams
+
+
+def jpeg_enc_tiles():
+    """(blocks, bytes): how many blocks in scan order one workgroup of the GPU Huffman coder assembles, how many unstuffed
+    bytes one places; host only"""
+    b, y = C.c_int32(0), C.c_int32(0)
+    rc = lib().ck_jpeg_enc_tiles(C.byref(b), C.byref(y))
+    if rc != 0:
+        raise _host_error(rc)
+    return b.value, y.value
 
 
 def overlay_plan(n, h, w, prims, frame_start, text_len=0):

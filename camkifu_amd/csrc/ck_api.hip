@@ -1056,6 +1056,166 @@ int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, in
     }
 }
 
+int ck_jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                  uint8_t* out, size_t stride, size_t* len)
+{
+    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
+    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
+    try {
+        int bad = -1;
+        char msg[CK_JPEG_MSG] = {0};
+        const int rc = ck_jpeg_enc_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, msg);
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_jpeg_enc_tiles(int32_t* blocks_per_tile, int32_t* bytes_per_tile)
+{
+    if (!blocks_per_tile || !bytes_per_tile) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    *blocks_per_tile = CK_ENC_TILE_BLOCKS;
+    *bytes_per_tile = CK_ENC_TILE_BYTES;
+    return CK_OK;
+}
+
+int ck_jpeg_set_encode_entropy(ck_ctx* ctx, int mode)
+{
+    CK_API_BEGIN(ctx)
+    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
+    ctx->jpeg_enc_entropy = mode;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_downloaded_bytes(ck_ctx* ctx, long long* bytes)
+{
+    CK_API_BEGIN(ctx)
+    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
+    *bytes = ctx->jpeg_downloaded;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// frames per pass in the encoder's device mode: ck_jpeg_encode's rule, the coefficients of a pass held to 2 GiB of HBM
+static int jpeg_enc_pass_frames_device(int n, size_t cframe)
+{
+    const int fit = jpeg_pass_frames(n, cframe);
+    const size_t hbm = ((size_t)2 << 30) / (cframe ? cframe : 1);
+    return hbm < 1 ? 1 : (hbm < (size_t)fit ? (int)hbm : fit);
+}
+
+// The Huffman stage of m frames on the GPU (CK_JPEG_ENTROPY_DEVICE), one pass over coefficients that lie in HBM: size and
+// scan -> 16 bytes down (the lowest block that cannot be coded, the bytes of the bit buffer) -> put, FF counts, lengths ->
+// 8 bytes per frame down -> stuff into the packed buffer -> the streams down in one copy into the pinned block, scattered
+// to out + f * stride from there.  Returns with the stream idle.  On a refusal *bad is the lowest frame that has one and
+// `why` what the host coder says of it; a failure that is no frame's fault leaves *bad at -1, its message in the context.
+static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* quant, int m, int h, int w, int sampling,
+                              int restart_interval, uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why)
+{
+    const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
+    const size_t blocks = (size_t)m * g.blocks, tiles = (size_t)m * g.nseg * g.seg_tiles, segs = (size_t)m * g.nseg;
+    const size_t consts_bytes = sizeof(CkEncTables) + 64 + CK_JPEG_ENC_HEADER_BOUND;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // the work block: 64-bit arrays first, then the 32-bit ones, then the constants
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t a = at; at = up16(at + bytes); return a; };
+    const size_t a_head = take(2 * 8), a_tile_off = take(tiles * 8), a_seg_bits = take(segs * 8), a_seg_u0 = take((segs + m) * 8);
+    const size_t a_frame_u0 = take(((size_t)m + 1) * 8), a_len = take((size_t)m * 8), a_out_off = take(((size_t)m + 1) * 8);
+    const size_t a_bits = take(blocks * 4), a_tile_bits = take(tiles * 4), a_consts = take(consts_bytes);
+    CK_TRY(ck_ensure(ctx, ctx->jenc_work, at));
+    uint8_t* wp = (uint8_t*)ctx->jenc_work.p;
+    CkEncWork wk;
+    wk.head = (uint64_t*)(wp + a_head); wk.tile_off = (uint64_t*)(wp + a_tile_off); wk.seg_bits = (uint64_t*)(wp + a_seg_bits);
+    wk.seg_u0 = (uint64_t*)(wp + a_seg_u0); wk.frame_u0 = (uint64_t*)(wp + a_frame_u0); wk.len = (uint64_t*)(wp + a_len);
+    wk.out_off = (uint64_t*)(wp + a_out_off); wk.bits = (uint32_t*)(wp + a_bits); wk.tile_bits = (uint32_t*)(wp + a_tile_bits);
+    wk.consts = wp + a_consts;
+    // pinned: the constants going up, the size words coming down
+    const size_t p_words = up16(consts_bytes);
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, p_words + 16 + (size_t)m * 8));
+    uint8_t* hp = (uint8_t*)ctx->host_pinned2.p;
+    memcpy(hp, &ck_jpeg_enc_tables(), sizeof(CkEncTables));
+    memcpy(hp + sizeof(CkEncTables), ck_jpeg_enc_zigzag(), 64);
+    memset(hp + sizeof(CkEncTables) + 64, 0, CK_JPEG_ENC_HEADER_BOUND);
+    const uint32_t hl = (uint32_t)ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, hp + sizeof(CkEncTables) + 64);
+    CK_HIP(ctx, hipMemcpyAsync(wp + a_consts, hp, consts_bytes, hipMemcpyHostToDevice, ctx->stream));
+    uint64_t* words = (uint64_t*)(hp + p_words);
+
+    CK_TRY(k_jpeg_enc_measure(ctx, d_coef, m, g, wk));
+    CK_HIP(ctx, hipMemcpyAsync(words, wk.head, 16, hipMemcpyDeviceToHost, ctx->stream));
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->jpeg_downloaded += 16;
+    if (words[0] != ~(uint64_t)0) {
+        const uint64_t f = words[0] >> 32, b = words[0] & 0xffffffffu;
+        if (f >= (uint64_t)m || b >= (uint64_t)g.blocks) return ck_fail(ctx, CK_ERR_STATE, "the size kernel names block %llu of frame %llu", (unsigned long long)b, (unsigned long long)f);
+        CK_HIP(ctx, hipMemcpyAsync(words, wk.bits + f * (uint64_t)g.blocks + b, 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        char msg[CK_JPEG_MSG];
+        ck_jpeg_enc_status_message(*(const uint32_t*)words, (long long)(b / (uint64_t)g.mcu_blocks), msg);
+        *bad = (int)f;
+        why = msg;
+        return CK_ERR_ARG;
+    }
+    const uint64_t total_u = words[1];
+    const size_t byte_tiles = (size_t)(total_u / CK_ENC_TILE_BYTES);
+    if (!total_u || total_u % CK_ENC_TILE_BYTES) return ck_fail(ctx, CK_ERR_STATE, "a bit buffer of %llu bytes", (unsigned long long)total_u);
+    CK_TRY(ck_ensure(ctx, ctx->jenc_bits, (size_t)total_u + byte_tiles * 8));
+    uint32_t* d_buf = (uint32_t*)ctx->jenc_bits.p;
+    uint32_t* d_ff_cnt = (uint32_t*)((uint8_t*)ctx->jenc_bits.p + total_u);
+    uint32_t* d_ff_off = d_ff_cnt + byte_tiles;
+    CK_TRY(k_jpeg_enc_put(ctx, d_coef, m, g, wk, d_buf, total_u, d_ff_cnt, d_ff_off, hl));
+    CK_HIP(ctx, hipMemcpyAsync(words, wk.len, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->jpeg_downloaded += (long long)m * 8;
+    std::vector<size_t> off((size_t)m + 1, 0);
+    for (int f = 0; f < m; f++) {
+        if (words[f] > stride) return ck_fail(ctx, CK_ERR_STATE, "frame %d: a stream of %llu bytes, above the bound", f, (unsigned long long)words[f]);
+        len[f] = (size_t)words[f];
+        off[(size_t)f + 1] = off[f] + up16(len[f]);
+    }
+    const size_t total = off[m];
+    CK_TRY(ck_ensure(ctx, ctx->jenc_pack, total));
+    CK_TRY(k_jpeg_enc_stuff(ctx, m, g, wk, d_buf, total_u, d_ff_off, hl, (uint8_t*)ctx->jenc_pack.p, total));
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
+    CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, ctx->jenc_pack.p, total, hipMemcpyDeviceToHost, ctx->stream));
+    CK_TRY(finish(ctx));
+    ctx->jpeg_downloaded += (long long)total;
+    for (int f = 0; f < m; f++) memcpy(out + (size_t)f * stride, (const uint8_t*)ctx->host_pinned.p + off[f], len[f]);
+    return CK_OK;
+}
+
+int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                  int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
+{
+    CK_API_BEGIN(ctx)
+    ctx->jpeg_downloaded = 0;
+    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    if (in_space != CK_HOST && in_space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", in_space);
+    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
+    CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
+    if (in_space == CK_DEVICE && ((uintptr_t)coef & 15)) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
+    for (int f = 0; f < n; f++) len[f] = 0;
+    char msg[CK_JPEG_MSG];
+    if (ck_jpeg_enc_check(quant, h, w, sampling, restart_interval, msg) != CK_OK) return ck_fail(ctx, CK_ERR_ARG, "frame 0: %s", msg);
+    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
+    const int pass = jpeg_enc_pass_frames_device(n, cframe);
+    for (int f0 = 0; f0 < n; f0 += pass) {
+        const int m = n - f0 < pass ? n - f0 : pass;
+        const void* d_coef;
+        CK_TRY(ck_to_device(ctx, coef + (size_t)f0 * (cframe / sizeof(int16_t)), (size_t)m * cframe, in_space, ctx->in_stage, &d_coef));
+        int bad = -1;
+        std::string why;
+        const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)d_coef, quant, m, h, w, sampling, restart_interval, out + (size_t)f0 * stride,
+                                          stride, len + f0, &bad, why);
+        if (rc != CK_OK && bad < 0) return rc;
+        if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+    }
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
 int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
                    int restart_interval, uint8_t* out, size_t stride, size_t* len)
 {
@@ -1066,6 +1226,31 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
     uint16_t quant[192];
     ck_jpeg_enc_quant(quality, quant);
     const size_t iframe = (size_t)h * w * 3, cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
+    ctx->jpeg_downloaded = 0;
+    if (ctx->jpeg_enc_entropy == CK_JPEG_ENTROPY_DEVICE) {
+        // per pass: frames up (when they are the host's) -> the forward kernel -> the entropy kernels: the coefficients stay
+        // in HBM, the streams come down
+        const int pass = jpeg_enc_pass_frames_device(n, cframe);
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, sizeof quant));
+        CK_TRY(ck_ensure(ctx, ctx->out_stage, (size_t)pass * cframe));
+        memcpy(ctx->host_pinned2.p, quant, sizeof quant);
+        const void* d_quant;
+        CK_TRY(ck_to_device(ctx, ctx->host_pinned2.p, sizeof quant, CK_HOST, ctx->in_stage2, &d_quant));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the pass stages its own words in that pinned block)
+        for (int f0 = 0; f0 < n; f0 += pass) {
+            const int m = n - f0 < pass ? n - f0 : pass;
+            const void* d_in;
+            CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
+            CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, m, h, w, sampling, (int16_t*)ctx->out_stage.p));
+            int bad = -1;
+            std::string why;
+            const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)ctx->out_stage.p, quant, m, h, w, sampling, restart_interval,
+                                              out + (size_t)f0 * stride, stride, len + f0, &bad, why);
+            if (rc != CK_OK && bad < 0) return rc;
+            if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+        }
+        return CK_OK;
+    }
     const int pass = jpeg_pass_frames(n, cframe);
     // per pass: frames up (when they are the host's) -> the kernel -> the coefficients down in one copy into the pinned
     // block -> the Huffman coder on the worker threads.  The stream is idle while they code, as in ck_jpeg_decode.
@@ -1083,6 +1268,7 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
         CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, m, h, w, sampling, (int16_t*)ctx->out_stage.p));
         CK_TRY(ck_from_device(ctx, ctx->host_pinned.p, ctx->out_stage.p, (size_t)m * cframe, CK_HOST));
         CK_TRY(finish(ctx));
+        ctx->jpeg_downloaded += (long long)((size_t)m * cframe);
         int bad = -1;
         std::string why;
         const int rc = jpeg_encode_batch((const int16_t*)ctx->host_pinned.p, quant, m, h, w, sampling, restart_interval,

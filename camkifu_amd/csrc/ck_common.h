@@ -21,6 +21,7 @@
 #include "../../include/camkifu_amd.h"
 #include "ck_buf.h"        // DevBuf, PinBuf: buffers that free themselves
 #include "ck_cnn_pack.h"   // the classifier's weight arrays and their packs (host only)
+#include "ck_jpeg_enc_stage.h"   // CkEncGeom: the steps of the encoder's Huffman stage (plain C++)
 
 // the context's stream, destroyed with it
 struct CkStream {
@@ -131,6 +132,9 @@ struct ck_ctx {
     DevBuf rec_stage;    // the device twin of rec_host, for records that live in HBM
     DevBuf harvest;      // ck_harvest_patches / ck_augment_patches: the small host inputs, the flags' codes, the block totals
     DevBuf harvest_src;  // staged (frame, region) pairs of a harvest that goes to the host
+    DevBuf jenc_work;    // the encoder's Huffman stage on the device: sizes and offsets of a pass (CkEncWork),
+    DevBuf jenc_bits;    // its unstuffed bits and the FF counts of their byte tiles,
+    DevBuf jenc_pack;    // and its streams, one behind the other
 
     CnnWeights cnn;
     int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
@@ -141,6 +145,8 @@ struct ck_ctx {
     int jpeg_bad_frame = -1;         // ck_jpeg_decode: the frame its last CK_ERR_DATA is about (-1: none)
     long long jpeg_uploaded = 0;     // bytes the last ck_jpeg_decode / ck_jpeg_coefficients_device copied to the device
     int jpeg_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_decode runs the Huffman stage (ck_jpeg_set_entropy)
+    int jpeg_enc_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_encode runs the Huffman stage (ck_jpeg_set_encode_entropy)
+    long long jpeg_downloaded = 0;   // bytes the last ck_jpeg_encode / ck_jpeg_entropy_encode_device copied from the device
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
@@ -290,6 +296,23 @@ struct CkHuffSet;
 struct CkStrandGeom;
 int k_jpeg_huff(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const CkStrand* d_rows, int n_strands, const CkHuffSet* d_sets,
                 int n_sets, const CkStrandGeom& g, long long cframe, int n_frames, int16_t* d_coef, uint32_t* d_status);
+// the Huffman stage of the encoder on the device (k_jpeg_enc_huff.hip), m frames of one geometry.  CkEncWork: where the sizes
+// and offsets of a pass lie in HBM -- per block, per block tile, per segment (seg_u0: nseg + 1 per frame) and per frame
+// (frame_u0, out_off: m + 1); head[0] the lowest (frame << 32 | block) that cannot be coded or all ones, head[1] the bytes of
+// the bit buffer; consts: the CkEncTables, the zigzag order (64 bytes) and the stream header.
+struct CkEncWork {
+    uint32_t *bits, *tile_bits;
+    uint64_t *tile_off, *seg_bits, *seg_u0, *frame_u0, *head, *len, *out_off;
+    const uint8_t* consts;
+};
+// size every block and scan: fills all of the above but len and out_off
+int k_jpeg_enc_measure(ck_ctx* ctx, const int16_t* d_coef, int m, const CkEncGeom& g, const CkEncWork& w);
+// the codes into d_buf (total_u = head[1] bytes, zeroed here), the FF counts of its byte tiles, w.len and w.out_off
+int k_jpeg_enc_put(ck_ctx* ctx, const int16_t* d_coef, int m, const CkEncGeom& g, const CkEncWork& w, uint32_t* d_buf, uint64_t total_u,
+                   uint32_t* d_ff_cnt, uint32_t* d_ff_off, uint32_t hl);
+// headers, stuffed bytes and markers into d_pack (pack_bytes of room), frame f at out_off[f]
+int k_jpeg_enc_stuff(ck_ctx* ctx, int m, const CkEncGeom& g, const CkEncWork& w, const uint32_t* d_buf, uint64_t total_u,
+                     const uint32_t* d_ff_off, uint32_t hl, uint8_t* d_pack, uint64_t pack_bytes);
 // overlays (k_overlay.hip): n_work non-empty bins of the plan of ck_overlay.cpp, drawn in place on images of h x w x c
 int k_overlay(ck_ctx* ctx, uint8_t* d_img, int h, int w, int c, const int32_t* d_work, int n_work, const int32_t* d_refs,
               const int32_t* d_recs, const uint8_t* d_text);

@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 namespace {
 
 // Annex K.1 and K.2, natural order
@@ -17,7 +19,7 @@ const uint8_t BASE_CHROMA[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66,
                                  99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
 
-constexpr size_t HEADER_BOUND = 1024;        // SOI, APP0, 2 DQT, SOF0, 4 DHT, DRI, SOS, EOI: 629 bytes
+constexpr size_t HEADER_BOUND = CK_JPEG_ENC_HEADER_BOUND;   // SOI, APP0, 2 DQT, SOF0, 4 DHT, DRI, SOS, EOI: 629 bytes
 constexpr size_t BLOCK_BOUND = 64 * 26 / 8 * 2;
 
 int refuse(char* msg, const char* fmt, ...)
@@ -29,30 +31,14 @@ int refuse(char* msg, const char* fmt, ...)
     return CK_ERR_ARG;
 }
 
-// symbol -> code and length (0: the table has no such symbol)
-struct EncHuff {
-    uint16_t code[256];
-    uint8_t len[256];
-    EncHuff(const uint8_t* bits, const uint8_t* vals)
-    {
-        memset(code, 0, sizeof code);
-        memset(len, 0, sizeof len);
-        int c = 0, k = 0;
-        for (int l = 1; l <= 16; l++) {
-            for (int i = 0; i < bits[l - 1]; i++, c++, k++) { code[vals[k]] = (uint16_t)c; len[vals[k]] = (uint8_t)l; }
-            c <<= 1;
-        }
-    }
-};
-
-struct Tables {
-    EncHuff dc[2] = {EncHuff(STD_DC_LUMA_BITS, STD_DC_VALS), EncHuff(STD_DC_CHROMA_BITS, STD_DC_VALS)};
-    EncHuff ac[2] = {EncHuff(STD_AC_LUMA_BITS, STD_AC_LUMA_VALS), EncHuff(STD_AC_CHROMA_BITS, STD_AC_CHROMA_VALS)};
-};
-const Tables& tables()
+void fill(CkEncHuff& t, const uint8_t* bits, const uint8_t* vals)
 {
-    static const Tables t;
-    return t;
+    memset(&t, 0, sizeof t);
+    int c = 0, k = 0;
+    for (int l = 1; l <= 16; l++) {
+        for (int i = 0; i < bits[l - 1]; i++, c++, k++) { t.code[vals[k]] = (uint16_t)c; t.len[vals[k]] = (uint8_t)l; }
+        c <<= 1;
+    }
 }
 
 // bytes appended to a buffer of known end; the callers leave room before they write
@@ -83,15 +69,46 @@ struct BitWriter {
     void pad() { if (n) put((1u << (8 - n)) - 1, 8 - n); }
 };
 
-inline int bit_size(int v)
+// what both coders refuse before they read a coefficient, in one order
+int check_args(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval, const uint8_t* out,
+               const size_t* len, char* msg)
 {
-    unsigned a = (unsigned)(v < 0 ? -v : v);
-    int s = 0;
-    while (a) { s++; a >>= 1; }
-    return s;
+    if (!coef || !quant || !out || !len) return refuse(msg, "NULL pointer");
+    if (h < 1 || w < 1 || h > 65535 || w > 65535) return refuse(msg, "bad JPEG frame size %dx%d: sides of 1 .. 65535", w, h);
+    if (sampling < CK_JPEG_GREY || sampling > CK_JPEG_420) return refuse(msg, "bad JPEG sampling %d", sampling);
+    if (restart_interval < 0 || restart_interval > 65535) return refuse(msg, "restart interval %d: 0 .. 65535 MCUs", restart_interval);
+    const bool grey = sampling == CK_JPEG_GREY;
+    for (int i = 0; i < (grey ? 64 : 192); i++)
+        if (quant[i] < 1 || quant[i] > 255) return refuse(msg, "quant entry %d is %d: baseline tables hold 1 .. 255", i, quant[i]);
+    if (!grey && memcmp(quant + 64, quant + 128, 64 * sizeof(uint16_t)) != 0) return refuse(msg, "Cb and Cr share one quant table");
+    return CK_OK;
 }
 
 }  // namespace
+
+int ck_jpeg_enc_check(const uint16_t* quant, int h, int w, int sampling, int restart_interval, char* msg)
+{
+    static const int16_t some = 0;
+    static const size_t one = 0;
+    static const uint8_t byte = 0;
+    msg[0] = 0;
+    return check_args(&some, quant, h, w, sampling, restart_interval, &byte, &one, msg);
+}
+
+const CkEncTables& ck_jpeg_enc_tables()
+{
+    static const CkEncTables t = [] {
+        CkEncTables x;
+        fill(x.dc[0], STD_DC_LUMA_BITS, STD_DC_VALS);
+        fill(x.dc[1], STD_DC_CHROMA_BITS, STD_DC_VALS);
+        fill(x.ac[0], STD_AC_LUMA_BITS, STD_AC_LUMA_VALS);
+        fill(x.ac[1], STD_AC_CHROMA_BITS, STD_AC_CHROMA_VALS);
+        return x;
+    }();
+    return t;
+}
+
+const uint8_t* ck_jpeg_enc_zigzag() { return ZIGZAG; }
 
 void ck_jpeg_enc_quant(int quality, uint16_t* quant)
 {
@@ -112,23 +129,11 @@ size_t ck_jpeg_enc_bound(int h, int w, int sampling)
     return HEADER_BOUND + (size_t)ck_jpeg_blocks(h, w, sampling) * BLOCK_BOUND + mcus * 4;
 }
 
-int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
-                        uint8_t* out, size_t cap, size_t* len, char* msg)
+// in libjpeg's order
+size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* out)
 {
-    msg[0] = 0;
-    if (len) *len = 0;
-    if (!coef || !quant || !out || !len) return refuse(msg, "NULL pointer");
-    if (h < 1 || w < 1 || h > 65535 || w > 65535) return refuse(msg, "bad JPEG frame size %dx%d: sides of 1 .. 65535", w, h);
-    if (sampling < CK_JPEG_GREY || sampling > CK_JPEG_420) return refuse(msg, "bad JPEG sampling %d", sampling);
-    if (restart_interval < 0 || restart_interval > 65535) return refuse(msg, "restart interval %d: 0 .. 65535 MCUs", restart_interval);
     const bool grey = sampling == CK_JPEG_GREY;
     const int ncomp = grey ? 1 : 3;
-    for (int i = 0; i < (grey ? 64 : 192); i++)
-        if (quant[i] < 1 || quant[i] > 255) return refuse(msg, "quant entry %d is %d: baseline tables hold 1 .. 255", i, quant[i]);
-    if (!grey && memcmp(quant + 64, quant + 128, 64 * sizeof(uint16_t)) != 0) return refuse(msg, "Cb and Cr share one quant table");
-    if (cap < HEADER_BOUND) return refuse(msg, "output buffer of %zu bytes: too small for the headers", cap);
-
-    // ---- headers, in libjpeg's order ----
     Out o{out};
     o.byte(0xFF); o.byte(0xD8);
     static const uint8_t JFIF[14] = {0x4A, 0x46, 0x49, 0x46, 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
@@ -159,14 +164,28 @@ int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w
     o.byte((unsigned)ncomp);
     for (int c = 0; c < ncomp; c++) { o.byte((unsigned)c + 1); o.byte(c ? 0x11u : 0x00u); }
     o.byte(0); o.byte(63); o.byte(0);
+    return (size_t)(o.p - out);
+}
+
+int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
+                        uint8_t* out, size_t cap, size_t* len, char* msg)
+{
+    msg[0] = 0;
+    if (len) *len = 0;
+    if (const int rc = check_args(coef, quant, h, w, sampling, restart_interval, out, len, msg)) return rc;
+    if (cap < HEADER_BOUND) return refuse(msg, "output buffer of %zu bytes: too small for the headers", cap);
+    const bool grey = sampling == CK_JPEG_GREY;
+    const int ncomp = grey ? 1 : 3;
+    const int hs = ck_jpeg_luma_h(sampling), vs = ck_jpeg_luma_v(sampling);
+    uint8_t* const scan = out + ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, out);
 
     // ---- the scan ----
-    const Tables& T = tables();
+    const CkEncTables& T = ck_jpeg_enc_tables();
     const int mcux = (w + 8 * hs - 1) / (8 * hs), mcuy = (h + 8 * vs - 1) / (8 * vs);
     const int lw = mcux * hs, lh = mcuy * vs;
     const size_t base[3] = {0, (size_t)lw * lh, (size_t)lw * lh + (size_t)mcux * mcuy};
     const uint8_t* const end = out + cap;
-    BitWriter bw{o.p};
+    BitWriter bw{scan};
     int pred[3] = {0, 0, 0};
     int since = 0, nrst = 0;
     const long long total = (long long)mcux * mcuy;
@@ -187,14 +206,14 @@ int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w
         for (int c = 0; c < ncomp; c++) {
             const int bh = (c == 0 && !grey) ? hs : 1, bv = (c == 0 && !grey) ? vs : 1;
             const int gw = c == 0 ? lw : mcux;
-            const EncHuff& dc = T.dc[c ? 1 : 0];
-            const EncHuff& ac = T.ac[c ? 1 : 0];
+            const CkEncHuff& dc = T.dc[c ? 1 : 0];
+            const CkEncHuff& ac = T.ac[c ? 1 : 0];
             for (int v = 0; v < bv; v++)
                 for (int u = 0; u < bh; u++) {
                     const int16_t* blk = coef + (base[c] + (size_t)(my * bv + v) * gw + (size_t)(mx * bh + u)) * 64;
                     const int diff = (int)blk[0] - pred[c];
                     pred[c] = blk[0];
-                    int s = bit_size(diff);
+                    int s = ck_enc_bit_size(diff);
                     if (s > 11) return refuse(msg, "DC difference of %d bits (MCU %lld): baseline JPEG has 11", s, mcu);
                     bw.put(dc.code[s], dc.len[s]);
                     if (s) bw.put((uint32_t)(diff < 0 ? diff - 1 : diff), s);
@@ -203,7 +222,7 @@ int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w
                         const int val = blk[ZIGZAG[k]];
                         if (val == 0) { run++; continue; }
                         for (; run > 15; run -= 16) bw.put(ac.code[0xF0], ac.len[0xF0]);
-                        s = bit_size(val);
+                        s = ck_enc_bit_size(val);
                         if (s > 10) return refuse(msg, "AC value of %d bits (MCU %lld): baseline JPEG has 10", s, mcu);
                         const int sym = (run << 4) | s;
                         bw.put(ac.code[sym], ac.len[sym]);
@@ -218,5 +237,129 @@ int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w
     bw.pad();
     *bw.p++ = 0xFF; *bw.p++ = 0xD9;
     *len = (size_t)(bw.p - out);
+    return CK_OK;
+}
+
+void ck_jpeg_enc_status_message(uint32_t status, long long mcu, char* msg)
+{
+    const int size = (int)(status & 255);
+    if (((status >> 8) & 255) == CK_ENC_DC) snprintf(msg, CK_JPEG_MSG, "DC difference of %d bits (MCU %lld): baseline JPEG has 11", size, mcu);
+    else snprintf(msg, CK_JPEG_MSG, "AC value of %d bits (MCU %lld): baseline JPEG has 10", size, mcu);
+}
+
+// The steps of ck_jpeg_enc_stage.h in plain loops, tile by tile as the kernels of k_jpeg_enc_huff.hip run them.
+int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                       uint8_t* out, size_t stride, size_t* len, int* bad, char* msg)
+{
+    msg[0] = 0;
+    *bad = -1;
+    if (len) for (int f = 0; f < n; f++) len[f] = 0;
+    if (const int rc = check_args(coef, quant, h, w, sampling, restart_interval, out, len, msg)) { *bad = 0; return rc; }
+    if (stride < ck_jpeg_enc_bound(h, w, sampling)) { *bad = 0; return refuse(msg, "output buffer of %zu bytes: too small for the headers", stride); }
+    const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
+    const CkEncTables& T = ck_jpeg_enc_tables();
+    const size_t cframe = (size_t)g.blocks * 64;
+    const int64_t ftiles = g.nseg * g.seg_tiles;
+
+    // size: every block, the bit sums of the tiles, the lowest (frame, block) that cannot be coded
+    std::vector<uint32_t> bits((size_t)n * g.blocks), tile_bits((size_t)n * ftiles, 0);
+    uint64_t fail = ~(uint64_t)0;
+    for (int f = 0; f < n; f++)
+        for (int64_t k = 0; k < g.nseg; k++)
+            for (int64_t t = 0; t < g.seg_tiles; t++) {
+                int64_t b0;
+                int cnt;
+                ck_enc_tile_blocks(g, k, t, &b0, &cnt);
+                for (int i = 0; i < cnt; i++) {
+                    const int64_t b = b0 + i, pb = ck_enc_pred_block(g, b);
+                    const int16_t* fc = coef + (size_t)f * cframe;
+                    const int pred = pb < 0 ? 0 : fc[ck_enc_place(g, pb) * 64];
+                    const uint32_t r = ck_enc_block_bits(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &T, ZIGZAG);
+                    bits[(size_t)f * g.blocks + b] = r;
+                    if (r & CK_ENC_FAIL) { const uint64_t key = ((uint64_t)f << 32) | (uint64_t)b; if (key < fail) fail = key; }
+                    else tile_bits[((size_t)f * g.nseg + k) * g.seg_tiles + t] += r;
+                }
+            }
+    if (fail != ~(uint64_t)0) {
+        *bad = (int)(fail >> 32);
+        const int64_t b = (int64_t)(fail & 0xffffffffu);
+        ck_jpeg_enc_status_message(bits[(size_t)*bad * g.blocks + b], b / g.mcu_blocks, msg);
+        return CK_ERR_ARG;
+    }
+
+    // scan: tiles in their segment, segments in their frame, frames in the bit buffer
+    std::vector<uint64_t> tile_off((size_t)n * ftiles), seg_u0((size_t)n * (g.nseg + 1)), seg_bits((size_t)n * g.nseg), frame_u0((size_t)n + 1);
+    uint64_t at = 0;
+    for (int f = 0; f < n; f++) {
+        uint64_t u = 0;
+        for (int64_t k = 0; k < g.nseg; k++) {
+            uint64_t sum = 0;
+            for (int64_t t = 0; t < g.seg_tiles; t++) {
+                const size_t ti = ((size_t)f * g.nseg + k) * g.seg_tiles + t;
+                tile_off[ti] = sum;
+                sum += tile_bits[ti];
+            }
+            seg_bits[(size_t)f * g.nseg + k] = sum;
+            seg_u0[(size_t)f * (g.nseg + 1) + k] = u;
+            u += ck_enc_seg_bytes(sum);
+        }
+        seg_u0[(size_t)f * (g.nseg + 1) + g.nseg] = u;
+        frame_u0[f] = at;
+        at += ck_enc_up(u, CK_ENC_TILE_BYTES);
+    }
+    frame_u0[n] = at;
+
+    // put: every tile into words of its own, then into the zeroed buffer
+    std::vector<uint32_t> buf(at / 4, 0), words(CK_ENC_TILE_WORDS);
+    for (int f = 0; f < n; f++)
+        for (int64_t k = 0; k < g.nseg; k++)
+            for (int64_t t = 0; t < g.seg_tiles; t++) {
+                int64_t b0;
+                int cnt;
+                ck_enc_tile_blocks(g, k, t, &b0, &cnt);
+                if (!cnt) continue;
+                const size_t ti = ((size_t)f * g.nseg + k) * g.seg_tiles + t;
+                const uint64_t sbits = seg_bits[(size_t)f * g.nseg + k];
+                const uint64_t p0 = 8 * (frame_u0[f] + seg_u0[(size_t)f * (g.nseg + 1) + k]) + tile_off[ti];
+                const bool last = tile_off[ti] + tile_bits[ti] == sbits;        // (a tile with blocks has bits)
+                const uint32_t nbits = tile_bits[ti] + (last ? (uint32_t)ck_enc_seg_pad(sbits) : 0);
+                const int nw = (int)(((p0 & 31) + nbits + 31) / 32);
+                memset(words.data(), 0, (size_t)nw * sizeof(uint32_t));
+                CkEncWordSink<CkEncPlainOr> sink{words.data(), (uint32_t)(p0 & 31)};
+                for (int i = 0; i < cnt; i++) {
+                    const int64_t b = b0 + i, pb = ck_enc_pred_block(g, b);
+                    const int16_t* fc = coef + (size_t)f * cframe;
+                    const int pred = pb < 0 ? 0 : fc[ck_enc_place(g, pb) * 64];
+                    ck_enc_block_put(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &T, ZIGZAG, sink);
+                }
+                if (last && ck_enc_seg_pad(sbits)) sink.put((1u << ck_enc_seg_pad(sbits)) - 1, ck_enc_seg_pad(sbits));
+                for (int i = 0; i < nw; i++) {
+                    uint32_t* dst = buf.data() + (p0 >> 5) + i;
+                    if (ck_enc_flush_how(i, nw)) *dst |= ck_enc_bswap(words[i]); else *dst = ck_enc_bswap(words[i]);
+                }
+            }
+
+    // stuff: FF bytes of the byte tiles, their sums before a tile in its frame, then every byte to its place
+    const uint8_t* bytes = (const uint8_t*)buf.data();
+    uint8_t header[CK_JPEG_ENC_HEADER_BOUND];
+    const size_t hl = ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, header);
+    for (int f = 0; f < n; f++) {
+        const uint64_t* su = seg_u0.data() + (size_t)f * (g.nseg + 1);
+        const uint64_t u = su[g.nseg];
+        uint8_t* o = out + (size_t)f * stride;
+        memcpy(o, header, hl);
+        uint64_t ff = 0;
+        for (uint64_t t0 = 0; t0 < u; t0 += CK_ENC_TILE_BYTES) {
+            const uint64_t t1 = t0 + CK_ENC_TILE_BYTES < u ? t0 + CK_ENC_TILE_BYTES : u;
+            uint64_t in_tile = 0;
+            for (uint64_t i = t0; i < t1; i++) {
+                const unsigned c = bytes[frame_u0[f] + i];
+                ck_enc_emit(o + hl, o + stride, su, g.nseg, i, c, ff + in_tile);
+                in_tile += c == 0xFF;
+            }
+            ff += in_tile;
+        }
+        len[f] = (size_t)ck_enc_stream_len(hl, u, ff, g.nseg);
+    }
     return CK_OK;
 }

@@ -6,6 +6,9 @@
 #include <stdint.h>
 
 #include "ck_jpeg.h"
+#include "ck_jpeg_enc_stage.h"
+
+#define CK_JPEG_ENC_HEADER_BOUND 1024   // SOI, APP0, 2 DQT, SOF0, 4 DHT, DRI, SOS, EOI: 629 bytes
 
 // jpeg_set_quality(quality, force_baseline) over the tables of Annex K.1 / K.2 -> quant[3][64], natural order, by component
 // (Y, Cb, Cr; the two chroma tables are equal).  quality is clamped to 1 .. 100.
@@ -22,3 +25,24 @@ size_t ck_jpeg_enc_bound(int h, int w, int sampling);
 // is written beyond cap, whatever the coefficients are.  msg (CK_JPEG_MSG bytes) says why.
 int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
                         uint8_t* out, size_t cap, size_t* len, char* msg);
+
+// the encode tables of Annex K.3 (built once) and the zigzag order, as the steps of ck_jpeg_enc_stage.h take them
+const CkEncTables& ck_jpeg_enc_tables();
+const uint8_t* ck_jpeg_enc_zigzag();
+
+// everything in front of the entropy-coded data, in libjpeg's order -> out (CK_JPEG_ENC_HEADER_BOUND bytes of room); returns
+// the bytes written.  The arguments are those ck_jpeg_enc_entropy has accepted.
+size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* out);
+
+// what ck_jpeg_enc_entropy refuses before it reads a coefficient (geometry, restart interval, quant tables), with its message
+int ck_jpeg_enc_check(const uint16_t* quant, int h, int w, int sampling, int restart_interval, char* msg);
+
+// a status word of ck_enc_block_bits (ck_jpeg_enc_stage.h) as ck_jpeg_enc_entropy words the refusal
+void ck_jpeg_enc_status_message(uint32_t status, long long mcu, char* msg);
+
+// ck_jpeg_enc_entropy for n frames (coef: n frames end to end, out + f * stride, len[f]) through the steps of
+// ck_jpeg_enc_stage.h -- size, scan, put, stuff -- in plain loops over the tiles the kernels of k_jpeg_enc_huff.hip use: the
+// same bytes, the same refusals.  On a refusal *bad is the lowest frame that has one and msg what ck_jpeg_enc_entropy says
+// of it (the lowest MCU); every len[f] is 0 then.  stride is at least ck_jpeg_enc_bound.
+int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                       uint8_t* out, size_t stride, size_t* len, int* bad, char* msg);

@@ -209,6 +209,26 @@ int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, in
  * come down in one copy into pinned memory of the context (a large batch in passes of about 256 MB each). */
 int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
                    int restart_interval, uint8_t* out, size_t stride, size_t* len);
+/* The Huffman stage of the encoder on the GPU (CK_JPEG_ENTROPY_DEVICE, as for decoding): every block sizes its own code, prefix
+ * sums place the blocks and the stuffed bytes, and only the finished streams come down -- in one copy per pass, frames end
+ * to end on 16 bytes, behind two small copies of sizes (16 bytes, then 8 bytes per frame).  Byte for byte the streams of the
+ * host coder, with its refusals.  A pass holds what ck_jpeg_encode's rule gives, its coefficients at most 2 GiB of HBM. */
+/* what ck_jpeg_encode does from now on; a new context has CK_JPEG_ENTROPY_HOST */
+int ck_jpeg_set_encode_entropy(ck_ctx* ctx, int mode);
+/* ck_jpeg_entropy_encode with the Huffman stage on the GPU: coef in `in_space` (16-byte aligned on the device), quant in HOST
+ * memory -> n streams in HOST memory at out + f * stride, len[f] bytes.  Same refusals, same frame, same message. */
+int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                  int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len);
+/* the bytes the context's last ck_jpeg_encode / ck_jpeg_entropy_encode_device copied from device to host, all passes: the
+ * coefficients in the host mode; the streams, each rounded up to 16 bytes, and 16 + 8 * frames bytes of sizes per pass in
+ * the device mode */
+int ck_jpeg_downloaded_bytes(ck_ctx* ctx, long long* bytes);
+/* host only: ck_jpeg_entropy_encode through the steps the GPU kernels run -- size, scan, put, stuff -- in plain loops over the
+ * same tiles -> the same streams, the same refusals */
+int ck_jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                  uint8_t* out, size_t stride, size_t* len);
+/* the tiles of those steps: blocks whose codes one workgroup assembles, unstuffed bytes one workgroup places (host only) */
+int ck_jpeg_enc_tiles(int32_t* blocks_per_tile, int32_t* bytes_per_tile);
 
 /* ---- overlays: the finders' debug drawing (cv2.line / circle / rectangle / putText)   core/imgutil.py:71-118,
  * board/boardfinder.py:121-134, stone/stonesfinder.py:779-885, core/video.py:223-271

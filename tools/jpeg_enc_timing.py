@@ -8,6 +8,10 @@ Frames of a filmed game (synth.film) at 1920x1080, resident in HBM; 4:2:0, quali
 2. host: the Huffman coder alone (capi.jpeg_entropy_encode), ms per frame -- one frame per call (one thread) and the whole
    batch per call (the library's worker threads, at most 16).
 3. end to end: Context.jpeg_encode of the batch in HBM -> a list of bytes, frames/s.
+4. device_entropy: the Huffman stage on the GPU (jpeg_set_encode_entropy("device")) against the host mode in the same
+   run: HIP-event time per frame of its four kernels beside the forward kernel, the bytes that come down per frame in both
+   modes, jpeg_encode frames/s in both modes at 128, 32, 8 and 1 frames a call (alternating rounds), and
+   tools/transcode.record_gobans on a 128-frame film in both modes.  The streams of both modes are compared.
 Every leg is warmed up and runs `--reps` rounds: median / min / max.
 
     python tools/jpeg_enc_timing.py [--size 1920x1080] [--n 32] [--reps 7] [--inner 8]
@@ -25,6 +29,86 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from ingest_timing import HBM_PEAK, spread_of  # noqa: E402
+
+
+KERNELS = ("jpeg_enc_size", "jpeg_enc_scan", "jpeg_enc_put", "jpeg_enc_stuff")
+
+
+def _fps(ctx, frames, quality, S, reps):
+    """frames/s of jpeg_encode in the host and the device mode, alternating rounds"""
+    n = frames.shape[0]
+    calls = max(2, 256 // n)                                 # (a round codes at least 256 frames in each mode)
+    secs = {"host": [], "device": []}
+    for mode in ("host", "device"):
+        ctx.jpeg_set_encode_entropy(mode)
+        ctx.jpeg_encode(frames, quality=quality, sampling=S)
+    for _ in range(reps):
+        for mode in ("host", "device"):
+            ctx.jpeg_set_encode_entropy(mode)
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                ctx.jpeg_encode(frames, quality=quality, sampling=S)
+            secs[mode].append((time.perf_counter() - t0) / calls)
+    ctx.jpeg_set_encode_entropy("host")
+    res = {}
+    for mode, ts in secs.items():
+        fps = sorted(n / t for t in ts)
+        res[mode] = dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1), rounds=len(fps))
+    res["device_over_host"] = round(res["device"]["median"] / res["host"]["median"], 3)
+    return res
+
+
+def device_entropy(ctx, capi, synth, dev, film, h, w, S, args):
+    import tempfile
+
+    import torch
+    n, q = film.shape[0], args.quality
+    res = {}
+    ctx.jpeg_set_encode_entropy("host")
+    want = ctx.jpeg_encode(film, quality=q, sampling=S)
+    host_down = ctx.jpeg_downloaded_bytes()
+    ctx.jpeg_set_encode_entropy("device")
+    res["streams_equal_the_host_modes"] = bool(ctx.jpeg_encode(film, quality=q, sampling=S) == want)
+    res["downloaded_bytes_per_frame"] = dict(host=host_down // n, device=ctx.jpeg_downloaded_bytes() // n)
+    # the kernels
+    ctx.timing_enable(True)
+    per = {k: [] for k in ("jpeg_enc",) + KERNELS}
+    for _ in range(args.reps):
+        ctx.timing_reset()
+        ctx.jpeg_encode(film, quality=q, sampling=S)
+        for k in per:
+            per[k].append(ctx.timing_get(k)[0] / n)
+    ctx.timing_enable(False)
+    ctx.jpeg_set_encode_entropy("host")
+    res["kernel_ms_per_frame"] = {("jpeg_forward" if k == "jpeg_enc" else k): spread_of(v) for k, v in per.items()}
+    # frames/s by batch size
+    res["encode_frames_per_s"] = {}
+    for b in (128, 32, 8, 1):
+        frames = film if b == n else (film[:b].contiguous() if b < n else film.repeat((b + n - 1) // n, 1, 1, 1)[:b].contiguous())
+        res["encode_frames_per_s"]["%d_frames_a_call" % b] = _fps(ctx, frames, q, S, args.reps)
+        del frames
+    # record_gobans on a 128-frame film of 640 x 480
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import transcode
+    from camkifu_amd.stone.nn_manager import NNManager
+    small = synth.film(128, 480, 640, seed=8, quiet=8, move_every=30, hand_frames=12)[0].numpy()
+    ctx.cnn_set_weights(NNManager.init_net())
+    rec = {"host": [], "device": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        for rnd in range(1 + max(3, args.reps // 2)):
+            for mode in ("host", "device"):
+                ctx.jpeg_set_encode_entropy(mode)
+                t0 = time.perf_counter()
+                transcode.record_gobans(small, os.path.join(tmp, mode + ".avi"), quality=q, batch=32, ctx=ctx, bg_init_frames=6)
+                if rnd:
+                    rec[mode].append(time.perf_counter() - t0)
+        with open(os.path.join(tmp, "host.avi"), "rb") as a, open(os.path.join(tmp, "device.avi"), "rb") as b:
+            res["record_gobans_files_equal"] = bool(a.read() == b.read())
+    ctx.jpeg_set_encode_entropy("host")
+    res["record_gobans_128_frames_s"] = {m: dict(median=round(float(np.median(t)), 4), min=round(min(t), 4), max=round(max(t), 4),
+                                                  rounds=len(t)) for m, t in rec.items()}
+    torch.cuda.synchronize()
+    return res
 
 
 def main(argv=None):
@@ -106,6 +190,7 @@ def main(argv=None):
         out["end_to_end"] = dict(frames_per_s=dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1),
                                                    spread=round((fps[-1] - fps[0]) / float(np.median(fps)), 4), rounds=len(fps)),
                                  frames_resident_in_hbm=True, two_halves_equal_encode=bool(same))
+        out["device_entropy"] = device_entropy(ctx, capi, synth, dev, film, h, w, S, args)
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

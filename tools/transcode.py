@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Write a film as Motion-JPEG: frames are encoded on the GPU (capi.Context.jpeg_encode: the forward kernel, then the
-Huffman coder on the host's worker threads) and appended to an .avi through core.capture.MjpegWriter.
+Huffman coder on the host's worker threads or, with --encode-entropy device, on the GPU as well: the same bytes) and
+appended to an .avi through core.capture.MjpegWriter.
 
-    python tools/transcode.py SRC OUT.avi [--quality Q] [--sampling 420|422|444|grey] [--batch N]
+    python tools/transcode.py SRC OUT.avi [--quality Q] [--sampling 420|422|444|grey] [--batch N] [--encode-entropy host|device]
     python tools/transcode.py SRC OUT.avi --gobans [--annotate] [--sgf game.sgf]
     python tools/transcode.py SRC OUT.avi --annotate [--sgf game.sgf]
 
@@ -179,6 +180,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--restart", default="0", metavar="N|row", help="restart markers every N MCUs, or every MCU row: the pieces "
                     "the device entropy mode decodes in parallel (plain transcoding only)")
+    ap.add_argument("--encode-entropy", choices=("host", "device"), default="host", help="where the encoder's Huffman stage "
+                    "runs: the host's worker threads, or the GPU (only the finished streams come down); the bytes are the same")
     ap.add_argument("--gobans", action="store_true", help="record the 380x380 goban images of a pipeline run instead of the frames")
     ap.add_argument("--annotate", action="store_true", help="draw what the finders concluded onto the frames, on the GPU; "
                     "without --gobans the analysed frames are written at full size")
@@ -187,14 +190,15 @@ def main(argv=None):
     if not args.out.lower().endswith(".avi"):
         raise SystemExit("the output is a Motion-JPEG .avi file")
     sampling = SAMPLINGS[args.sampling]
+    from camkifu_amd import capi
+    ctx = capi.get_context()
+    ctx.jpeg_set_encode_entropy(args.encode_entropy)
     if not args.gobans and not args.annotate:
-        res = transcode(args.src, args.out, args.quality, sampling, args.batch, restart=args.restart)
+        res = transcode(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx, restart=args.restart)
         print("%s: %d frames of %dx%d at %.3g fps, %d bytes" % (args.out, res["frames"], res["w"], res["h"], res["fps"], res["bytes"]))
         return res
     import time
-    from camkifu_amd import capi
     from camkifu_amd.stone.nn_manager import NNManager
-    ctx = capi.get_context()
     ctx.cnn_set_weights(NNManager.get_net())
     t0 = time.time()
     res = record_gobans(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx, annotate=args.annotate,

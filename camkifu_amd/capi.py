@@ -19,6 +19,7 @@ CK_OK, CK_ERR_ARG, CK_ERR_HIP, CK_ERR_CAPACITY, CK_ERR_STATE, CK_ERR_DATA = 0, 1
 CK_HOST, CK_DEVICE = 0, 1
 CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
 CK_JPEG_ENTROPY_HOST, CK_JPEG_ENTROPY_DEVICE = 0, 1
+CK_JPEG_ENTROPY_DEVICE_SPANS = 2
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
@@ -449,11 +450,24 @@ class Context:
 
     def jpeg_set_entropy(self, mode):
         """where jpeg_decode runs the Huffman stage from now on: "host" (the default: the library's worker threads) or
-        "device" (one GPU lane per restart interval; the compressed bytes go up instead of the coefficients)"""
-        modes = {"host": CK_JPEG_ENTROPY_HOST, "device": CK_JPEG_ENTROPY_DEVICE}
+        "device" (one GPU lane per restart interval; the compressed bytes go up instead of the coefficients), or
+        "device-spans" (the same upload, decoded in parallel inside a restart interval as well: a lane per span of
+        jpeg_set_span_bytes bytes)"""
+        modes = {"host": CK_JPEG_ENTROPY_HOST, "device": CK_JPEG_ENTROPY_DEVICE, "device-spans": CK_JPEG_ENTROPY_DEVICE_SPANS}
         if mode not in modes:
-            raise CkError("jpeg entropy mode: 'host' or 'device' is needed, got %r" % (mode,))
+            raise CkError("jpeg entropy mode: 'host' or 'device' is needed (or 'device-spans'), got %r" % (mode,))
         self._chk(lib().ck_jpeg_set_entropy(self._h, modes[mode]))
+
+    def jpeg_set_span_bytes(self, nbytes):
+        """the span size of the "device-spans" mode, 8 .. 4096 bytes (jpeg_span_bytes() gives the default)"""
+        self._chk(lib().ck_jpeg_set_span_bytes(self._h, int(nbytes)))
+
+    def jpeg_span_stats(self):
+        """what the last jpeg_decode / jpeg_coefficients_device of this context did in "device-spans" mode -> dict(spans,
+        unresolved, suspect_strands, one_lane_frames)"""
+        st = (C.c_longlong * 4)()
+        self._chk(lib().ck_jpeg_span_stats(self._h, st))
+        return dict(zip(JPEG_SPAN_STATS, (int(v) for v in st)))
 
     def jpeg_uploaded_bytes(self):
         """the bytes the last jpeg_decode or jpeg_coefficients_device of this context copied from host to device"""
@@ -1158,6 +1172,41 @@ def jpeg_coefficients_strands(streams):
         err.bad_frame = bad.value
         raise err
     return info, coef, quant
+
+
+JPEG_SPAN_STATS = ("spans", "unresolved", "suspect_strands", "one_lane_frames")
+
+
+def jpeg_span_bytes():
+    """the default span size of the "device-spans" entropy mode, in bytes"""
+    b = C.c_int32(0)
+    rc = lib().ck_jpeg_span_bytes(C.byref(b))
+    if rc != 0:
+        raise _host_error(rc)
+    return b.value
+
+
+def jpeg_coefficients_spans(streams, span_bytes=None):
+    """jpeg_coefficients through the steps the "device-spans" kernels run (speculate, resolve, write, dc, verdict, and the
+    one-lane decoder for suspect frames), on the host (host only) -> (info, coef, quant, stats): the same results, the same
+    accept / refuse decisions; stats as Context.jpeg_span_stats gives them (also the error's `stats` on a refusal)"""
+    ptrs, lens, keep = _jpeg_streams(streams)
+    n = len(keep)
+    info = jpeg_probe(keep[0])
+    geom = JpegInfo(info["h"], info["w"], info["sampling"], info["restart_interval"], info["blocks"])
+    coef = np.empty((n, info["blocks"] * 64), np.int16)
+    quant = np.empty((n, 3, 64), np.uint16)
+    bad = C.c_int32(-1)
+    st = (C.c_longlong * 4)()
+    rc = lib().ck_jpeg_coefficients_spans(ptrs, lens, n, C.byref(geom), jpeg_span_bytes() if span_bytes is None else int(span_bytes),
+                                          coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), C.byref(bad), st)
+    stats = dict(zip(JPEG_SPAN_STATS, (int(v) for v in st)))
+    if rc != 0:
+        err = _host_error(rc)
+        err.bad_frame = bad.value
+        err.stats = stats
+        raise err
+    return info, coef, quant, stats
 
 
 def _check_frames(frames):

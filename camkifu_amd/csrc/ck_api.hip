@@ -16,6 +16,7 @@
 #include "ck_stonegeom.h"
 #include "ck_jpeg.h"
 #include "ck_jpeg_strand.h"
+#include "ck_jpeg_span.h"
 #include "ck_jpeg_enc.h"
 #include "ck_overlay.h"
 
@@ -729,8 +730,11 @@ static int jpeg_pass_frames_device(int n, const size_t* len, size_t cframe)
 // on the host.  Returns with the stream idle.  On a refusal *bad is the lowest frame with a failed strand (or the frame
 // the planner refused, when no frame before it failed) and `why` the cause at its lowest MCU; a failure that is no frame's
 // fault (HIP, memory) leaves *bad at -1 and its message in the context.
+// span_bytes > 0 (CK_JPEG_ENTROPY_DEVICE_SPANS): the first span of every strand goes up behind the quant tables, the five
+// steps of k_jpeg_span.hip decode, the verdict words come down, and only the frames that hold a suspect strand go through
+// k_jpeg_huff (k_jpeg_huff_frame), whose status words decide as above; every other strand's status is 0.
 static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int m, const ck_jpeg_info& geom,
-                          int16_t* d_coef, const uint16_t** d_quant, uint16_t* h_quant, int* bad, std::string& why)
+                          int16_t* d_coef, const uint16_t** d_quant, uint16_t* h_quant, int* bad, std::string& why, int span_bytes = 0)
 {
     CkJpegPlan plan;
     const int prc = ck_jpeg_plan_build(data, len, m, geom, &plan);
@@ -746,7 +750,8 @@ static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t*
         const size_t n_bytes = at + 16;                            // (zeroed slack: a wide load at the last byte stays inside)
         const size_t rows_at = up16(n_bytes), sets_at = up16(rows_at + ns * sizeof(CkStrand));
         const size_t quant_at = up16(sets_at + plan.sets.size() * sizeof(CkHuffSet));
-        const size_t total = quant_at + (size_t)frames * 192 * sizeof(uint16_t);
+        const size_t span0_at = up16(quant_at + (size_t)frames * 192 * sizeof(uint16_t));
+        const size_t total = span_bytes > 0 ? span0_at + (ns + 1) * sizeof(int32_t) : quant_at + (size_t)frames * 192 * sizeof(uint16_t);
         CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
         uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
         for (int f = 0; f < frames; f++) {
@@ -764,17 +769,74 @@ static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t*
         }
         memcpy(hp + sets_at, plan.sets.data(), plan.sets.size() * sizeof(CkHuffSet));
         memcpy(hp + quant_at, plan.quant.data(), (size_t)frames * 192 * sizeof(uint16_t));
+        long long n_spans = 0;
+        if (span_bytes > 0) {
+            memset(hp + quant_at + (size_t)frames * 192 * sizeof(uint16_t), 0, span0_at - (quant_at + (size_t)frames * 192 * sizeof(uint16_t)));
+            int32_t* span0 = (int32_t*)(hp + span0_at);
+            for (size_t s = 0; s < ns; s++) {
+                span0[s] = (int32_t)n_spans;
+                n_spans += ck_span_count(rows[s].end - rows[s].begin, span_bytes);
+                if (n_spans > 0x7fffffff / 8) return ck_fail(ctx, CK_ERR_ARG, "%lld spans in one pass", n_spans);
+            }
+            span0[ns] = (int32_t)n_spans;
+        }
         const void* d_in;
         CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage2, &d_in));
         ctx->jpeg_uploaded += (long long)total;
         const uint8_t* d = (const uint8_t*)d_in;
         CK_TRY(ck_ensure(ctx, ctx->misc, ns * sizeof(uint32_t)));
-        CK_TRY(k_jpeg_huff(ctx, d, (long long)n_bytes, (const CkStrand*)(d + rows_at), (int)ns, (const CkHuffSet*)(d + sets_at),
-                           (int)plan.sets.size(), plan.g, (long long)geom.blocks * 64, frames, d_coef, (uint32_t*)ctx->misc.p));
         CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ns * sizeof(uint32_t)));
         uint32_t* status = (uint32_t*)ctx->host_pinned2.p;
-        CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (span_bytes > 0) {
+            CkSpanJob J{};
+            J.bytes = d; J.n_bytes = (long long)n_bytes;
+            J.rows = (const CkStrand*)(d + rows_at); J.n_strands = (int)ns;
+            J.span0 = (const int32_t*)(d + span0_at);
+            J.sets = (const CkHuffSet*)(d + sets_at); J.n_sets = (int)plan.sets.size();
+            J.g = plan.g; J.cframe = (long long)geom.blocks * 64; J.n_frames = frames; J.span_bytes = span_bytes; J.bpm = ck_span_bpm(plan.g);
+            // the work arrays of the pass, the 8-byte ones first
+            const size_t cand = (size_t)n_spans * (size_t)J.bpm;
+            const size_t a_at = 0, x_at = a_at + cand * 8, e_at = x_at + cand * 8, c_at = e_at + (size_t)n_spans * 8, o_at = c_at + cand * 4;
+            const size_t f_at = o_at + (size_t)n_spans * 4, u_at = f_at + ns * 4, v_at = u_at + ns * 4;
+            CK_TRY(ck_ensure(ctx, ctx->jspan, v_at + ns * 4));
+            uint8_t* wk = (uint8_t*)ctx->jspan.p;
+            J.cand_a = (uint64_t*)(wk + a_at); J.cand_x = (uint64_t*)(wk + x_at); J.entry = (uint64_t*)(wk + e_at);
+            J.cand_c = (uint32_t*)(wk + c_at); J.ord = (int32_t*)(wk + o_at);
+            J.flags = (uint32_t*)(wk + f_at); J.unresolved = (uint32_t*)(wk + u_at); J.verdict = (uint32_t*)(wk + v_at);
+            J.coef = d_coef;
+            CK_TRY(k_jpeg_span(ctx, J, n_spans));
+            CK_HIP(ctx, hipMemcpyAsync(status, J.verdict, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            // the frames that hold a suspect strand (their rows lie together: the plan is frame-major)
+            std::vector<int> first_row((size_t)frames, -1), n_rows((size_t)frames, 0);
+            std::vector<uint8_t> again((size_t)frames, 0);
+            ctx->jpeg_span_stats[0] += n_spans;
+            bool any = false;
+            for (size_t s = 0; s < ns; s++) {
+                const size_t f = (size_t)plan.strands[s].frame;
+                if (first_row[f] < 0) first_row[f] = (int)s;
+                n_rows[f]++;
+                ctx->jpeg_span_stats[1] += status[s] >> 1;
+                if (status[s] & 1) { ctx->jpeg_span_stats[2]++; again[f] = 1; any = true; }
+            }
+            memset(status, 0, ns * sizeof(uint32_t));
+            if (any) {
+                CK_HIP(ctx, hipMemsetAsync(ctx->misc.p, 0, ns * sizeof(uint32_t), ctx->stream));
+                for (int f = 0; f < frames; f++)
+                    if (again[f]) {
+                        ctx->jpeg_span_stats[3]++;
+                        CK_TRY(k_jpeg_huff_frame(ctx, d, (long long)n_bytes, J.rows, first_row[f], n_rows[f], J.sets, J.n_sets, plan.g, J.cframe,
+                                                 frames, f, d_coef, (uint32_t*)ctx->misc.p));
+                    }
+                CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            }
+        } else {
+            CK_TRY(k_jpeg_huff(ctx, d, (long long)n_bytes, (const CkStrand*)(d + rows_at), (int)ns, (const CkHuffSet*)(d + sets_at),
+                               (int)plan.sets.size(), plan.g, (long long)geom.blocks * 64, frames, d_coef, (uint32_t*)ctx->misc.p));
+            CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
         for (size_t s = 0; s < ns; s++)
             if (status[s]) {
                 char msg[CK_JPEG_MSG];
@@ -793,11 +855,49 @@ static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t*
 int ck_jpeg_set_entropy(ck_ctx* ctx, int mode)
 {
     CK_API_BEGIN(ctx)
-    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
+    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE && mode != CK_JPEG_ENTROPY_DEVICE_SPANS)
+        return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
     ctx->jpeg_entropy = mode;
     return CK_OK;
     CK_API_END(ctx)
 }
+
+int ck_jpeg_set_span_bytes(ck_ctx* ctx, int bytes)
+{
+    CK_API_BEGIN(ctx)
+    if (bytes < CK_SPAN_MIN || bytes > CK_SPAN_MAX) return ck_fail(ctx, CK_ERR_ARG, "span size %d outside %d .. %d bytes", bytes, CK_SPAN_MIN, CK_SPAN_MAX);
+    ctx->jpeg_span_bytes = bytes;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_span_bytes(int32_t* bytes)
+{
+    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
+    *bytes = CK_SPAN_DEFAULT;
+    return CK_OK;
+}
+
+int ck_jpeg_span_stats(ck_ctx* ctx, long long* stats)
+{
+    CK_API_BEGIN(ctx)
+    if (!stats) return ck_fail(ctx, CK_ERR_ARG, "stats is NULL");
+    for (int i = 0; i < CK_SPAN_STATS; i++) stats[i] = ctx->jpeg_span_stats[i];
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// in that mode the frame a call refuses is named in the host decoder's words (ck_jpeg_span_host_wording)
+static void jpeg_span_wording(const ck_ctx* ctx, const uint8_t* data, size_t len, const ck_jpeg_info& geom, std::string& why)
+{
+    if (ctx->jpeg_entropy != CK_JPEG_ENTROPY_DEVICE_SPANS) return;
+    char msg[CK_JPEG_MSG] = {0};
+    snprintf(msg, sizeof msg, "%s", why.c_str());
+    ck_jpeg_span_host_wording(data, len, geom, msg);
+    why = msg;
+}
+// the context's span size when its mode decodes inside strands, else 0 (jpeg_huff_pass)
+static int jpeg_ctx_spans(const ck_ctx* ctx) { return ctx->jpeg_entropy == CK_JPEG_ENTROPY_DEVICE_SPANS ? ctx->jpeg_span_bytes : 0; }
 
 int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
                                 int16_t* coef, uint16_t* quant, int out_space, int32_t* bad_frame)
@@ -806,6 +906,7 @@ int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const s
     if (bad_frame) *bad_frame = -1;
     ctx->jpeg_bad_frame = -1;
     ctx->jpeg_uploaded = 0;
+    for (long long& v : ctx->jpeg_span_stats) v = 0;
     if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
     CK_TRY(check_jpeg_geom(ctx, geom->h, geom->w, geom->sampling, geom->blocks));
     if (out_space != CK_HOST && (((uintptr_t)coef | (uintptr_t)quant) & 15))
@@ -820,9 +921,10 @@ int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const s
         int bad = -1;
         std::string why;
         const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, *geom, d_coef, &d_quant, out_space == CK_HOST ? quant + (size_t)f0 * 192 : nullptr,
-                                      &bad, why);
+                                      &bad, why, jpeg_ctx_spans(ctx));
         if (rc != CK_OK && bad < 0) return rc;                    // no frame's fault (HIP, memory): the message is stored
         if (rc != CK_OK) {
+            jpeg_span_wording(ctx, data[f0 + bad], len[f0 + bad], *geom, why);
             if (bad_frame) *bad_frame = f0 + bad;
             ctx->jpeg_bad_frame = f0 + bad;
             (void)hipStreamSynchronize(ctx->stream);
@@ -884,11 +986,36 @@ int ck_jpeg_coefficients_strands(const uint8_t* const* data, const size_t* len, 
     }
 }
 
+int ck_jpeg_coefficients_spans(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom, int span_bytes,
+                               int16_t* coef, uint16_t* quant, int32_t* bad_frame, long long* stats)
+{
+    if (bad_frame) *bad_frame = -1;
+    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    if (span_bytes < CK_SPAN_MIN || span_bytes > CK_SPAN_MAX)
+        return ck_fail(nullptr, CK_ERR_ARG, "span size %d outside %d .. %d bytes", span_bytes, CK_SPAN_MIN, CK_SPAN_MAX);
+    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
+    try {
+        int bad = -1;
+        char msg[CK_JPEG_MSG] = {0};
+        long long st[CK_SPAN_STATS];
+        const int rc = ck_jpeg_spans_host(data, len, n, *geom, span_bytes, coef, quant, &bad, msg, st);
+        if (stats) memcpy(stats, st, sizeof st);
+        if (rc != CK_OK) {
+            if (bad_frame) *bad_frame = bad;
+            return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
+        }
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
 int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space)
 {
     CK_API_BEGIN(ctx)
     ctx->jpeg_bad_frame = -1;
     ctx->jpeg_uploaded = 0;
+    for (long long& v : ctx->jpeg_span_stats) v = 0;
     if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
     auto first = std::make_unique<CkJpegFrame>();
     char msg[CK_JPEG_MSG];
@@ -901,7 +1028,7 @@ int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, i
     const int pass = jpeg_pass_frames(n, cframe + qframe);
     OutStage<uint8_t> o;
     CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
-    if (ctx->jpeg_entropy == CK_JPEG_ENTROPY_DEVICE) {
+    if (ctx->jpeg_entropy != CK_JPEG_ENTROPY_HOST) {
         // per pass: the compressed bytes up, the Huffman kernel, the reconstruct kernel: the coefficients stay in HBM
         const int pass = jpeg_pass_frames_device(n, len, cframe);
         CK_TRY(ck_ensure(ctx, ctx->in_stage, (size_t)pass * cframe));
@@ -910,9 +1037,10 @@ int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, i
             const uint16_t* d_quant = nullptr;
             int bad = -1;
             std::string why;
-            const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, geom, (int16_t*)ctx->in_stage.p, &d_quant, nullptr, &bad, why);
+            const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, geom, (int16_t*)ctx->in_stage.p, &d_quant, nullptr, &bad, why, jpeg_ctx_spans(ctx));
             if (rc != CK_OK && bad < 0) return rc;                // no frame's fault (HIP, memory): the message is stored
             if (rc != CK_OK) {
+                jpeg_span_wording(ctx, data[f0 + bad], len[f0 + bad], geom, why);
                 ctx->jpeg_bad_frame = f0 + bad;
                 (void)hipStreamSynchronize(ctx->stream);
                 return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());

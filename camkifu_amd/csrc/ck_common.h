@@ -135,6 +135,7 @@ struct ck_ctx {
     DevBuf jenc_work;    // the encoder's Huffman stage on the device: sizes and offsets of a pass (CkEncWork),
     DevBuf jenc_bits;    // its unstuffed bits and the FF counts of their byte tiles,
     DevBuf jenc_pack;    // and its streams, one behind the other
+    DevBuf jspan;        // CK_JPEG_ENTROPY_DEVICE_SPANS: candidates, entries and flags of a pass (k_jpeg_span.hip)
 
     CnnWeights cnn;
     int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
@@ -145,6 +146,8 @@ struct ck_ctx {
     int jpeg_bad_frame = -1;         // ck_jpeg_decode: the frame its last CK_ERR_DATA is about (-1: none)
     long long jpeg_uploaded = 0;     // bytes the last ck_jpeg_decode / ck_jpeg_coefficients_device copied to the device
     int jpeg_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_decode runs the Huffman stage (ck_jpeg_set_entropy)
+    int jpeg_span_bytes = 512;       // S of CK_JPEG_ENTROPY_DEVICE_SPANS (CK_SPAN_DEFAULT; ck_jpeg_set_span_bytes)
+    long long jpeg_span_stats[4] = {0, 0, 0, 0};   // of the last decode in that mode (ck_jpeg_span_stats)
     int jpeg_enc_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_encode runs the Huffman stage (ck_jpeg_set_encode_entropy)
     long long jpeg_downloaded = 0;   // bytes the last ck_jpeg_encode / ck_jpeg_entropy_encode_device copied from the device
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
@@ -296,6 +299,14 @@ struct CkHuffSet;
 struct CkStrandGeom;
 int k_jpeg_huff(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const CkStrand* d_rows, int n_strands, const CkHuffSet* d_sets,
                 int n_sets, const CkStrandGeom& g, long long cframe, int n_frames, int16_t* d_coef, uint32_t* d_status);
+// the same kernel over the n_rows rows from first_row on, all of frame `frame`, whose coefficients alone are zeroed first
+int k_jpeg_huff_frame(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const CkStrand* d_rows, int first_row, int n_rows,
+                      const CkHuffSet* d_sets, int n_sets, const CkStrandGeom& g, long long cframe, int n_frames, int frame, int16_t* d_coef,
+                      uint32_t* d_status);
+// parallel decoding inside a strand (k_jpeg_span.hip): the five steps of ck_jpeg_span.h over a pass, d_coef zeroed here first;
+// J's pointers are HBM; n_spans = span0[n_strands].  Leaves J.verdict (n_strands words) for the caller to fetch.
+struct CkSpanJob;
+int k_jpeg_span(ck_ctx* ctx, const CkSpanJob& J, long long n_spans);
 // the Huffman stage of the encoder on the device (k_jpeg_enc_huff.hip), m frames of one geometry.  CkEncWork: where the sizes
 // and offsets of a pass lie in HBM -- per block, per block tile, per segment (seg_u0: nseg + 1 per frame) and per frame
 // (frame_u0, out_off: m + 1); head[0] the lowest (frame << 32 | block) that cannot be coded or all ones, head[1] the bytes of

@@ -71,3 +71,20 @@ int k_jpeg_huff(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const Ck
     CK_HIP(ctx, hipGetLastError());
     return CK_OK;
 }
+
+// One frame again, for the span decoder (k_jpeg_span.hip) whose verdict on one of its strands was "suspect": rows
+// first_row .. first_row + n_rows - 1 are the frame's, its coefficients alone are zeroed, and the status words land at the
+// rows' own places in d_status.
+int k_jpeg_huff_frame(ck_ctx* ctx, const uint8_t* d_bytes, long long n_bytes, const CkStrand* d_rows, int first_row, int n_rows,
+                      const CkHuffSet* d_sets, int n_sets, const CkStrandGeom& g, long long cframe, int n_frames, int frame, int16_t* d_coef,
+                      uint32_t* d_status)
+{
+    if (first_row < 0 || n_rows <= 0 || n_sets <= 0 || frame < 0 || frame >= n_frames) return ck_fail(ctx, CK_ERR_ARG, "k_jpeg_huff_frame: nothing to decode");
+    CK_HIP(ctx, hipMemsetAsync(d_coef + (size_t)frame * (size_t)cframe, 0, (size_t)cframe * sizeof(int16_t), ctx->stream));
+    TimeScope ts(ctx, "jpeg_huff");
+    const dim3 grid((unsigned)((n_rows + HUFF_LANES - 1) / HUFF_LANES));
+    hipLaunchKernelGGL(jpeg_huff_kernel, grid, dim3(HUFF_LANES), 0, ctx->stream, d_bytes, n_bytes, d_rows + first_row, n_rows, d_sets, n_sets,
+                       g, cframe, n_frames, d_coef, d_status + first_row);
+    CK_HIP(ctx, hipGetLastError());
+    return CK_OK;
+}

@@ -1414,8 +1414,9 @@ class FastFilePipeline:
         through process_batch.
         `downsample` = N > 0: the decoded frames go through N levels of pyrDown on the device first (no fusion with the
         decoder); the pipeline must have been built for capi.pyr_shape(h, w, N).
-        `entropy` = "host" | "device": set the context's JPEG entropy mode first (Context.jpeg_set_entropy; "device" runs the
-        Huffman stage on the GPU, one lane per restart interval, and uploads the compressed bytes); None leaves it as it is.
+        `entropy` = "host" | "device" | "device-spans": set the context's JPEG entropy mode first (Context.jpeg_set_entropy;
+        "device" runs the Huffman stage on the GPU, one lane per restart interval, and uploads the compressed bytes;
+        "device-spans" decodes in parallel inside a restart interval as well); None leaves it as it is.
         A frame whose entropy-coded data is damaged, or that has no good frame before it, raises CkError naming the frame's
         number in the file -- on EVERY rank (the ranks exchange one word per batch before any of them enters the batch's
         collectives), with the cause on the rank that owns the frame.  Returns the concatenated request lists (rank 0)."""

@@ -185,6 +185,25 @@ int ck_jpeg_plan(const uint8_t* const* data, const size_t* len, int n, const ck_
 int ck_jpeg_coefficients_strands(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
                                  int16_t* coef, uint16_t* quant, int32_t* bad_frame);
 
+/* Parallel decoding INSIDE a strand, opt-in as well: CK_JPEG_ENTROPY_DEVICE_SPANS for ck_jpeg_set_entropy.  Every strand is
+ * cut into spans of S raw bytes.  A lane per span and per block slot of the MCU starts one span early on a guess and records
+ * where it stands when it crosses into its span (Huffman streams fall into step after a short run); a walk per strand
+ * picks the guesses that meet the true chain and decodes the few spans none met; a lane per span then writes its
+ * coefficients, and a sum per strand turns DC differences into values.  A strand whose chain is not clean beyond doubt
+ * has its frame decoded again by the one-lane kernel of CK_JPEG_ENTROPY_DEVICE, whose status decides: the mode accepts and
+ * refuses the same streams as the host decoder, names the same frame and gives the same coefficients. */
+enum { CK_JPEG_ENTROPY_DEVICE_SPANS = 2 };
+/* S for the context, 8 .. 4096 bytes (anything else is CK_ERR_ARG); ck_jpeg_span_bytes gives the default */
+int ck_jpeg_set_span_bytes(ck_ctx* ctx, int bytes);
+int ck_jpeg_span_bytes(int32_t* bytes);
+/* what the context's last ck_jpeg_decode / ck_jpeg_coefficients_device did in that mode, all passes: stats[0] spans,
+ * [1] unresolved spans (decoded by the walk itself), [2] suspect strands, [3] frames handed to the one-lane kernel */
+int ck_jpeg_span_stats(ck_ctx* ctx, long long* stats);
+/* host only: the plan, then the steps the GPU kernels run, in their order ON THE HOST, the one-lane decoder for suspect
+ * frames included -> what ck_jpeg_coefficients gives.  span_bytes: 8 .. 4096; stats (nullable): 4 values as above */
+int ck_jpeg_coefficients_spans(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom, int span_bytes,
+                               int16_t* coef, uint16_t* quant, int32_t* bad_frame, long long* stats);
+
 /* ---- compressed output: baseline JPEG encode (.jpg stills, Motion-JPEG frames of an .avi)   core/vmanager.py:309-325 (cv2.imwrite)
  * The mirror of the calls above, and as exact: the streams are, byte for byte, what libjpeg's default compressor writes
  * (fixed-point RGB -> YCbCr, box downsampling without smoothing, slow-integer forward DCT, the quant tables of

@@ -34,7 +34,7 @@ def main():
     ap.add_argument("--failfast", action="store_true")
     ap.add_argument("--downsample", type=int, default=0, metavar="N",
                     help="levels of cv2.pyrDown every frame goes through before the finders see it (cvconf.downsample)")
-    ap.add_argument("--jpeg-entropy", choices=("host", "device"), default=None,
+    ap.add_argument("--jpeg-entropy", choices=("host", "device", "device-spans"), default=None,
                     help="where a Motion-JPEG film's Huffman stage runs (Context.jpeg_set_entropy of the process-wide context)")
     args = ap.parse_args()
     cvconf.downsample = args.downsample

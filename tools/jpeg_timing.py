@@ -15,6 +15,11 @@ write) as baseline JPEG, 4:2:0, quality 90, and held in host memory.
    kernel and the reconstruct kernel (HIP events); jpeg_decode frames/s in device mode against host mode (16 threads) in
    alternating rounds, for the whole film per call and for smaller calls (the strands per call at which the device mode
    starts to win); process_mjpeg in both modes against process_y4m, with the three game records.
+5. "device-spans" entropy mode (parallel decoding inside a restart interval) on the same two films -> "device_spans": the
+   HIP-event time of each of its five steps per frame, the shares of Context.jpeg_span_stats, jpeg_decode frames/s at 1, 8,
+   32 and 128 frames a call against host mode and against "device" mode in alternating rounds, process_mjpeg against host
+   mode and process_y4m with the game records; and on the film without restart intervals a sweep of the span size.
+   `--sections device_spans` runs this part alone and keeps the other parts of an existing --out file.
 
     python tools/jpeg_timing.py [--size 1920x1080] [--film 128] [--n 32] [--reps 7] [--inner 8] [--e2e-reps 5]
 
@@ -58,6 +63,9 @@ def main(argv=None):
     ap.add_argument("--inner", type=int, default=8, help="kernel calls per round")
     ap.add_argument("--batch", type=int, default=32, help="frames per pipeline batch")
     ap.add_argument("--e2e-reps", type=int, default=5)
+    ap.add_argument("--sections", default="all", choices=("all", "device_spans"),
+                    help="device_spans: only part 5, merged into the existing --out file")
+    ap.add_argument("--spans", default="64,128,256,512,1024", help="span sizes of the sweep, bytes")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_timing.json"))
     args = ap.parse_args(argv)
     if args.reps < 5 or args.e2e_reps < 5:
@@ -86,7 +94,14 @@ def main(argv=None):
     del film
     torch.cuda.empty_cache()
     out["plan"]["jpeg_bytes_per_frame"] = int(np.mean([j.size for j in jpegs]))
-    try:
+    only_spans = args.sections == "device_spans"
+    if only_spans and os.path.exists(args.out):
+        with open(args.out) as f:
+            kept = json.load(f)
+        kept["device_spans_run"] = dict(tool=out["tool"], device=out["device"], plan=out["plan"])
+        out = kept
+
+    def parts_1_to_4():
         # 1. host
         batch = jpegs[:n]
         capi.jpeg_coefficients(batch)
@@ -243,6 +258,123 @@ def main(argv=None):
             dev_out[film_name] = leg
             print("device entropy, %s: done" % film_name, flush=True)
         out["device_entropy"] = dev_out
+
+    def part_5():
+        # 5. parallel decoding inside a restart interval
+        if only_spans:
+            ctx.cnn_set_weights(NNManager.init_net())                  # (part 3 does it otherwise)
+        bgr = torch.empty((F, h, w, 3), dtype=torch.uint8, device=dev)
+        STEPS = ("jpeg_span_speculate", "jpeg_span_resolve", "jpeg_span_write", "jpeg_span_dc", "jpeg_span_verdict", "jpeg_huff", "jpeg")
+        modes = ("host", "device", "device-spans")
+
+        def decode_fps(js, mode, count):
+            ctx.jpeg_set_entropy(mode)
+            t0 = time.perf_counter()
+            for b0 in range(0, F, count):
+                ctx.jpeg_decode(js[b0:b0 + count], out=bgr[:len(js[b0:b0 + count])])
+            torch.cuda.synchronize()
+            return F / (time.perf_counter() - t0)
+
+        def step_times(js, span):
+            ctx.jpeg_set_entropy("device-spans")
+            ctx.jpeg_set_span_bytes(span)
+            ctx.jpeg_decode(js, out=bgr)
+            st = ctx.jpeg_span_stats()
+            ctx.timing_enable(True)
+            ms = {k: [] for k in STEPS}
+            for _ in range(args.reps):
+                ctx.timing_reset()
+                ctx.jpeg_decode(js, out=bgr)
+                for k in STEPS:
+                    ms[k].append(ctx.timing_get(k)[0] / F)
+            ctx.timing_enable(False)
+            never = dict(median_ms=0.0, min_ms=0.0, max_ms=0.0, spread=0.0)        # (jpeg_huff: no suspect strand, no launch)
+            return st, {k: spread_of(v) if min(v) > 0 else dict(never, rounds=len(v)) for k, v in ms.items()}
+
+        span_out = dict(default_span_bytes=capi.jpeg_span_bytes())
+        for film_name, js in (("restart_row", jpegs_row), ("no_restart", jpegs)):
+            ctx.jpeg_set_entropy("host")
+            want = ctx.jpeg_decode(js[:2])
+            ctx.jpeg_set_span_bytes(capi.jpeg_span_bytes())
+            st, steps = step_times(js, capi.jpeg_span_bytes())
+            leg = dict(jpeg_bytes_per_frame=int(np.mean([j.size for j in js])),
+                       equal_to_host_mode=bool(np.array_equal(ctx.jpeg_decode(js[:2]), want)),
+                       bytes_uploaded_per_frame=ctx.jpeg_uploaded_bytes() // 2,
+                       kernel_ms_per_frame=steps,
+                       entropy_kernels_ms_per_frame=round(sum(steps[k]["median_ms"] for k in STEPS[:6]), 4),
+                       span_stats=dict(st, spans_per_frame=round(st["spans"] / F, 1),
+                                       unresolved_share=round(st["unresolved"] / max(1, st["spans"]), 5)))
+            by_batch = []
+            for count in [c for c in (1, 8, 32, 128) if c <= F]:
+                fps = {m: [] for m in modes}
+                for m in modes:
+                    decode_fps(js, m, count)
+                for _ in range(args.e2e_reps):
+                    for m in modes:
+                        fps[m].append(decode_fps(js, m, count))
+                med = {m: float(np.median(v)) for m, v in fps.items()}
+                by_batch.append(dict(frames_per_call=count,
+                                     frames_per_s={m: dict(median=round(med[m], 1), min=round(min(fps[m]), 1), max=round(max(fps[m]), 1))
+                                                   for m in modes},
+                                     spans_over_host=round(med["device-spans"] / med["host"], 3),
+                                     spans_over_device=round(med["device-spans"] / med["device"], 3),
+                                     winner=max(modes, key=lambda m: med[m])))
+                print("device-spans entropy, %s, %d frames a call: done" % (film_name, count), flush=True)
+            leg["jpeg_decode_by_frames_per_call"] = by_batch
+            clips = {"host": MjpegClip(js, h, w), "device-spans": MjpegClip(js, h, w), "y4m": I420Clip(i420.numpy(), h, w)}
+
+            def run3(kind):
+                p = pipeline.FastFilePipeline(h, w, ControllerHeadless(), ctx=ctx)
+                try:
+                    t0 = time.perf_counter()
+                    if kind == "y4m":
+                        reqs = p.process_y4m(clips[kind], batch=args.batch)
+                    else:
+                        reqs = p.process_mjpeg(clips[kind], batch=args.batch, entropy=kind)
+                    torch.cuda.synchronize()
+                    return time.perf_counter() - t0, reqs
+                finally:
+                    p.close()
+            first3 = {k: run3(k) for k in clips}
+            secs3 = {k: [] for k in clips}
+            for _ in range(args.e2e_reps):
+                for k in clips:
+                    secs3[k].append(run3(k)[0])
+            e2e = dict(pipeline_batch=args.batch)
+            for k in clips:
+                fps = sorted(F / t for t in secs3[k])
+                e2e[k] = dict(frames_per_s=dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1),
+                                                rounds=len(fps)), game_record=game_quality(first3[k][1], truth, moves, F))
+            e2e["spans_over_host"] = round(e2e["device-spans"]["frames_per_s"]["median"] / e2e["host"]["frames_per_s"]["median"], 3)
+            e2e["spans_over_y4m"] = round(e2e["device-spans"]["frames_per_s"]["median"] / e2e["y4m"]["frames_per_s"]["median"], 3)
+            e2e["same_game_record_as_host"] = bool(e2e["device-spans"]["game_record"] == e2e["host"]["game_record"])
+            leg["process_mjpeg"] = e2e
+            if film_name == "no_restart":
+                sweep = []
+                for span in [int(v) for v in args.spans.split(",")]:
+                    st, steps = step_times(js, span)
+                    fps = dict()
+                    for count in [c for c in (32, 128) if c <= F]:
+                        decode_fps(js, "device-spans", count)
+                        fps[count] = [decode_fps(js, "device-spans", count) for _ in range(args.e2e_reps)]
+                    sweep.append(dict(span_bytes=span, spans_per_frame=round(st["spans"] / F, 1),
+                                      unresolved_share=round(st["unresolved"] / max(1, st["spans"]), 5),
+                                      kernel_ms_per_frame={k: steps[k]["median_ms"] for k in STEPS[:5]},
+                                      entropy_kernels_ms_per_frame=round(sum(steps[k]["median_ms"] for k in STEPS[:5]), 4),
+                                      jpeg_decode_frames_per_s={str(c): dict(median=round(float(np.median(v)), 1), min=round(min(v), 1),
+                                                                             max=round(max(v), 1)) for c, v in fps.items()}))
+                leg["span_size_sweep"] = sweep
+                leg["fastest_span_bytes_by_kernel_time"] = min(sweep, key=lambda r: r["entropy_kernels_ms_per_frame"])["span_bytes"]
+                ctx.jpeg_set_span_bytes(capi.jpeg_span_bytes())
+            ctx.jpeg_set_entropy("host")
+            span_out[film_name] = leg
+            print("device-spans entropy, %s: done" % film_name, flush=True)
+        out["device_spans"] = span_out
+
+    try:
+        if not only_spans:
+            parts_1_to_4()
+        part_5()
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

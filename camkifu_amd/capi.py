@@ -19,6 +19,7 @@ CK_OK, CK_ERR_ARG, CK_ERR_HIP, CK_ERR_CAPACITY, CK_ERR_STATE, CK_ERR_DATA = 0, 1
 CK_HOST, CK_DEVICE = 0, 1
 CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
 CK_JPEG_ENTROPY_HOST, CK_JPEG_ENTROPY_DEVICE = 0, 1
+CK_JPEG_TABLES_STANDARD, CK_JPEG_TABLES_OPTIMISED = 0, 1
 CK_JPEG_ENTROPY_DEVICE_SPANS = 2
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
@@ -523,12 +524,20 @@ class Context:
         self._chk(lib().ck_jpeg_forward(self._h, p, n, h, w, sp, quant.ctypes.data_as(C.c_void_p), sampling, op, osp))
         return out
 
-    def jpeg_encode(self, frames, quality=90, sampling=CK_JPEG_420, restart_interval=0):
+    def jpeg_encode(self, frames, quality=90, sampling=CK_JPEG_420, restart_interval=0, optimize=False):
         """BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM -> a list of n `bytes`: baseline
         JPEG streams, byte for byte what PIL.Image.save(.., "JPEG", quality=quality, subsampling=..) writes.  The forward
         kernel runs on the GPU; the Huffman coder on the host (the frames of a batch in parallel), or, after
         jpeg_set_encode_entropy("device"), on the GPU as well: then the coefficients stay in HBM and only the streams come
-        down.  The bytes are the same in both modes.  restart_interval in MCUs, 0: none."""
+        down.  The bytes are the same in both modes.  restart_interval in MCUs, 0: none.  optimize=True: Huffman tables
+        fitted to each frame for this call, the bytes of PIL's optimize=True -- the same pixels in a smaller stream;
+        False: what jpeg_set_encode_tables has set (the standard tables in a new context)."""
+        if optimize and self._jpeg_tables != "optimised":
+            self.jpeg_set_encode_tables("optimised")
+            try:
+                return self.jpeg_encode(frames, quality, sampling, restart_interval)
+            finally:
+                self.jpeg_set_encode_tables("standard")
         _check_frames(frames)
         n, h, w = self._shape(frames, 3)
         sampling = int(sampling)
@@ -549,16 +558,35 @@ class Context:
             raise CkError("jpeg entropy mode: 'host' or 'device' is needed, got %r" % (mode,))
         self._chk(lib().ck_jpeg_set_encode_entropy(self._h, modes[mode]))
 
+    _jpeg_tables = "standard"
+
+    def jpeg_set_encode_tables(self, mode):
+        """the Huffman tables jpeg_encode writes from now on, in either entropy mode: "standard" (the default: Annex K.3)
+        or "optimised" (fitted to each frame, libjpeg's optimize_coding)"""
+        modes = {"standard": CK_JPEG_TABLES_STANDARD, "optimised": CK_JPEG_TABLES_OPTIMISED}
+        if mode not in modes:
+            raise CkError("jpeg encode tables: 'standard' or 'optimised' is needed, got %r" % (mode,))
+        self._chk(lib().ck_jpeg_set_encode_tables(self._h, modes[mode]))
+        self._jpeg_tables = mode
+
+    def jpeg_encode_histograms(self, n):
+        """a test hook: the symbol counters the GPU kernels left in HBM in the last pass of this context's last optimised
+        encode in the device mode -> (n, 4, 256) uint32, as jpeg_histogram gives them; n: the frames of that pass"""
+        counts = np.zeros((int(n), 4, 256), np.uint32)
+        self._chk(lib().ck_jpeg_encode_histograms(self._h, int(n), counts.ctypes.data_as(C.c_void_p)))
+        return counts
+
     def jpeg_downloaded_bytes(self):
         """the bytes the last jpeg_encode or jpeg_entropy_encode_device of this context copied from device to host"""
         b = C.c_longlong(0)
         self._chk(lib().ck_jpeg_downloaded_bytes(self._h, C.byref(b)))
         return b.value
 
-    def jpeg_entropy_encode_device(self, coef, quant, h, w, sampling, restart_interval=0):
+    def jpeg_entropy_encode_device(self, coef, quant, h, w, sampling, restart_interval=0, optimize=False):
         """jpeg_entropy_encode with the Huffman stage on the GPU: coefficients (n, blocks * 64) int16, a numpy array or a
         torch tensor in HBM, + one set of quant tables (3, 64) -> a list of n `bytes`, those of the host coder.  CkError
-        (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code, in the host coder's words."""
+        (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code, in the host coder's words.  optimize=True:
+        tables fitted to each frame, counted and built on the GPU (ck_jpeg_entropy_encode_opt_device)."""
         h, w, sampling = int(h), int(w), int(sampling)
         n = int(coef.shape[0]) if len(coef.shape) == 2 else -1
         _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
@@ -567,8 +595,9 @@ class Context:
         p, sp, keep = self._in(coef, np.int16)
         out = np.empty(max(1, n) * stride, np.uint8)
         lens = (C.c_size_t * max(1, n))()
-        self._chk(lib().ck_jpeg_entropy_encode_device(self._h, p, sp, quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
-                                                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens))
+        fn = lib().ck_jpeg_entropy_encode_opt_device if optimize else lib().ck_jpeg_entropy_encode_device
+        self._chk(fn(self._h, p, sp, quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+                     int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens))
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
     def overlay_draw(self, images, lists):
@@ -1244,10 +1273,11 @@ def jpeg_encode_bound(h, w, sampling):
     return b.value
 
 
-def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0):
+def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0, optimize=False):
     """the Huffman stage of the encoder alone (host only): coefficients (n, blocks * 64) int16, or (blocks * 64,) of one
     frame, in the layout of jpeg_coefficients + one set of quant tables (3, 64) -> a list of n `bytes` (one `bytes` for one
-    frame).  CkError (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code."""
+    frame).  CkError (CK_ERR_ARG) for a coefficient the baseline Huffman tables cannot code.  optimize=True: tables fitted
+    to each frame (ck_jpeg_entropy_encode_opt), the bytes of PIL's optimize=True."""
     h, w, sampling = int(h), int(w), int(sampling)
     coef = np.ascontiguousarray(coef, np.int16)
     single = coef.ndim == 1
@@ -1258,17 +1288,18 @@ def jpeg_entropy_encode(coef, quant, h, w, sampling, restart_interval=0):
     stride = jpeg_encode_bound(h, w, sampling)
     out = np.empty(max(1, n) * stride, np.uint8)
     lens = (C.c_size_t * max(1, n))()
-    rc = lib().ck_jpeg_entropy_encode(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
-                                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
+    fn = lib().ck_jpeg_entropy_encode_opt if optimize else lib().ck_jpeg_entropy_encode
+    rc = fn(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+            int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
     if rc != 0:
         raise _host_error(rc)
     streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
     return streams[0] if single else streams
 
 
-def jpeg_entropy_encode_staged(coef, quant, h, w, sampling, restart_interval=0):
-    """jpeg_entropy_encode through the steps the GPU kernels run (size, scan, put, stuff), on the host (host only): the same
-    streams, the same refusals"""
+def jpeg_entropy_encode_staged(coef, quant, h, w, sampling, restart_interval=0, optimize=False):
+    """jpeg_entropy_encode through the steps the GPU kernels run (size, scan, put, stuff; with optimize=True histo and tables
+    in front of them), on the host (host only): the same streams, the same refusals"""
     h, w, sampling = int(h), int(w), int(sampling)
     coef = np.ascontiguousarray(coef, np.int16)
     single = coef.ndim == 1
@@ -1279,12 +1310,43 @@ def jpeg_entropy_encode_staged(coef, quant, h, w, sampling, restart_interval=0):
     stride = jpeg_encode_bound(h, w, sampling)
     out = np.empty(max(1, n) * stride, np.uint8)
     lens = (C.c_size_t * max(1, n))()
-    rc = lib().ck_jpeg_entropy_encode_staged(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
-                                             int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
+    fn = lib().ck_jpeg_entropy_encode_opt_staged if optimize else lib().ck_jpeg_entropy_encode_staged
+    rc = fn(coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
+            int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens)
     if rc != 0:
         raise _host_error(rc)
     streams = [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
     return streams[0] if single else streams
+
+
+def jpeg_histogram(coef, h, w, sampling, restart_interval=0):
+    """the symbols the Huffman coder emits for each frame, counted (host only): coefficients (n, blocks * 64) int16, or
+    (blocks * 64,) of one frame -> (n, 4, 256) uint32, or (4, 256): DC luma, AC luma, DC chroma, AC chroma, the order of the
+    DHT segments.  CkError for a coefficient the coder refuses."""
+    h, w, sampling = int(h), int(w), int(sampling)
+    coef = np.ascontiguousarray(coef, np.int16)
+    single = coef.ndim == 1
+    coef = coef.reshape(1, -1) if single else coef
+    n = coef.shape[0]
+    _check_array(coef, (n, jpeg_blocks(h, w, sampling) * 64), np.int16, "coef")
+    counts = np.zeros((max(1, n), 4, 256), np.uint32)
+    rc = lib().ck_jpeg_histogram(coef.ctypes.data_as(C.c_void_p), n, h, w, sampling, int(restart_interval), counts.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise _host_error(rc)
+    return counts[0] if single else counts[:n]
+
+
+def jpeg_optimal_table(counts):
+    """libjpeg's jpeg_gen_optimal_table (host only): 256 symbol counts -> (bits, vals): bits (16,) uint8, the number of codes
+    of 1 .. 16 bits, and the symbols in the order of their codes -- the body of a DHT segment"""
+    counts = np.ascontiguousarray(counts, np.uint32)
+    _check_array(counts, (256,), np.uint32, "counts")
+    bits, vals, count = np.zeros(16, np.uint8), np.zeros(256, np.uint8), C.c_int32(0)
+    rc = lib().ck_jpeg_optimal_table(counts.ctypes.data_as(C.c_void_p), bits.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p),
+                                     C.byref(count))
+    if rc != 0:
+        raise _host_error(rc)
+    return bits, vals[:count.value].copy()
 
 
 def jpeg_enc_tiles():

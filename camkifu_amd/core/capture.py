@@ -282,16 +282,19 @@ def _default_encode():
     return capi.get_context().jpeg_encode
 
 
-def write_jpeg(path, bgr, quality=90, sampling=None, encode=None, restart_interval=0):
+def write_jpeg(path, bgr, quality=90, sampling=None, encode=None, restart_interval=0, optimize=False):
     """one BGR image (h, w, 3), a numpy array or a tensor in HBM, as a baseline JPEG still: the bytes libjpeg's default
     compressor writes (cv2.imwrite, PIL.Image.save).  sampling: capi.CK_JPEG_* (4:2:0 when None); encode: a callable
     (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context; restart_interval: MCUs
-    between restart markers (0: none; handed to `encode` as restart_interval= only when set).  -> bytes written"""
+    between restart markers (0: none; handed to `encode` as restart_interval= only when set); optimize: Huffman tables
+    fitted to the image, a smaller file of the same pixels (handed on as optimize=True only when set).  -> bytes written"""
     from .. import capi
     if len(bgr.shape) != 3 or bgr.shape[2] != 3:
         raise ValueError("write_jpeg takes one (h, w, 3) image, got %r" % (tuple(bgr.shape),))
     encode = encode or _default_encode()
     extra = dict(restart_interval=int(restart_interval)) if restart_interval else {}
+    if optimize:
+        extra["optimize"] = True
     data = encode(bgr[None], quality=quality, sampling=capi.CK_JPEG_420 if sampling is None else sampling, **extra)[0]
     with open(path, "wb") as f:
         f.write(data)
@@ -305,14 +308,16 @@ class MjpegWriter:
     `encode`: a callable (frames, quality=, sampling=) -> [bytes], by default jpeg_encode of the process-wide Context.
     `restart_interval`: MCUs between restart markers (0: none; handed to `encode` as restart_interval= only when set) -- a
     film with them decodes in parallel pieces in the device entropy mode (Context.jpeg_set_entropy).
+    `optimize`: Huffman tables fitted to every frame, a smaller film of the same pixels (handed on as optimize=True only when set).
     A batch that would take the file past AVI_MAX_BYTES raises AviError before any of it is written (the reader stops
     there: no OpenDML); the file can still be closed and holds the batches before.  Use as a context manager, or close()."""
 
-    def __init__(self, path, h, w, fps=30.0, quality=90, sampling=None, encode=None, restart_interval=0):
+    def __init__(self, path, h, w, fps=30.0, quality=90, sampling=None, encode=None, restart_interval=0, optimize=False):
         from .. import capi
         self.path, self.h, self.w = path, int(h), int(w)
         self.quality = int(quality)
         self.restart_interval = int(restart_interval)
+        self.optimize = bool(optimize)
         self.sampling = capi.CK_JPEG_420 if sampling is None else int(sampling)
         self.encode = encode
         self.rate, self.scale = (int(fps[0]), int(fps[1])) if isinstance(fps, (tuple, list)) else (int(round(float(fps) * 1000)), 1000)
@@ -361,6 +366,8 @@ class MjpegWriter:
         if self.encode is None:
             self.encode = _default_encode()
         extra = dict(restart_interval=self.restart_interval) if self.restart_interval else {}
+        if self.optimize:
+            extra["optimize"] = True
         streams = self.encode(frames, quality=self.quality, sampling=self.sampling, **extra)
         if len(streams) != shp[0]:
             raise AviError("the encoder gave %d streams for %d frames" % (len(streams), shp[0]))

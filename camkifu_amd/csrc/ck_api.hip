@@ -1132,15 +1132,15 @@ static int check_jpeg_out(ck_ctx* ctx, int h, int w, int sampling, int restart_i
 
 // the Huffman stage of n frames, in parallel; on failure *bad is the first frame that failed and `why` its message
 static int jpeg_encode_batch(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                             uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why)
+                             uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why, bool optimise = false)
 {
     const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64;
     std::vector<int> rcs((size_t)n, CK_OK);
     std::vector<std::string> msgs((size_t)n);
     ck_parallel_for(n, 16, [&](int f) {
         char msg[CK_JPEG_MSG];
-        rcs[f] = ck_jpeg_enc_entropy(coef + (size_t)f * cframe, quant, h, w, sampling, restart_interval, out + (size_t)f * stride, stride,
-                                     len + f, msg);
+        rcs[f] = (optimise ? ck_jpeg_enc_entropy_opt : ck_jpeg_enc_entropy)(coef + (size_t)f * cframe, quant, h, w, sampling, restart_interval,
+                                                                            out + (size_t)f * stride, stride, len + f, msg);
         if (rcs[f] != CK_OK) msgs[f] = msg;
     });
     for (int f = 0; f < n; f++)
@@ -1167,17 +1167,56 @@ int ck_jpeg_forward(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in
     CK_API_END(ctx)
 }
 
-int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                           uint8_t* out, size_t stride, size_t* len)
+// optimised tables count a frame's symbols in 32 bits
+static int check_jpeg_opt_blocks(ck_ctx* ctx, int h, int w, int sampling)
+{
+    if ((long long)ck_jpeg_blocks(h, w, sampling) > (long long)CK_ENC_OPT_MAX_BLOCKS)
+        return ck_fail(ctx, CK_ERR_ARG, "a %dx%d frame has %d blocks: optimised Huffman tables take 2^25", w, h, ck_jpeg_blocks(h, w, sampling));
+    return CK_OK;
+}
+
+static int jpeg_entropy_encode_host(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                    uint8_t* out, size_t stride, size_t* len, bool optimise)
 {
     if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
     CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
     CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
+    if (optimise) CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
     try {
         int bad = -1;
         std::string why;
-        const int rc = jpeg_encode_batch(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, why);
+        const int rc = jpeg_encode_batch(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, why, optimise);
         if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, why.c_str());
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                           uint8_t* out, size_t stride, size_t* len)
+{
+    return jpeg_entropy_encode_host(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
+}
+
+int ck_jpeg_entropy_encode_opt(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                               uint8_t* out, size_t stride, size_t* len)
+{
+    return jpeg_entropy_encode_host(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
+}
+
+static int jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                      uint8_t* out, size_t stride, size_t* len, bool optimise)
+{
+    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
+    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
+    if (optimise) CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
+    try {
+        int bad = -1;
+        char msg[CK_JPEG_MSG] = {0};
+        const int rc = (optimise ? ck_jpeg_enc_staged_opt : ck_jpeg_enc_staged)(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, msg);
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
         return CK_OK;
     } catch (const std::exception& e) {
         return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
@@ -1187,18 +1226,58 @@ int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, in
 int ck_jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
                                   uint8_t* out, size_t stride, size_t* len)
 {
-    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    return jpeg_entropy_encode_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
+}
+
+int ck_jpeg_entropy_encode_opt_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                      uint8_t* out, size_t stride, size_t* len)
+{
+    return jpeg_entropy_encode_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
+}
+
+int ck_jpeg_histogram(const int16_t* coef, int n, int h, int w, int sampling, int restart_interval, uint32_t* counts)
+{
+    if (!coef || !counts || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
     CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
-    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
+    CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
+    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64;
+    for (int f = 0; f < n; f++) {
+        char msg[CK_JPEG_MSG];
+        const int rc = ck_jpeg_enc_histogram(coef + (size_t)f * cframe, h, w, sampling, restart_interval, counts + (size_t)f * 4 * 256, msg);
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", f, msg);
+    }
+    return CK_OK;
+}
+
+int ck_jpeg_optimal_table(const uint32_t* counts, uint8_t* bits, uint8_t* vals, int32_t* count)
+{
+    if (!counts || !bits || !vals || !count) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
     try {
-        int bad = -1;
-        char msg[CK_JPEG_MSG] = {0};
-        const int rc = ck_jpeg_enc_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, msg);
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
+        ck_jpeg_enc_optimal_table(counts, bits, vals, count);
         return CK_OK;
     } catch (const std::exception& e) {
         return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
     }
+}
+
+int ck_jpeg_set_encode_tables(ck_ctx* ctx, int mode)
+{
+    CK_API_BEGIN(ctx)
+    if (mode != CK_JPEG_TABLES_STANDARD && mode != CK_JPEG_TABLES_OPTIMISED) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG table mode %d", mode);
+    ctx->jpeg_enc_tables = mode;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_jpeg_encode_histograms(ck_ctx* ctx, int n, uint32_t* counts)
+{
+    CK_API_BEGIN(ctx)
+    if (!counts) return ck_fail(ctx, CK_ERR_ARG, "counts is NULL");
+    if (n <= 0 || n != ctx->jenc_freq_frames) return ck_fail(ctx, CK_ERR_STATE, "the last pass counted %d frames, not %d", ctx->jenc_freq_frames, n);
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CK_HIP(ctx, hipMemcpy(counts, (const uint8_t*)ctx->jenc_work.p + ctx->jenc_freq_at, (size_t)n * 4 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CK_OK;
+    CK_API_END(ctx)
 }
 
 int ck_jpeg_enc_tiles(int32_t* blocks_per_tile, int32_t* bytes_per_tile)
@@ -1240,12 +1319,15 @@ static int jpeg_enc_pass_frames_device(int n, size_t cframe)
 // 8 bytes per frame down -> stuff into the packed buffer -> the streams down in one copy into the pinned block, scattered
 // to out + f * stride from there.  Returns with the stream idle.  On a refusal *bad is the lowest frame that has one and
 // `why` what the host coder says of it; a failure that is no frame's fault leaves *bad at -1, its message in the context.
+// With `optimise` the counters, tables, DHT segments and headers of the frames lie in the work block as well, the header in
+// front of and behind the DHT segments goes up with the constants, and nothing more comes down.
 static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* quant, int m, int h, int w, int sampling,
-                              int restart_interval, uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why)
+                              int restart_interval, uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why, bool optimise)
 {
     const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
     const size_t blocks = (size_t)m * g.blocks, tiles = (size_t)m * g.nseg * g.seg_tiles, segs = (size_t)m * g.nseg;
-    const size_t consts_bytes = sizeof(CkEncTables) + 64 + CK_JPEG_ENC_HEADER_BOUND;
+    const size_t consts_std = sizeof(CkEncTables) + 64 + CK_JPEG_ENC_HEADER_BOUND;
+    const size_t consts_bytes = consts_std + (optimise ? (size_t)CK_ENC_HEADER_SLOT + 64 : 0);
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     // the work block: 64-bit arrays first, then the 32-bit ones, then the constants
     size_t at = 0;
@@ -1253,6 +1335,9 @@ static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t
     const size_t a_head = take(2 * 8), a_tile_off = take(tiles * 8), a_seg_bits = take(segs * 8), a_seg_u0 = take((segs + m) * 8);
     const size_t a_frame_u0 = take(((size_t)m + 1) * 8), a_len = take((size_t)m * 8), a_out_off = take(((size_t)m + 1) * 8);
     const size_t a_bits = take(blocks * 4), a_tile_bits = take(tiles * 4), a_consts = take(consts_bytes);
+    const size_t om = optimise ? (size_t)m : 0;
+    const size_t a_freq = take(om * 4 * 256 * 4), a_tables = take(om * sizeof(CkEncTables)), a_dht = take(om * 4 * CK_ENC_DHT_SLOT);
+    const size_t a_dht_len = take(om * 4 * 4), a_headers = take(om * CK_ENC_HEADER_SLOT), a_hlen = take(om * 4);
     CK_TRY(ck_ensure(ctx, ctx->jenc_work, at));
     uint8_t* wp = (uint8_t*)ctx->jenc_work.p;
     CkEncWork wk;
@@ -1260,6 +1345,13 @@ static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t
     wk.seg_u0 = (uint64_t*)(wp + a_seg_u0); wk.frame_u0 = (uint64_t*)(wp + a_frame_u0); wk.len = (uint64_t*)(wp + a_len);
     wk.out_off = (uint64_t*)(wp + a_out_off); wk.bits = (uint32_t*)(wp + a_bits); wk.tile_bits = (uint32_t*)(wp + a_tile_bits);
     wk.consts = wp + a_consts;
+    ctx->jenc_freq_at = a_freq;
+    ctx->jenc_freq_frames = optimise ? m : 0;
+    if (optimise) {
+        wk.freq = (uint32_t*)(wp + a_freq); wk.tables = wp + a_tables; wk.dht = wp + a_dht; wk.dht_len = (uint32_t*)(wp + a_dht_len);
+        wk.headers = wp + a_headers; wk.hlen = (uint32_t*)(wp + a_hlen);
+        wk.pre = wk.consts + consts_std; wk.post = wk.pre + CK_ENC_HEADER_SLOT;
+    }
     // pinned: the constants going up, the size words coming down
     const size_t p_words = up16(consts_bytes);
     CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, p_words + 16 + (size_t)m * 8));
@@ -1268,6 +1360,10 @@ static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t
     memcpy(hp + sizeof(CkEncTables), ck_jpeg_enc_zigzag(), 64);
     memset(hp + sizeof(CkEncTables) + 64, 0, CK_JPEG_ENC_HEADER_BOUND);
     const uint32_t hl = (uint32_t)ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, hp + sizeof(CkEncTables) + 64);
+    if (optimise) {
+        memset(hp + consts_std, 0, (size_t)CK_ENC_HEADER_SLOT + 64);
+        ck_jpeg_enc_header_parts(quant, h, w, sampling, restart_interval, hp + consts_std, &wk.pre_len, hp + consts_std + CK_ENC_HEADER_SLOT, &wk.post_len);
+    }
     CK_HIP(ctx, hipMemcpyAsync(wp + a_consts, hp, consts_bytes, hipMemcpyHostToDevice, ctx->stream));
     uint64_t* words = (uint64_t*)(hp + p_words);
 
@@ -1314,8 +1410,8 @@ static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t
     return CK_OK;
 }
 
-int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
-                                  int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
+static int jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                      int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len, bool optimise)
 {
     CK_API_BEGIN(ctx)
     ctx->jpeg_downloaded = 0;
@@ -1323,6 +1419,7 @@ int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space
     if (in_space != CK_HOST && in_space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", in_space);
     CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
     CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
+    if (optimise) CK_TRY(check_jpeg_opt_blocks(ctx, h, w, sampling));
     if (in_space == CK_DEVICE && ((uintptr_t)coef & 15)) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
     for (int f = 0; f < n; f++) len[f] = 0;
     char msg[CK_JPEG_MSG];
@@ -1336,12 +1433,24 @@ int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space
         int bad = -1;
         std::string why;
         const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)d_coef, quant, m, h, w, sampling, restart_interval, out + (size_t)f0 * stride,
-                                          stride, len + f0, &bad, why);
+                                          stride, len + f0, &bad, why, optimise);
         if (rc != CK_OK && bad < 0) return rc;
         if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
     }
     return CK_OK;
     CK_API_END(ctx)
+}
+
+int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                  int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
+{
+    return jpeg_entropy_encode_device(ctx, coef, in_space, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
+}
+
+int ck_jpeg_entropy_encode_opt_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                      int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
+{
+    return jpeg_entropy_encode_device(ctx, coef, in_space, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
 }
 
 int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
@@ -1351,6 +1460,8 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
     if (!bgr || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
     CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
     CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
+    const bool optimise = ctx->jpeg_enc_tables == CK_JPEG_TABLES_OPTIMISED;
+    if (optimise) CK_TRY(check_jpeg_opt_blocks(ctx, h, w, sampling));
     uint16_t quant[192];
     ck_jpeg_enc_quant(quality, quant);
     const size_t iframe = (size_t)h * w * 3, cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
@@ -1373,7 +1484,7 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
             int bad = -1;
             std::string why;
             const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)ctx->out_stage.p, quant, m, h, w, sampling, restart_interval,
-                                              out + (size_t)f0 * stride, stride, len + f0, &bad, why);
+                                              out + (size_t)f0 * stride, stride, len + f0, &bad, why, optimise);
             if (rc != CK_OK && bad < 0) return rc;
             if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
         }
@@ -1400,7 +1511,7 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
         int bad = -1;
         std::string why;
         const int rc = jpeg_encode_batch((const int16_t*)ctx->host_pinned.p, quant, m, h, w, sampling, restart_interval,
-                                         out + (size_t)f0 * stride, stride, len + f0, &bad, why);
+                                         out + (size_t)f0 * stride, stride, len + f0, &bad, why, optimise);
         if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
     }
     return CK_OK;

@@ -149,6 +149,9 @@ struct ck_ctx {
     int jpeg_span_bytes = 512;       // S of CK_JPEG_ENTROPY_DEVICE_SPANS (CK_SPAN_DEFAULT; ck_jpeg_set_span_bytes)
     long long jpeg_span_stats[4] = {0, 0, 0, 0};   // of the last decode in that mode (ck_jpeg_span_stats)
     int jpeg_enc_entropy = CK_JPEG_ENTROPY_HOST;   // where ck_jpeg_encode runs the Huffman stage (ck_jpeg_set_encode_entropy)
+    int jpeg_enc_tables = CK_JPEG_TABLES_STANDARD;   // the Huffman tables ck_jpeg_encode writes (ck_jpeg_set_encode_tables)
+    size_t jenc_freq_at = 0;         // where the last optimised pass left its counters in jenc_work, and of how many frames
+    int jenc_freq_frames = 0;        // (0: the last pass was a standard one) -- ck_jpeg_encode_histograms
     long long jpeg_downloaded = 0;   // bytes the last ck_jpeg_encode / ck_jpeg_entropy_encode_device copied from the device
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
@@ -315,8 +318,14 @@ struct CkEncWork {
     uint32_t *bits, *tile_bits;
     uint64_t *tile_off, *seg_bits, *seg_u0, *frame_u0, *head, *len, *out_off;
     const uint8_t* consts;
+    // optimised tables (freq NULL: the standard ones): per frame 4 x 256 counters, a CkEncTables, four DHT slots with their
+    // lengths, a header slot with its length; pre / post: the header in front of and behind the DHT segments (in consts)
+    uint32_t *freq = nullptr, *dht_len = nullptr, *hlen = nullptr;
+    uint8_t *tables = nullptr, *dht = nullptr, *headers = nullptr;
+    const uint8_t *pre = nullptr, *post = nullptr;
+    uint32_t pre_len = 0, post_len = 0;
 };
-// size every block and scan: fills all of the above but len and out_off
+// (optimised tables: histo and tables first, then) size every block and scan: fills all of the above but len and out_off
 int k_jpeg_enc_measure(ck_ctx* ctx, const int16_t* d_coef, int m, const CkEncGeom& g, const CkEncWork& w);
 // the codes into d_buf (total_u = head[1] bytes, zeroed here), the FF counts of its byte tiles, w.len and w.out_off
 int k_jpeg_enc_put(ck_ctx* ctx, const int16_t* d_coef, int m, const CkEncGeom& g, const CkEncWork& w, uint32_t* d_buf, uint64_t total_u,

@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -129,12 +131,11 @@ size_t ck_jpeg_enc_bound(int h, int w, int sampling)
     return HEADER_BOUND + (size_t)ck_jpeg_blocks(h, w, sampling) * BLOCK_BOUND + mcus * 4;
 }
 
-// in libjpeg's order
-size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* out)
+// in libjpeg's order: what stands in front of the DHT segments, ...
+static void header_front(Out& o, const uint16_t* quant, int h, int w, int sampling)
 {
     const bool grey = sampling == CK_JPEG_GREY;
     const int ncomp = grey ? 1 : 3;
-    Out o{out};
     o.byte(0xFF); o.byte(0xD8);
     static const uint8_t JFIF[14] = {0x4A, 0x46, 0x49, 0x46, 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
     o.segment(0xE0, sizeof JFIF);
@@ -148,6 +149,23 @@ size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, in
     o.segment(0xC0, 6 + 3 * (size_t)ncomp);
     o.byte(8); o.be16((unsigned)h); o.be16((unsigned)w); o.byte((unsigned)ncomp);
     for (int c = 0; c < ncomp; c++) { o.byte((unsigned)c + 1); o.byte(c == 0 ? (unsigned)(hs * 16 + vs) : 0x11u); o.byte(c ? 1u : 0u); }
+}
+// ... and what stands behind them
+static void header_back(Out& o, int sampling, int restart_interval)
+{
+    const int ncomp = sampling == CK_JPEG_GREY ? 1 : 3;
+    if (restart_interval) { o.segment(0xDD, 2); o.be16((unsigned)restart_interval); }
+    o.segment(0xDA, 4 + 2 * (size_t)ncomp);
+    o.byte((unsigned)ncomp);
+    for (int c = 0; c < ncomp; c++) { o.byte((unsigned)c + 1); o.byte(c ? 0x11u : 0x00u); }
+    o.byte(0); o.byte(63); o.byte(0);
+}
+
+size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* out)
+{
+    const bool grey = sampling == CK_JPEG_GREY;
+    Out o{out};
+    header_front(o, quant, h, w, sampling);
     const struct { unsigned id; const uint8_t* bits; const uint8_t* vals; } dht[4] = {
         {0x00, STD_DC_LUMA_BITS, STD_DC_VALS}, {0x10, STD_AC_LUMA_BITS, STD_AC_LUMA_VALS},
         {0x01, STD_DC_CHROMA_BITS, STD_DC_VALS}, {0x11, STD_AC_CHROMA_BITS, STD_AC_CHROMA_VALS}};
@@ -159,12 +177,18 @@ size_t ck_jpeg_enc_headers(const uint16_t* quant, int h, int w, int sampling, in
         for (int i = 0; i < 16; i++) o.byte(dht[t].bits[i]);
         for (int i = 0; i < total; i++) o.byte(dht[t].vals[i]);
     }
-    if (restart_interval) { o.segment(0xDD, 2); o.be16((unsigned)restart_interval); }
-    o.segment(0xDA, 4 + 2 * (size_t)ncomp);
-    o.byte((unsigned)ncomp);
-    for (int c = 0; c < ncomp; c++) { o.byte((unsigned)c + 1); o.byte(c ? 0x11u : 0x00u); }
-    o.byte(0); o.byte(63); o.byte(0);
+    header_back(o, sampling, restart_interval);
     return (size_t)(o.p - out);
+}
+
+void ck_jpeg_enc_header_parts(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* pre, uint32_t* pre_len,
+                              uint8_t* post, uint32_t* post_len)
+{
+    Out a{pre}, b{post};
+    header_front(a, quant, h, w, sampling);
+    header_back(b, sampling, restart_interval);
+    *pre_len = (uint32_t)(a.p - pre);
+    *post_len = (uint32_t)(b.p - post);
 }
 
 int ck_jpeg_enc_entropy(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
@@ -247,9 +271,10 @@ void ck_jpeg_enc_status_message(uint32_t status, long long mcu, char* msg)
     else snprintf(msg, CK_JPEG_MSG, "AC value of %d bits (MCU %lld): baseline JPEG has 10", size, mcu);
 }
 
-// The steps of ck_jpeg_enc_stage.h in plain loops, tile by tile as the kernels of k_jpeg_enc_huff.hip run them.
-int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                       uint8_t* out, size_t stride, size_t* len, int* bad, char* msg)
+// The steps of ck_jpeg_enc_stage.h in plain loops, tile by tile as the kernels of k_jpeg_enc_huff.hip run them; with
+// `optimise` the histo and tables steps first, and the tables and the header of each frame its own.
+static int staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                  uint8_t* out, size_t stride, size_t* len, int* bad, char* msg, bool optimise)
 {
     msg[0] = 0;
     *bad = -1;
@@ -257,9 +282,58 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
     if (const int rc = check_args(coef, quant, h, w, sampling, restart_interval, out, len, msg)) { *bad = 0; return rc; }
     if (stride < ck_jpeg_enc_bound(h, w, sampling)) { *bad = 0; return refuse(msg, "output buffer of %zu bytes: too small for the headers", stride); }
     const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
-    const CkEncTables& T = ck_jpeg_enc_tables();
+    if (optimise && g.blocks > CK_ENC_OPT_MAX_BLOCKS) { *bad = 0; return refuse(msg, "%lld blocks in a frame: optimised tables take 2^25", (long long)g.blocks); }
     const size_t cframe = (size_t)g.blocks * 64;
     const int64_t ftiles = g.nseg * g.seg_tiles;
+
+    // histo and tables: the counters of every frame (a block that cannot be coded stops its walk there: size names it),
+    // its four tables, its header
+    const int ntab = sampling == CK_JPEG_GREY ? 2 : 4;
+    std::vector<CkEncTables> own(optimise ? (size_t)n : 0);
+    std::vector<uint8_t> headers((size_t)n * CK_ENC_HEADER_SLOT, 0);
+    std::vector<uint32_t> hlen((size_t)n, 0);
+    if (optimise) {
+        uint8_t pre[CK_ENC_HEADER_SLOT], post[64], dht[4 * CK_ENC_DHT_SLOT];
+        uint32_t pre_len, post_len, dht_len[4];
+        ck_jpeg_enc_header_parts(quant, h, w, sampling, restart_interval, pre, &pre_len, post, &post_len);
+        std::vector<uint32_t> freq(4 * 256);
+        auto work = std::make_unique<CkEncTreeWork>();
+        for (int f = 0; f < n; f++) {
+            const int16_t* fc = coef + (size_t)f * cframe;
+            std::fill(freq.begin(), freq.end(), 0u);
+            for (int64_t k = 0; k < g.nseg; k++)
+                for (int64_t t = 0; t < g.seg_tiles; t++) {
+                    int64_t b0;
+                    int cnt;
+                    ck_enc_tile_blocks(g, k, t, &b0, &cnt);
+                    for (int i = 0; i < cnt; i++) {
+                        const int64_t b = b0 + i, pb = ck_enc_pred_block(g, b);
+                        ck_enc_block_histo<CkEncPlainInc>(fc + ck_enc_place(g, b) * 64, pb < 0 ? 0 : fc[ck_enc_place(g, pb) * 64],
+                                                          ck_enc_is_chroma(g, b), freq.data(), ZIGZAG);
+                    }
+                }
+            memset(&own[f], 0, sizeof(CkEncTables));
+            for (int t = 0; t < ntab; t++) {
+                uint8_t bits[16], vals[256];
+                int32_t count;
+                for (int i = 0; i < 256; i++) work->freq[i] = freq[(size_t)t * 256 + i];
+                ck_enc_optimal_table(work.get(), bits, vals, &count, CkEncSerial());
+                ck_enc_fill(t & 1 ? &own[f].ac[t >> 1] : &own[f].dc[t >> 1], bits, vals);
+                dht_len[t] = ck_enc_dht(dht + (size_t)t * CK_ENC_DHT_SLOT, t, bits, vals, count);
+            }
+            hlen[f] = ck_enc_header_len(pre_len, dht_len, ntab, post_len);
+            if (hlen[f] > (uint32_t)CK_ENC_HEADER_SLOT) { *bad = f; return refuse(msg, "a header of %u bytes", hlen[f]); }
+            for (uint32_t i = 0; i < hlen[f]; i++)
+                headers[(size_t)f * CK_ENC_HEADER_SLOT + i] = ck_enc_header_byte(i, pre, pre_len, dht, dht_len, ntab, post);
+        }
+    } else {
+        const uint32_t hl = (uint32_t)ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, headers.data());
+        for (int f = 0; f < n; f++) {
+            hlen[f] = hl;
+            if (f) memcpy(headers.data() + (size_t)f * CK_ENC_HEADER_SLOT, headers.data(), hl);
+        }
+    }
+    auto tables_of = [&](int f) -> const CkEncTables& { return optimise ? own[f] : ck_jpeg_enc_tables(); };
 
     // size: every block, the bit sums of the tiles, the lowest (frame, block) that cannot be coded
     std::vector<uint32_t> bits((size_t)n * g.blocks), tile_bits((size_t)n * ftiles, 0);
@@ -274,7 +348,7 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
                     const int64_t b = b0 + i, pb = ck_enc_pred_block(g, b);
                     const int16_t* fc = coef + (size_t)f * cframe;
                     const int pred = pb < 0 ? 0 : fc[ck_enc_place(g, pb) * 64];
-                    const uint32_t r = ck_enc_block_bits(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &T, ZIGZAG);
+                    const uint32_t r = ck_enc_block_bits(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &tables_of(f), ZIGZAG);
                     bits[(size_t)f * g.blocks + b] = r;
                     if (r & CK_ENC_FAIL) { const uint64_t key = ((uint64_t)f << 32) | (uint64_t)b; if (key < fail) fail = key; }
                     else tile_bits[((size_t)f * g.nseg + k) * g.seg_tiles + t] += r;
@@ -310,7 +384,7 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
     frame_u0[n] = at;
 
     // put: every tile into words of its own, then into the zeroed buffer
-    std::vector<uint32_t> buf(at / 4, 0), words(CK_ENC_TILE_WORDS);
+    std::vector<uint32_t> buf(at / 4, 0), words(optimise ? CK_ENC_OPT_TILE_WORDS : CK_ENC_TILE_WORDS);
     for (int f = 0; f < n; f++)
         for (int64_t k = 0; k < g.nseg; k++)
             for (int64_t t = 0; t < g.seg_tiles; t++) {
@@ -330,7 +404,7 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
                     const int64_t b = b0 + i, pb = ck_enc_pred_block(g, b);
                     const int16_t* fc = coef + (size_t)f * cframe;
                     const int pred = pb < 0 ? 0 : fc[ck_enc_place(g, pb) * 64];
-                    ck_enc_block_put(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &T, ZIGZAG, sink);
+                    ck_enc_block_put(fc + ck_enc_place(g, b) * 64, pred, ck_enc_is_chroma(g, b), &tables_of(f), ZIGZAG, sink);
                 }
                 if (last && ck_enc_seg_pad(sbits)) sink.put((1u << ck_enc_seg_pad(sbits)) - 1, ck_enc_seg_pad(sbits));
                 for (int i = 0; i < nw; i++) {
@@ -341,9 +415,9 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
 
     // stuff: FF bytes of the byte tiles, their sums before a tile in its frame, then every byte to its place
     const uint8_t* bytes = (const uint8_t*)buf.data();
-    uint8_t header[CK_JPEG_ENC_HEADER_BOUND];
-    const size_t hl = ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, header);
     for (int f = 0; f < n; f++) {
+        const uint8_t* header = headers.data() + (size_t)f * CK_ENC_HEADER_SLOT;
+        const size_t hl = hlen[f];
         const uint64_t* su = seg_u0.data() + (size_t)f * (g.nseg + 1);
         const uint64_t u = su[g.nseg];
         uint8_t* o = out + (size_t)f * stride;
@@ -361,5 +435,96 @@ int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h,
         }
         len[f] = (size_t)ck_enc_stream_len(hl, u, ff, g.nseg);
     }
+    return CK_OK;
+}
+
+int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                       uint8_t* out, size_t stride, size_t* len, int* bad, char* msg)
+{
+    return staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, bad, msg, false);
+}
+
+int ck_jpeg_enc_staged_opt(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                           uint8_t* out, size_t stride, size_t* len, int* bad, char* msg)
+{
+    return staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, bad, msg, true);
+}
+
+// ---- optimised tables on the host: one pass counts, one pass codes ----
+int ck_jpeg_enc_histogram(const int16_t* coef, int h, int w, int sampling, int restart_interval, uint32_t* freq, char* msg)
+{
+    msg[0] = 0;
+    if (!coef || !freq) return refuse(msg, "NULL pointer");
+    if (h < 1 || w < 1 || h > 65535 || w > 65535) return refuse(msg, "bad JPEG frame size %dx%d: sides of 1 .. 65535", w, h);
+    if (sampling < CK_JPEG_GREY || sampling > CK_JPEG_420) return refuse(msg, "bad JPEG sampling %d", sampling);
+    if (restart_interval < 0 || restart_interval > 65535) return refuse(msg, "restart interval %d: 0 .. 65535 MCUs", restart_interval);
+    const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
+    if (g.blocks > CK_ENC_OPT_MAX_BLOCKS) return refuse(msg, "%lld blocks in a frame: optimised tables take 2^25", (long long)g.blocks);
+    memset(freq, 0, 4 * 256 * sizeof(uint32_t));
+    for (int64_t b = 0; b < g.blocks; b++) {
+        const int64_t pb = ck_enc_pred_block(g, b);
+        const uint32_t st = ck_enc_block_histo<CkEncPlainInc>(coef + ck_enc_place(g, b) * 64, pb < 0 ? 0 : coef[ck_enc_place(g, pb) * 64],
+                                                              ck_enc_is_chroma(g, b), freq, ZIGZAG);
+        if (st) { ck_jpeg_enc_status_message(st, (long long)(b / g.mcu_blocks), msg); return CK_ERR_ARG; }
+    }
+    return CK_OK;
+}
+
+void ck_jpeg_enc_optimal_table(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int32_t* count)
+{
+    auto work = std::make_unique<CkEncTreeWork>();
+    for (int i = 0; i < 256; i++) work->freq[i] = freq[i];
+    memset(vals, 0, 256);
+    ck_enc_optimal_table(work.get(), bits, vals, count, CkEncSerial());
+}
+
+int ck_jpeg_enc_entropy_opt(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
+                            uint8_t* out, size_t cap, size_t* len, char* msg)
+{
+    msg[0] = 0;
+    if (len) *len = 0;
+    if (const int rc = check_args(coef, quant, h, w, sampling, restart_interval, out, len, msg)) return rc;
+    if (cap < HEADER_BOUND) return refuse(msg, "output buffer of %zu bytes: too small for the headers", cap);
+    // the first pass: what is refused is refused before any table is made
+    uint32_t freq[4 * 256];
+    if (const int rc = ck_jpeg_enc_histogram(coef, h, w, sampling, restart_interval, freq, msg)) return rc;
+    const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
+    const int ntab = sampling == CK_JPEG_GREY ? 2 : 4;
+    auto T = std::make_unique<CkEncTables>();
+    memset(T.get(), 0, sizeof(CkEncTables));
+    Out o{out};
+    header_front(o, quant, h, w, sampling);
+    for (int t = 0; t < ntab; t++) {
+        uint8_t bits[16], vals[256], dht[CK_ENC_DHT_SLOT];
+        int32_t count;
+        ck_jpeg_enc_optimal_table(freq + 256 * t, bits, vals, &count);
+        ck_enc_fill(t & 1 ? &T->ac[t >> 1] : &T->dc[t >> 1], bits, vals);
+        const uint32_t n = ck_enc_dht(dht, t, bits, vals, count);
+        if ((size_t)(o.p - out) + n + 64 > HEADER_BOUND) return refuse(msg, "a header above %zu bytes", HEADER_BOUND);
+        memcpy(o.p, dht, n);
+        o.p += n;
+    }
+    header_back(o, sampling, restart_interval);
+
+    // the second pass: the scan, with room for an MCU whose every code has 16 bits
+    constexpr size_t OPT_BLOCK_BOUND = (size_t)(CK_ENC_OPT_BLOCK_BITS + 7) / 8 * 2;
+    const uint8_t* const end = out + cap;
+    BitWriter bw{o.p};
+    for (int64_t mcu = 0; mcu < g.mcus; mcu++) {
+        if ((size_t)(end - bw.p) < (size_t)g.mcu_blocks * OPT_BLOCK_BOUND + 8)
+            return refuse(msg, "output buffer of %zu bytes: too small (MCU %lld of %lld)", cap, (long long)mcu, (long long)g.mcus);
+        if (mcu && mcu % g.seg_mcus == 0) {
+            bw.pad();
+            *bw.p++ = 0xFF; *bw.p++ = (uint8_t)(0xD0 + ((mcu / g.seg_mcus - 1) & 7));
+        }
+        for (int j = 0; j < g.mcu_blocks; j++) {
+            const int64_t b = mcu * g.mcu_blocks + j, pb = ck_enc_pred_block(g, b);
+            ck_enc_block_put(coef + ck_enc_place(g, b) * 64, pb < 0 ? 0 : coef[ck_enc_place(g, pb) * 64], ck_enc_is_chroma(g, b), T.get(), ZIGZAG, bw);
+        }
+    }
+    if ((size_t)(end - bw.p) < 4) return refuse(msg, "output buffer of %zu bytes: too small", cap);
+    bw.pad();
+    *bw.p++ = 0xFF; *bw.p++ = 0xD9;
+    *len = (size_t)(bw.p - out);
     return CK_OK;
 }

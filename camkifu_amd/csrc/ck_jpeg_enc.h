@@ -46,3 +46,22 @@ void ck_jpeg_enc_status_message(uint32_t status, long long mcu, char* msg);
 // of it (the lowest MCU); every len[f] is 0 then.  stride is at least ck_jpeg_enc_bound.
 int ck_jpeg_enc_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
                        uint8_t* out, size_t stride, size_t* len, int* bad, char* msg);
+
+// ---- optimised Huffman tables (libjpeg's optimize_coding): tables fitted to each frame, the same coefficients ----
+// the symbols ck_jpeg_enc_entropy would emit for the frame, counted: freq[4][256], table t = 2 * chroma + ac (the order of
+// the DHT segments).  CK_ERR_ARG with the coder's message for a coefficient it refuses, and for a frame of more than 2^25
+// blocks (the counters have 32 bits).
+int ck_jpeg_enc_histogram(const int16_t* coef, int h, int w, int sampling, int restart_interval, uint32_t* freq, char* msg);
+// jpeg_gen_optimal_table: freq[256] -> bits[16] (codes of length 1 .. 16) and vals[256], of which *count are used
+void ck_jpeg_enc_optimal_table(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int32_t* count);
+// ck_jpeg_enc_entropy with the frame's own tables in its DHT segments: two passes over the coefficients.  The same
+// refusals, made in the first pass; the room an MCU needs is that of codes of 16 bits throughout.
+int ck_jpeg_enc_entropy_opt(const int16_t* coef, const uint16_t* quant, int h, int w, int sampling, int restart_interval,
+                            uint8_t* out, size_t cap, size_t* len, char* msg);
+// ck_jpeg_enc_staged with the histo and tables steps in front: the bytes and refusals of ck_jpeg_enc_entropy_opt
+int ck_jpeg_enc_staged_opt(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                           uint8_t* out, size_t stride, size_t* len, int* bad, char* msg);
+// the header without its DHT segments: SOI .. SOF0 -> pre (CK_ENC_HEADER_SLOT bytes of room), DRI and SOS -> post (64)
+void ck_jpeg_enc_header_parts(const uint16_t* quant, int h, int w, int sampling, int restart_interval, uint8_t* pre, uint32_t* pre_len,
+                              uint8_t* post, uint32_t* post_len);
+static_assert(CK_ENC_HEADER_SLOT == CK_JPEG_ENC_HEADER_BOUND, "a frame's header slot on the device is the header bound");

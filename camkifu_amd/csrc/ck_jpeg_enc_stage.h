@@ -20,6 +20,14 @@
 //          byte i of a frame goes to header + i + (FF before i) + 2 * (segments before i) with 00 behind an FF, the marker
 //          FF D0+(k & 7) behind the last byte of segment k, FF D9 behind the last of all (ck_enc_emit).
 // The padded last byte of a segment is stuffed like any other when it comes out FF, as the host coder's pad() does.
+//
+// With OPTIMISED tables (libjpeg's optimize_coding) two steps come first, and the code tables and the header belong to a frame:
+//   histo  every block alone: the symbols ck_enc_block_walk names, counted into the frame's four tables of 256 counters --
+//          DC luma, AC luma, DC chroma, AC chroma, the order of the DHT segments.
+//   tables a table alone: libjpeg's jpeg_gen_optimal_table over its counters (ck_enc_optimal_table) -> the 16 counts and the
+//          values of a DHT segment, the CkEncHuff derived from them (ck_enc_fill), the segment's bytes (ck_enc_dht); then
+//          the frame's header: what stands in front of the DHT segments, the segments, what stands behind (ck_enc_header_byte).
+// A DC code can be 16 bits long then, so a block has up to CK_ENC_OPT_BLOCK_BITS bits and a tile CK_ENC_OPT_TILE_WORDS words.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -37,6 +45,12 @@ constexpr int CK_ENC_TILE_BYTES = 1024;                      // 256 lanes, a dwo
 constexpr int CK_ENC_BLOCK_BITS = 20 + 63 * 26;              // DC: 9 + 11, AC: 16 + 10
 // the bits of a full tile, 7 pad bits, up to 31 bits in front of it in its first dword
 constexpr int CK_ENC_TILE_WORDS = (CK_ENC_TILE_BLOCKS * CK_ENC_BLOCK_BITS + 7 + 31 + 31) / 32;
+// optimised tables: any code can have 16 bits
+constexpr int CK_ENC_OPT_BLOCK_BITS = 27 + 63 * 26;          // DC: 16 + 11, AC: 16 + 10
+constexpr int CK_ENC_OPT_TILE_WORDS = (CK_ENC_TILE_BLOCKS * CK_ENC_OPT_BLOCK_BITS + 7 + 31 + 31) / 32;
+constexpr int64_t CK_ENC_OPT_MAX_BLOCKS = (int64_t)1 << 25;  // of a frame: 64 symbols a block, so a counter stays below 2^32
+constexpr int CK_ENC_DHT_SLOT = 288;                         // room for a DHT segment of one table: 21 + 256 bytes, rounded up
+constexpr int CK_ENC_HEADER_SLOT = 1024;                     // room for a frame's header (CK_JPEG_ENC_HEADER_BOUND)
 
 // symbol -> code and length (0: the table has no such symbol)
 struct CkEncHuff {
@@ -125,30 +139,47 @@ CK_HD inline int ck_enc_bit_size(int v)
     return a ? 32 - __builtin_clz(a) : 0;
 }
 
-// the codes of a block as (value, length) pairs of at most 27 bits -- a code and the value bits behind it in one -- in the
-// host coder's order, with its refusals; 0 or a status word
-template <class Sink>
-CK_HD inline uint32_t ck_enc_block_put(const int16_t* blk, int pred, int is_chroma, const CkEncTables* T, const uint8_t* zigzag, Sink& sink)
+// the symbols of a block in the host coder's order, with its refusals: v.sym(ac, symbol, size, value) for the DC difference
+// (ac 0: the symbol is its size) and for every AC symbol (ZRL and EOB have size 0); 0 or a status word
+template <class Visit>
+CK_HD inline uint32_t ck_enc_block_walk(const int16_t* blk, int pred, const uint8_t* zigzag, Visit& v)
 {
-    const CkEncHuff& dc = T->dc[is_chroma];
-    const CkEncHuff& ac = T->ac[is_chroma];
     const int diff = (int)blk[0] - pred;
     int s = ck_enc_bit_size(diff);
     if (s > 11) return ck_enc_status(CK_ENC_DC, s);
-    sink.put(((uint32_t)dc.code[s] << s) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), dc.len[s] + s);
+    v.sym(0, s, s, diff);
     int run = 0;
     for (int k = 1; k < 64; k++) {
         const int val = blk[zigzag[k]];
         if (val == 0) { run++; continue; }
-        for (; run > 15; run -= 16) sink.put(ac.code[0xF0], ac.len[0xF0]);
+        for (; run > 15; run -= 16) v.sym(1, 0xF0, 0, 0);
         s = ck_enc_bit_size(val);
         if (s > 10) return ck_enc_status(CK_ENC_AC, s);
-        const int sym = (run << 4) | s;
-        sink.put(((uint32_t)ac.code[sym] << s) | ((uint32_t)(val < 0 ? val - 1 : val) & ((1u << s) - 1)), ac.len[sym] + s);
+        v.sym(1, (run << 4) | s, s, val);
         run = 0;
     }
-    if (run) sink.put(ac.code[0], ac.len[0]);
+    if (run) v.sym(1, 0, 0, 0);
     return 0;
+}
+
+// the codes of a block as (value, length) pairs of at most 27 bits -- a code and the value bits behind it in one -- in the
+// host coder's order, with its refusals; 0 or a status word
+template <class Sink>
+struct CkEncCoder {
+    const CkEncHuff& dc;
+    const CkEncHuff& ac;
+    Sink& sink;
+    CK_HD inline void sym(int is_ac, int symbol, int s, int val)
+    {
+        const CkEncHuff& t = is_ac ? ac : dc;
+        sink.put(((uint32_t)t.code[symbol] << s) | ((uint32_t)(val < 0 ? val - 1 : val) & ((1u << s) - 1)), t.len[symbol] + s);
+    }
+};
+template <class Sink>
+CK_HD inline uint32_t ck_enc_block_put(const int16_t* blk, int pred, int is_chroma, const CkEncTables* T, const uint8_t* zigzag, Sink& sink)
+{
+    CkEncCoder<Sink> coder{T->dc[is_chroma], T->ac[is_chroma], sink};
+    return ck_enc_block_walk(blk, pred, zigzag, coder);
 }
 
 struct CkEncCount {
@@ -215,3 +246,159 @@ CK_HD inline void ck_enc_emit(uint8_t* dst, const uint8_t* end, const uint64_t* 
 }
 // the length of a frame's stream
 CK_HD inline uint64_t ck_enc_stream_len(uint64_t header, uint64_t bytes, uint64_t ff, int64_t nseg) { return header + bytes + ff + 2 * (uint64_t)nseg; }
+
+// ---- optimised tables: histo and tables ----
+// table t of a frame's four: t = 2 * chroma + ac, the order of the DHT segments (DC0, AC0, DC1, AC1)
+CK_HD inline int ck_enc_table_index(int is_chroma, int is_ac) { return 2 * is_chroma + is_ac; }
+
+// histo on the host: the symbols of a block into the frame's counters (4 x 256); Add()(counter) is `++` here and an atomic
+// in LDS on the device
+struct CkEncPlainInc {
+    CK_HD inline void operator()(uint32_t* c) const { ++*c; }
+};
+template <class Add>
+struct CkEncHisto {
+    uint32_t* dc;                                            // the 256 counters of the block's DC table
+    uint32_t* ac;                                            // and of its AC table
+    CK_HD inline void sym(int is_ac, int symbol, int, int) { Add()((is_ac ? ac : dc) + symbol); }
+};
+template <class Add>
+CK_HD inline uint32_t ck_enc_block_histo(const int16_t* blk, int pred, int is_chroma, uint32_t* freq, const uint8_t* zigzag)
+{
+    CkEncHisto<Add> h{freq + 256 * ck_enc_table_index(is_chroma, 0), freq + 256 * ck_enc_table_index(is_chroma, 1)};
+    return ck_enc_block_walk(blk, pred, zigzag, h);
+}
+
+// jpeg_gen_optimal_table.  Sums in 64 bits; the caller puts the counters into freq[0 .. 255].  Who runs it is X: on the host
+// one thread (CkEncSerial); on the device a wave, whose lanes find the least entry together (x.least), lane 0 doing the
+// rest (x.one) with a barrier between the two (x.sync).  Every loop has a bound the counters cannot move.
+constexpr int CK_ENC_MAX_CLEN = 256;                         // 257 leaves: no code is longer before the lengths are limited
+struct CkEncTreeWork {
+    uint64_t freq[257];
+    int32_t codesize[257], others[257];                      // others: the merges (c1 | c2 << 16), then the sort's offsets
+    uint32_t nbits[CK_ENC_MAX_CLEN + 2];
+};
+struct CkEncSerial {
+    // the entry with the least non-zero freq other than `skip`, the largest index among equals; -1: none
+    CK_HD inline int least(const uint64_t* freq, int skip) const
+    {
+        uint64_t v = ~(uint64_t)0;
+        int c = -1;
+        for (int i = 0; i <= 256; i++)
+            if (i != skip && freq[i] && freq[i] <= v) { v = freq[i]; c = i; }
+        return c;
+    }
+    CK_HD inline bool one() const { return true; }
+    CK_HD inline void sync() const {}
+};
+// -> bits[16] (codes of length 1 .. 16), vals[256] (the first *count are used), as a DHT segment lists them
+template <class X>
+CK_HD inline void ck_enc_optimal_table(CkEncTreeWork* w, uint8_t* bits, uint8_t* vals, int32_t* count, const X& x)
+{
+    if (x.one()) {
+        w->freq[256] = 1;                                    // the pseudo-symbol: no real symbol gets the code of all ones
+        for (int i = 0; i <= 256; i++) { w->codesize[i] = 0; w->others[i] = 0; }
+        for (int i = 0; i < CK_ENC_MAX_CLEN + 2; i++) w->nbits[i] = 0;
+    }
+    x.sync();
+    int merges = 0;
+    for (; merges < 256; merges++) {
+        const int c1 = x.least(w->freq, -1);
+        const int c2 = c1 < 0 ? -1 : x.least(w->freq, c1);
+        if (c2 < 0) break;
+        x.sync();
+        if (x.one()) {
+            w->freq[c1] += w->freq[c2];
+            w->freq[c2] = 0;
+            w->others[merges] = c1 | (c2 << 16);
+        }
+        x.sync();
+    }
+    if (x.one()) {
+        // libjpeg adds 1 to the code size of every leaf of both trees at each merge, walking two chains of leaves.  The
+        // same sizes without the chains: from the last merge back, the tree that was absorbed (c2) gets what the absorbing
+        // one (c1, which stands for the merged tree from then on) collected later, and both get this merge.
+        for (int k = merges - 1; k >= 0; k--) {
+            const int c1 = w->others[k] & 0xffff, c2 = w->others[k] >> 16;
+            w->codesize[c2] = w->codesize[c1] + 1;
+            w->codesize[c1] += 1;
+        }
+        int top = 0;
+        for (int i = 0; i <= 256; i++) {
+            const int l = w->codesize[i] > CK_ENC_MAX_CLEN ? CK_ENC_MAX_CLEN : w->codesize[i];
+            if (l) { w->nbits[l]++; if (l > top) top = l; }
+        }
+        // no code above 16 bits: a pair of the longest codes goes one up beside a shorter code that goes one down.
+        // (libjpeg starts at 32 and gives up on a longer code; from `top` on the rule is the same where it has one)
+        int guard = 257 * CK_ENC_MAX_CLEN;
+        for (int i = top; i > 16; i--)
+            while (w->nbits[i] > 1 && guard-- > 0) {
+                int j = i - 2;
+                while (j > 0 && w->nbits[j] == 0) j--;
+                if (j == 0) { guard = 0; break; }
+                w->nbits[i] -= 2;
+                w->nbits[i - 1]++;
+                w->nbits[j + 1] += 2;
+                w->nbits[j]--;
+            }
+        int i = 16;
+        while (i > 0 && w->nbits[i] == 0) i--;
+        if (i) w->nbits[i]--;                                // the pseudo-symbol leaves
+        for (int l = 1; l <= 16; l++) bits[l - 1] = (uint8_t)w->nbits[l];
+        // the values by code length, by value inside a length: a counting sort over the lengths before they were limited
+        int32_t* start = w->others;
+        for (int l = 0; l <= CK_ENC_MAX_CLEN; l++) start[l] = 0;
+        for (int s = 0; s < 256; s++) {
+            const int l = w->codesize[s] > CK_ENC_MAX_CLEN ? CK_ENC_MAX_CLEN : w->codesize[s];
+            if (l) start[l]++;
+        }
+        int32_t at = 0;
+        for (int l = 1; l <= top; l++) { const int32_t c = start[l]; start[l] = at; at += c; }
+        for (int s = 0; s < 256; s++) {
+            const int l = w->codesize[s] > CK_ENC_MAX_CLEN ? CK_ENC_MAX_CLEN : w->codesize[s];
+            if (l) vals[start[l]++] = (uint8_t)s;
+        }
+        *count = at;
+    }
+    x.sync();
+}
+
+// bits[16] and vals of a DHT segment -> symbol to code and length
+CK_HD inline void ck_enc_fill(CkEncHuff* t, const uint8_t* bits, const uint8_t* vals)
+{
+    for (int i = 0; i < 256; i++) { t->code[i] = 0; t->len[i] = 0; }
+    int c = 0, k = 0;
+    for (int l = 1; l <= 16; l++) {
+        for (int i = 0; i < bits[l - 1] && k < 256; i++, c++, k++) { t->code[vals[k]] = (uint16_t)c; t->len[vals[k]] = (uint8_t)l; }
+        c <<= 1;
+    }
+}
+// the DHT segment of table t (count values) -> out (CK_ENC_DHT_SLOT bytes of room); its length
+CK_HD inline uint32_t ck_enc_dht(uint8_t* out, int t, const uint8_t* bits, const uint8_t* vals, int count)
+{
+    const int n = count < 0 ? 0 : (count > 256 ? 256 : count);
+    out[0] = 0xFF; out[1] = 0xC4;
+    out[2] = (uint8_t)((19 + n) >> 8); out[3] = (uint8_t)((19 + n) & 255);
+    out[4] = (uint8_t)(((t & 1) << 4) | (t >> 1));           // Tc << 4 | Th
+    for (int i = 0; i < 16; i++) out[5 + i] = bits[i];
+    for (int i = 0; i < n; i++) out[21 + i] = vals[i];
+    return (uint32_t)(21 + n);
+}
+// byte i of a frame's header: `pre` (SOI .. SOF0), the ntab DHT segments (slots of CK_ENC_DHT_SLOT bytes), `post` (DRI, SOS)
+CK_HD inline uint32_t ck_enc_header_len(uint32_t pre_len, const uint32_t* dht_len, int ntab, uint32_t post_len)
+{
+    uint32_t n = pre_len + post_len;
+    for (int t = 0; t < ntab; t++) n += dht_len[t];
+    return n;
+}
+CK_HD inline uint8_t ck_enc_header_byte(uint32_t i, const uint8_t* pre, uint32_t pre_len, const uint8_t* dht, const uint32_t* dht_len, int ntab,
+                                        const uint8_t* post)
+{
+    if (i < pre_len) return pre[i];
+    i -= pre_len;
+    for (int t = 0; t < ntab; t++) {
+        if (i < dht_len[t]) return dht[(size_t)t * CK_ENC_DHT_SLOT + i];
+        i -= dht_len[t];
+    }
+    return post[i];
+}

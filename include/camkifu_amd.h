@@ -207,10 +207,11 @@ int ck_jpeg_coefficients_spans(const uint8_t* const* data, const size_t* len, in
 /* ---- compressed output: baseline JPEG encode (.jpg stills, Motion-JPEG frames of an .avi)   core/vmanager.py:309-325 (cv2.imwrite)
  * The mirror of the calls above, and as exact: the streams are, byte for byte, what libjpeg's default compressor writes
  * (fixed-point RGB -> YCbCr, box downsampling without smoothing, slow-integer forward DCT, the quant tables of
- * jpeg_set_quality, the Huffman tables of Annex K.3, JFIF 1.01 headers) -- PIL.Image.save(.., "JPEG", quality=q, subsampling=s).
+ * jpeg_set_quality, the Huffman tables of Annex K.3 unless optimised ones are asked for, JFIF 1.01 headers) --
+ * PIL.Image.save(.., "JPEG", quality=q, subsampling=s).
  *   GPU:  BGR frames -> per frame int16 quantised coefficient blocks, in the layout ck_jpeg_coefficients writes (one kernel)
  *   host: headers + Huffman coder -> one stream per frame
- * No optimised tables, no progressive or arithmetic coding, quality 1 .. 100. */
+ * Optimised tables on request (ck_jpeg_set_encode_tables, below); no progressive or arithmetic coding, quality 1 .. 100. */
 /* quant[3][64] uint16 (natural order, by component) of a quality; clamped to 1 .. 100 (host only) */
 int ck_jpeg_quant(int quality, uint16_t* quant);
 /* *bytes: the largest stream a frame of h x w can become (host only) */
@@ -248,6 +249,35 @@ int ck_jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, in
                                   uint8_t* out, size_t stride, size_t* len);
 /* the tiles of those steps: blocks whose codes one workgroup assembles, unstuffed bytes one workgroup places (host only) */
 int ck_jpeg_enc_tiles(int32_t* blocks_per_tile, int32_t* bytes_per_tile);
+/* Optimised Huffman tables: libjpeg's optimize_coding, PIL.Image.save(.., optimize=True).  The coefficients, and so the pixels,
+ * are those of the standard mode; every DHT segment carries a table fitted to its frame, and the stream is, byte for byte,
+ * what libjpeg writes then.  Per frame: the symbols the coder emits are counted in its scan order (four tables of 256
+ * counters: DC luma, AC luma, DC chroma, AC chroma -- a grey frame has the first two), each table goes through
+ * jpeg_gen_optimal_table (the two least counts merge, the larger index among equals; no code is all ones; codes above
+ * 16 bits are shortened pairwise), and the scan is coded with the result.  What the standard mode refuses is refused with
+ * the same frame and message, before a table is made; a frame of more than 2^25 blocks is CK_ERR_ARG (32-bit counters).
+ * ck_jpeg_encode_bound holds for both modes. */
+enum { CK_JPEG_TABLES_STANDARD = 0, CK_JPEG_TABLES_OPTIMISED = 1 };
+/* what ck_jpeg_encode writes from now on, in either entropy mode; a new context has CK_JPEG_TABLES_STANDARD */
+int ck_jpeg_set_encode_tables(ck_ctx* ctx, int mode);
+/* host only: the counters of n frames, counts[n][4][256] uint32 in the order above */
+int ck_jpeg_histogram(const int16_t* coef, int n, int h, int w, int sampling, int restart_interval, uint32_t* counts);
+/* host only: counts[256] -> bits[16] (the number of codes of 1 .. 16 bits) and vals[256], of which *count are used: the
+ * body of a DHT segment */
+int ck_jpeg_optimal_table(const uint32_t* counts, uint8_t* bits, uint8_t* vals, int32_t* count);
+/* ck_jpeg_entropy_encode, _staged and _device with optimised tables: on the worker threads in two passes per frame; through
+ * the kernels' steps in plain loops on the host (histo and tables in front of size, scan, put, stuff); on the GPU, where the
+ * counters, the tables and the headers stay in HBM and ck_jpeg_downloaded_bytes counts what it counts in the standard mode */
+int ck_jpeg_entropy_encode_opt(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                               uint8_t* out, size_t stride, size_t* len);
+int ck_jpeg_entropy_encode_opt_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
+                                      uint8_t* out, size_t stride, size_t* len);
+int ck_jpeg_entropy_encode_opt_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
+                                      int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len);
+/* a test hook: the counters the kernels left in HBM in the last pass of the context's last optimised encode on the GPU,
+ * counts[n][4][256] as ck_jpeg_histogram gives them; n must be that pass's frames (CK_ERR_STATE otherwise, and after a
+ * standard encode).  A copy of its own: ck_jpeg_downloaded_bytes does not count it. */
+int ck_jpeg_encode_histograms(ck_ctx* ctx, int n, uint32_t* counts);
 
 /* ---- overlays: the finders' debug drawing (cv2.line / circle / rectangle / putText)   core/imgutil.py:71-118,
  * board/boardfinder.py:121-134, stone/stonesfinder.py:779-885, core/video.py:223-271

@@ -12,6 +12,10 @@ Frames of a filmed game (synth.film) at 1920x1080, resident in HBM; 4:2:0, quali
    run: HIP-event time per frame of its four kernels beside the forward kernel, the bytes that come down per frame in both
    modes, jpeg_encode frames/s in both modes at 128, 32, 8 and 1 frames a call (alternating rounds), and
    tools/transcode.record_gobans on a 128-frame film in both modes.  The streams of both modes are compared.
+5. optimised: Huffman tables fitted to every frame (jpeg_encode(optimize=True)) against the standard tables in the same run:
+   bytes per frame and their ratio, HIP-event time per frame of jpeg_enc_histo and jpeg_enc_tables beside the four other
+   steps, and jpeg_encode frames/s at 128, 32, 8 and 1 frames a call -- device-optimised against device-standard and
+   host-optimised against host-standard, alternating rounds.  The streams of both entropy modes are compared.
 Every leg is warmed up and runs `--reps` rounds: median / min / max.
 
     python tools/jpeg_enc_timing.py [--size 1920x1080] [--n 32] [--reps 7] [--inner 8]
@@ -32,6 +36,7 @@ from ingest_timing import HBM_PEAK, spread_of  # noqa: E402
 
 
 KERNELS = ("jpeg_enc_size", "jpeg_enc_scan", "jpeg_enc_put", "jpeg_enc_stuff")
+OPT_KERNELS = ("jpeg_enc_histo", "jpeg_enc_tables")
 
 
 def _fps(ctx, frames, quality, S, reps):
@@ -55,6 +60,58 @@ def _fps(ctx, frames, quality, S, reps):
         fps = sorted(n / t for t in ts)
         res[mode] = dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1), rounds=len(fps))
     res["device_over_host"] = round(res["device"]["median"] / res["host"]["median"], 3)
+    return res
+
+
+def _fps_tables(ctx, frames, quality, S, reps, mode):
+    """frames/s of jpeg_encode with the standard and with optimised tables in one entropy mode, alternating rounds"""
+    n = frames.shape[0]
+    calls = max(2, 256 // n)
+    ctx.jpeg_set_encode_entropy(mode)
+    secs = {"standard": [], "optimised": []}
+    for tables in secs:
+        ctx.jpeg_encode(frames, quality=quality, sampling=S, optimize=tables == "optimised")
+    for _ in range(reps):
+        for tables in secs:
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                ctx.jpeg_encode(frames, quality=quality, sampling=S, optimize=tables == "optimised")
+            secs[tables].append((time.perf_counter() - t0) / calls)
+    ctx.jpeg_set_encode_entropy("host")
+    res = {}
+    for tables, ts in secs.items():
+        fps = sorted(n / t for t in ts)
+        res[tables] = dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1), rounds=len(fps))
+    res["optimised_over_standard"] = round(res["optimised"]["median"] / res["standard"]["median"], 3)
+    return res
+
+
+def optimised(ctx, film, S, args):
+    n, q = film.shape[0], args.quality
+    res = {}
+    ctx.jpeg_set_encode_entropy("host")
+    standard = ctx.jpeg_encode(film, quality=q, sampling=S)
+    want = ctx.jpeg_encode(film, quality=q, sampling=S, optimize=True)
+    ctx.jpeg_set_encode_entropy("device")
+    res["streams_equal_the_host_modes"] = bool(ctx.jpeg_encode(film, quality=q, sampling=S, optimize=True) == want)
+    res["downloaded_bytes_per_frame_device"] = ctx.jpeg_downloaded_bytes() // n
+    a, b = float(np.mean([len(s) for s in standard])), float(np.mean([len(s) for s in want]))
+    res["jpeg_bytes_per_frame"] = dict(standard=int(a), optimised=int(b), optimised_over_standard=round(b / a, 4))
+    ctx.timing_enable(True)
+    per = {k: [] for k in ("jpeg_enc",) + OPT_KERNELS + KERNELS}
+    for _ in range(args.reps):
+        ctx.timing_reset()
+        ctx.jpeg_encode(film, quality=q, sampling=S, optimize=True)
+        for k in per:
+            per[k].append(ctx.timing_get(k)[0] / n)
+    ctx.timing_enable(False)
+    ctx.jpeg_set_encode_entropy("host")
+    res["kernel_ms_per_frame"] = {("jpeg_forward" if k == "jpeg_enc" else k): spread_of(v) for k, v in per.items()}
+    res["encode_frames_per_s"] = {}
+    for b in (128, 32, 8, 1):
+        frames = film if b == n else (film[:b].contiguous() if b < n else film.repeat((b + n - 1) // n, 1, 1, 1)[:b].contiguous())
+        res["encode_frames_per_s"]["%d_frames_a_call" % b] = {mode: _fps_tables(ctx, frames, q, S, args.reps, mode) for mode in ("device", "host")}
+        del frames
     return res
 
 
@@ -118,6 +175,7 @@ def main(argv=None):
     ap.add_argument("--n", type=int, default=32, help="frames per batch")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=8, help="kernel calls per round")
+    ap.add_argument("--only-optimised", action="store_true", help="skip leg 4 (its record_gobans runs take the longest)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_enc_timing.json"))
     args = ap.parse_args(argv)
     if args.reps < 5:
@@ -190,7 +248,9 @@ def main(argv=None):
         out["end_to_end"] = dict(frames_per_s=dict(median=round(float(np.median(fps)), 1), min=round(fps[0], 1), max=round(fps[-1], 1),
                                                    spread=round((fps[-1] - fps[0]) / float(np.median(fps)), 4), rounds=len(fps)),
                                  frames_resident_in_hbm=True, two_halves_equal_encode=bool(same))
-        out["device_entropy"] = device_entropy(ctx, capi, synth, dev, film, h, w, S, args)
+        if not args.only_optimised:
+            out["device_entropy"] = device_entropy(ctx, capi, synth, dev, film, h, w, S, args)
+        out["optimised"] = optimised(ctx, film, S, args)
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

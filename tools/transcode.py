@@ -4,12 +4,13 @@ Huffman coder on the host's worker threads or, with --encode-entropy device, on 
 appended to an .avi through core.capture.MjpegWriter.
 
     python tools/transcode.py SRC OUT.avi [--quality Q] [--sampling 420|422|444|grey] [--batch N] [--encode-entropy host|device]
+                              [--optimize]
     python tools/transcode.py SRC OUT.avi --gobans [--annotate] [--sgf game.sgf]
     python tools/transcode.py SRC OUT.avi --annotate [--sgf game.sgf]
 
 SRC is anything core.capture.open_capture takes: a .y4m file, a Motion-JPEG .avi, a .npy file of (n, h, w, 3) BGR frames.
 Every frame of SRC goes into OUT, at SRC's frame rate; a .y4m or .avi is converted / decoded straight into HBM and encoded
-from there.
+from there.  --optimize fits the Huffman tables to every frame (libjpeg's optimize_coding): the same pixels, a smaller file.
 
 --gobans records what the stones finder saw instead: SRC runs through a one-rank FastFilePipeline (a file thinned to
 cvconf.file_fps, as every run of a file is) and each batch's canonical 380 x 380 goban images are encoded while they are
@@ -70,8 +71,9 @@ def restart_mcus(restart, w, sampling):
     return n
 
 
-def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None, restart=0):
-    """restart: MCUs between restart markers, or "row" -> dict(frames, bytes, h, w, fps)"""
+def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None, restart=0, optimize=False):
+    """restart: MCUs between restart markers, or "row"; optimize: Huffman tables fitted to every frame
+    -> dict(frames, bytes, h, w, fps)"""
     from camkifu_amd import capi
     from camkifu_amd.core.capture import CAP_PROP_FPS, MjpegWriter, open_capture
     ctx = ctx if ctx is not None else capi.get_context()
@@ -84,7 +86,7 @@ def transcode(src, out, quality=90, sampling=3, batch=64, ctx=None, restart=0):
         h, w = capture.h, capture.w
     fps = capture.get(CAP_PROP_FPS) or 30.0
     with MjpegWriter(out, h, w, fps=fps, quality=quality, sampling=sampling, encode=ctx.jpeg_encode,
-                     restart_interval=restart_mcus(restart, w, sampling)) as wr:
+                     restart_interval=restart_mcus(restart, w, sampling), optimize=optimize) as wr:
         for frames in _frames_of(capture, ctx, batch):
             wr.write(frames)
     return dict(frames=wr.frames, bytes=os.path.getsize(out), h=int(h), w=int(w), fps=float(fps))
@@ -182,6 +184,8 @@ def main(argv=None):
                     "the device entropy mode decodes in parallel (plain transcoding only)")
     ap.add_argument("--encode-entropy", choices=("host", "device"), default="host", help="where the encoder's Huffman stage "
                     "runs: the host's worker threads, or the GPU (only the finished streams come down); the bytes are the same")
+    ap.add_argument("--optimize", action="store_true", help="Huffman tables fitted to every frame (libjpeg's optimize_coding): "
+                    "the same pixels in a smaller file, in either entropy mode")
     ap.add_argument("--gobans", action="store_true", help="record the 380x380 goban images of a pipeline run instead of the frames")
     ap.add_argument("--annotate", action="store_true", help="draw what the finders concluded onto the frames, on the GPU; "
                     "without --gobans the analysed frames are written at full size")
@@ -193,8 +197,9 @@ def main(argv=None):
     from camkifu_amd import capi
     ctx = capi.get_context()
     ctx.jpeg_set_encode_entropy(args.encode_entropy)
+    ctx.jpeg_set_encode_tables("optimised" if args.optimize else "standard")
     if not args.gobans and not args.annotate:
-        res = transcode(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx, restart=args.restart)
+        res = transcode(args.src, args.out, args.quality, sampling, args.batch, ctx=ctx, restart=args.restart, optimize=args.optimize)
         print("%s: %d frames of %dx%d at %.3g fps, %d bytes" % (args.out, res["frames"], res["w"], res["h"], res["fps"], res["bytes"]))
         return res
     import time

@@ -1401,11 +1401,14 @@ int k_cnn_pack_weights(ck_ctx* ctx, const float* const w[12], int space)
     const float* arrays[12];
     for (int i = 0; i < 12; i++) {
         float* h = host.data() + ck_cnn_offset(i);
-        if (space == CK_DEVICE) CK_HIP(ctx, hipMemcpy(h, w[i], CK_CNN_COUNTS[i] * 4, hipMemcpyDeviceToHost));
+        // device weights come down on the context's OWN stream: that is the stream ck_stream_wait has ordered behind their
+        // producer (a plain hipMemcpy runs on the null stream, which a non-blocking producer stream does not hold back)
+        if (space == CK_DEVICE) CK_HIP(ctx, hipMemcpyAsync(h, w[i], CK_CNN_COUNTS[i] * 4, hipMemcpyDeviceToHost, ctx->stream));
         else if (space == CK_HOST) memcpy(h, w[i], CK_CNN_COUNTS[i] * 4);
         else return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", space);
         arrays[i] = h;
     }
+    if (space == CK_DEVICE) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     CnnPacks P;
     ck_cnn_pack(arrays, P);
     CnnWeights& W = ctx->cnn;

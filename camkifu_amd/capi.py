@@ -65,6 +65,11 @@ class JpegInfo(C.Structure):
                 ("blocks", C.c_int32)]                     # ck_jpeg_info
 
 
+class PngInfo(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("color_type", C.c_int32), ("bit_depth", C.c_int32),
+                ("palette_entries", C.c_int32), ("reserved", C.c_int32), ("rowbytes", C.c_longlong)]      # ck_png_info
+
+
 def build(force=False):
     """Compile every HIP source for gfx950 into camkifu_amd/libck_hip.so (in-tree)."""
     if force:
@@ -598,6 +603,47 @@ class Context:
         fn = lib().ck_jpeg_entropy_encode_opt_device if optimize else lib().ck_jpeg_entropy_encode_device
         self._chk(fn(self._h, p, sp, quant.ctypes.data_as(C.c_void_p), n, h, w, sampling,
                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens))
+        return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+
+    def png_decode(self, streams, to_device=None, out=None):
+        """PNG files (a list of bytes-like objects or uint8 arrays in host memory, all of the first one's height and width,
+        each of its own colour type, bit depth and palette) -> BGR frames (n, h, w, 3), what cv2.imread gives: alpha dropped,
+        16-bit samples cut to their high byte.  The chunk walk and the inflate run on the host (the frames of a batch in
+        parallel), the unfiltering and the expansion to BGR in one kernel.  `to_device`: a torch device to leave the frames
+        in HBM; `out`: a preallocated (n, h, w, 3) array / tensor to fill.  CkError with code CK_ERR_DATA and a message that
+        names the frame and the cause for a file the reader refuses or that is damaged; its index is the error's `bad_frame`."""
+        ptrs, lens, keep = _jpeg_streams(streams)
+        n = len(keep)
+        info = PngInfo()
+        rc = lib().ck_png_header(C.c_void_p(keep[0].ctypes.data), keep[0].size, C.byref(info))     # (the size of the output)
+        if rc != 0:
+            err = CkError("libck_hip error %d: frame 0: %s" % (rc, (lib().ck_last_error(None) or b"").decode()))
+            err.code, err.bad_frame = rc, 0
+            raise err
+        out, op, osp = self._out(None, (n, info.h, info.w, 3), np.uint8, out, to_device)
+        bad = C.c_int32(-1)
+        rc = lib().ck_png_decode(self._h, ptrs, lens, n, op, osp, C.byref(bad))
+        if rc != 0:
+            err = CkError("libck_hip error %d: %s" % (rc, (lib().ck_last_error(self._h) or b"").decode()))
+            err.code = rc
+            if bad.value >= 0:
+                err.bad_frame = bad.value
+            raise err
+        return out
+
+    def png_encode(self, frames, filter=None):
+        """BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM -> a list of n `bytes`: 8-bit RGB
+        PNG files with one IDAT chunk.  filter: None chooses per row the type with the least sum of absolute residuals
+        (libpng's heuristic), 0 .. 4 forces None / Sub / Up / Avg / Paeth.  Filtering, the Huffman codes (one deflate block
+        per band of png_tiles()["band_rows"] rows, literals only), the bit packing and the Adler-32 run on the GPU; only the
+        zlib streams come down, the chunks and their CRCs are put around them on the host."""
+        _check_frames(frames)
+        n, h, w = self._shape(frames, 3)
+        stride = png_encode_bound(h, w)
+        p, sp, keep = self._in(frames)
+        out = np.empty(n * stride, np.uint8)             # (pages the files do not reach are never touched)
+        lens = (C.c_size_t * n)()
+        self._chk(lib().ck_png_encode(self._h, p, n, h, w, sp, _png_filter(filter), out.ctypes.data_as(C.c_void_p), stride, lens))
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
     def overlay_draw(self, images, lists):
@@ -1357,6 +1403,87 @@ def jpeg_enc_tiles():
     if rc != 0:
         raise _host_error(rc)
     return b.value, y.value
+
+
+def _png_info(stream, deep):
+    ptrs, lens, keep = _jpeg_streams([stream])
+    info = PngInfo()
+    fn = lib().ck_png_probe if deep else lib().ck_png_header
+    rc = fn(C.c_void_p(keep[0].ctypes.data), keep[0].size, C.byref(info))
+    if rc != 0:
+        raise _host_error(rc)
+    return dict(h=info.h, w=info.w, color_type=info.color_type, bit_depth=info.bit_depth, palette_entries=info.palette_entries,
+                rowbytes=info.rowbytes)
+
+
+def png_header(stream):
+    """the chunk walk of one PNG file alone (signature, CRCs, IHDR) -> dict(h, w, color_type, bit_depth, palette_entries,
+    rowbytes); host only.  CkError (code CK_ERR_DATA) with the cause for a file the reader refuses."""
+    return _png_info(stream, False)
+
+
+def png_probe(stream):
+    """everything the host does for one PNG file -- the chunk walk, the inflate, the size of its output, the filter bytes --
+    -> the dict of png_header; host only.  CkError (code CK_ERR_DATA) with the cause for a file the reader refuses."""
+    return _png_info(stream, True)
+
+
+def png_inflate(data):
+    """a zlib stream -> its bytes, by the library's own inflate (host only): what zlib.decompress gives, and CkError (code
+    CK_ERR_DATA) where zlib.decompress raises"""
+    ptrs, lens, keep = _jpeg_streams([data])
+    cap = max(1 << 16, 8 * keep[0].size)
+    while True:
+        out = np.empty(cap, np.uint8)
+        total = C.c_size_t(0)
+        rc = lib().ck_png_inflate(C.c_void_p(keep[0].ctypes.data), keep[0].size, out.ctypes.data_as(C.c_void_p), cap, C.byref(total))
+        if rc != 0:
+            raise _host_error(rc)
+        if total.value <= cap:
+            return out[:total.value].tobytes()
+        cap = total.value
+
+
+def png_encode_bound(h, w):
+    """the largest file a frame of h x w can become, in bytes; host only"""
+    b = C.c_size_t(0)
+    rc = lib().ck_png_encode_bound(int(h), int(w), C.byref(b))
+    if rc != 0:
+        raise _host_error(rc)
+    return b.value
+
+
+def _png_filter(filter):
+    if filter is None:
+        return -1
+    if filter not in (0, 1, 2, 3, 4):
+        raise CkError("png filter: None (chosen per row) or 0 .. 4 (None, Sub, Up, Avg, Paeth) is needed, got %r" % (filter,))
+    return int(filter)
+
+
+def png_encode_staged(frames, filter=None):
+    """Context.png_encode through the same steps in plain loops on the host (host only): BGR frames (n, h, w, 3) or one
+    frame (h, w, 3) -> a list of n `bytes`, byte for byte what the GPU writes"""
+    _check_frames(frames)
+    frames = np.ascontiguousarray(frames.numpy() if _is_torch(frames) else frames, np.uint8)
+    n, h, w = Context._shape(frames, 3)
+    stride = png_encode_bound(h, w)
+    out = np.empty(n * stride, np.uint8)
+    lens = (C.c_size_t * n)()
+    rc = lib().ck_png_encode_staged(frames.ctypes.data_as(C.c_void_p), n, h, w, _png_filter(filter), out.ctypes.data_as(C.c_void_p), stride, lens)
+    if rc != 0:
+        raise _host_error(rc)
+    return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
+
+
+def png_tiles():
+    """the seams of the PNG kernels -> dict(band_rows, tile_bytes: the encoder's deflate block and bit-packing tile;
+    chunk_bytes, group_rows: what a lane of the unfilter kernel takes per step and the rows in flight); host only"""
+    v = [C.c_int32(0) for _ in range(4)]
+    rc = lib().ck_png_tiles(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise _host_error(rc)
+    return dict(zip(("band_rows", "tile_bytes", "chunk_bytes", "group_rows"), (x.value for x in v)))
 
 
 def overlay_plan(n, h, w, prims, frame_start, text_len=0):

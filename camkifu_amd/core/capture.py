@@ -14,7 +14,7 @@ uncompressed containers and over the one compressed format that decodes exactly,
                downsamples in one kernel (ck_i420_to_bgr_pyr)
   ArrayCapture an (n, h, w, 3) uint8 array or .npy file of BGR frames (memory mapped)
   AviMjpegCapture  .avi holding Motion-JPEG: the file is memory mapped, the frames' JPEG bytes go to the decoder as they lie
-  ImageCapture     a .jpg / .jpeg still, served over and over (the reference's CaptureReaderImg)
+  ImageCapture     a .jpg / .jpeg or .png still, served over and over (the reference's CaptureReaderImg)
 
 cv2 property ids are kept so CaptureReaderBase.skip reads like the reference's.
 
@@ -301,6 +301,24 @@ def write_jpeg(path, bgr, quality=90, sampling=None, encode=None, restart_interv
     return len(data)
 
 
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def write_png(path, bgr, encode=None, filter=None):
+    """one BGR image (h, w, 3), a numpy array or a tensor in HBM, as a PNG still: 8-bit RGB, lossless, what any viewer and
+    cv2.imread open.  encode: a callable (frames, filter=) -> [bytes], by default png_encode of the process-wide Context;
+    filter: None chooses per row (libpng's heuristic), 0 .. 4 forces one type.  -> bytes written"""
+    if len(bgr.shape) != 3 or bgr.shape[2] != 3:
+        raise ValueError("write_png takes one (h, w, 3) image, got %r" % (tuple(bgr.shape),))
+    if encode is None:
+        from .. import capi
+        encode = capi.get_context().png_encode
+    data = encode(bgr[None], filter=filter)[0]
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
 class MjpegWriter:
     """Motion-JPEG into a RIFF 'AVI ' file, streamed: write(frames) encodes a batch -- (n, h, w, 3) BGR, a numpy array or a
     tensor in HBM -- and appends one '00dc' chunk per frame; close() patches the RIFF, movi, avih and strh fields that depend
@@ -561,8 +579,9 @@ class AviMjpegCapture:
 
 
 class ImageCapture:
-    """The reference's CaptureReaderImg (core/vmanager.py:638-660) for a .jpg / .jpeg still: the image is decoded once
-    (`decode` as for AviMjpegCapture) and every read() returns a copy of it; get() returns 0 whatever is asked, and
+    """The reference's CaptureReaderImg (core/vmanager.py:638-660) for a .jpg / .jpeg or .png still: the image is decoded
+    once (`decode` as for AviMjpegCapture; by default jpeg_decode or, for a file that starts with the PNG signature,
+    png_decode of the process-wide Context) and every read() returns a copy of it; get() returns 0 whatever is asked, and
     nothing sleeps."""
 
     def __init__(self, path, decode=None):
@@ -574,7 +593,8 @@ class ImageCapture:
                 data = f.read()
             if decode is None:
                 from .. import capi
-                decode = capi.get_context().jpeg_decode
+                ctx = capi.get_context()
+                decode = ctx.png_decode if data[:8] == PNG_SIGNATURE else ctx.jpeg_decode
             self.img = np.asarray(decode([data]))[0]
         except (OSError, RuntimeError) as exc:
             self.error = exc
@@ -605,12 +625,12 @@ class ImageCapture:
 
 def open_capture(video, convert=None):
     """the capture for a controller's `video` attribute: an array, a .npy path, a .y4m path, an MJPEG .avi path or a
-    .jpg / .jpeg still"""
+    .jpg / .jpeg / .png still"""
     if isinstance(video, str) and video.lower().endswith(".y4m"):
         return Y4MCapture(video, convert=convert)
     if isinstance(video, str) and video.lower().endswith(".avi"):
         return AviMjpegCapture(video)
-    if isinstance(video, str) and video.lower().endswith((".jpg", ".jpeg")):
+    if isinstance(video, str) and video.lower().endswith((".jpg", ".jpeg", ".png")):
         return ImageCapture(video)
     return ArrayCapture(video)
 

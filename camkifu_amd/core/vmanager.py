@@ -69,26 +69,38 @@ class VManagerBase(Thread):
     def vid_progress(self, percent):
         """progress listeners (a GUI) hook in here"""
 
+    def snapshot_png(self, save_goban=False, encode=None):
+        """snapshot() as a PNG still: lossless like the .npy, and a picture any viewer opens -- the reference's own
+        snapshot-N.png (core/vmanager.py:309-325), encoded on the GPU (`encode`: see capture.write_png).  N counts all three
+        kinds; game-N.sgf goes beside it with save_goban.  -> the snapshot's path, None without an image"""
+        return self._snapshot(save_goban, "png", encode)
+
     def snapshot(self, save_goban=False, fmt="npy", encode=None):
         """save the stones finder's canonical goban image as the next free snapshot-N of cvconf.snapshot_dir and, with
         save_goban, the game so far as game-N.sgf beside it: what NNManager.gen_data reads.  fmt "npy" (the default) is
         lossless; "jpg" is a picture any viewer opens, as the reference's cv2.imwrite gives (core/vmanager.py:309-325):
         baseline JPEG, quality 95, 4:4:4, encoded on the GPU (`encode`: see capture.write_jpeg).  N counts both kinds, so
-        the two never share a number.  -> the snapshot's path, None without an image"""
+        the kinds never share a number (snapshot_png's files count too).  -> the snapshot's path, None without an image"""
+        if fmt not in ("npy", "jpg"):
+            raise ValueError("snapshot format %r: npy or jpg" % (fmt,))
+        return self._snapshot(save_goban, fmt, encode)
+
+    def _snapshot(self, save_goban, fmt, encode):
         import os
         import re
         import numpy as np
-        if fmt not in ("npy", "jpg"):
-            raise ValueError("snapshot format %r: npy or jpg" % (fmt,))
         img = getattr(self.stones_finder, "goban_img", None)
         if img is None:
             print("No goban image available to save")
             return None
         folder = cvconf.snapshot_dir
-        taken = [int(m.group(1)) for m in (re.fullmatch(r"snapshot-(\d+)\.(?:npy|jpg)", f) for f in os.listdir(folder))
+        taken = [int(m.group(1)) for m in (re.fullmatch(r"snapshot-(\d+)\.(?:npy|jpg|png)", f) for f in os.listdir(folder))
                  if m and os.path.isfile(os.path.join(folder, m.group(0)))]
         name = "snapshot-%d.%s" % (max(taken, default=-1) + 1, fmt)
-        if fmt == "jpg":
+        if fmt == "png":
+            from .capture import write_png
+            write_png(os.path.join(folder, name), img[0] if len(img.shape) == 4 else img, encode=encode)
+        elif fmt == "jpg":
             from .capture import write_jpeg
             from .. import capi
             write_jpeg(os.path.join(folder, name), img[0] if len(img.shape) == 4 else img, quality=95, sampling=capi.CK_JPEG_444,

@@ -18,6 +18,7 @@
 #include "ck_jpeg_strand.h"
 #include "ck_jpeg_span.h"
 #include "ck_jpeg_enc.h"
+#include "ck_png.h"
 #include "ck_overlay.h"
 
 thread_local std::string g_ck_create_error;
@@ -1513,6 +1514,216 @@ int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_
         const int rc = jpeg_encode_batch((const int16_t*)ctx->host_pinned.p, quant, m, h, w, sampling, restart_interval,
                                          out + (size_t)f0 * stride, stride, len + f0, &bad, why, optimise);
         if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
+    }
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// ---- PNG: the host half (ck_png.cpp) behind the ABI, and the two calls that reach the GPU (k_png.hip) ----
+static void png_info_of(const CkPngHead& hd, ck_png_info* info)
+{
+    info->h = hd.h; info->w = hd.w; info->color_type = hd.color_type; info->bit_depth = hd.bit_depth;
+    info->palette_entries = hd.palette_n; info->reserved = 0; info->rowbytes = hd.rowbytes;
+}
+
+static int png_host_call(const uint8_t* data, size_t len, ck_png_info* info, bool deep)
+{
+    if (!data || !info) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    try {
+        CkPngHead hd;
+        char msg[CK_PNG_MSG];
+        int rc = ck_png_walk(data, len, &hd, msg);
+        if (rc == CK_OK && deep) {
+            std::vector<uint8_t> rows(hd.inflated());
+            rc = ck_png_rows(hd, rows.data(), msg);
+        }
+        if (rc != CK_OK) return ck_fail(nullptr, rc, "%s", msg);
+        png_info_of(hd, info);
+        return CK_OK;
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_png_header(const uint8_t* data, size_t len, ck_png_info* info) { return png_host_call(data, len, info, false); }
+int ck_png_probe(const uint8_t* data, size_t len, ck_png_info* info) { return png_host_call(data, len, info, true); }
+
+int ck_png_inflate(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total)
+{
+    if (!data || !total || (!out && cap)) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    try {
+        char msg[CK_PNG_MSG];
+        const int rc = ck_png_unzip(data, len, out, cap, total, msg);
+        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+static int check_png_size(ck_ctx* ctx, int h, int w)
+{
+    if (h <= 0 || w <= 0 || h > CK_PNG_MAX_SIDE || w > CK_PNG_MAX_SIDE || (long long)h * w > CK_PNG_MAX_PIXELS)
+        return ck_fail(ctx, CK_ERR_ARG, "bad PNG frame size %dx%d: 1 .. %d a side and up to 2^28 pixels", w, h, CK_PNG_MAX_SIDE);
+    return CK_OK;
+}
+
+int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, int32_t* group_rows)
+{
+    if (!band_rows || !tile_bytes || !chunk_bytes || !group_rows) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    *band_rows = CK_PNG_BAND_ROWS; *tile_bytes = CK_PNG_TILE_BYTES; *chunk_bytes = CK_PNG_CHUNK; *group_rows = CK_PNG_GROUP_ROWS;
+    return CK_OK;
+}
+
+int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space, int32_t* bad_frame)
+{
+    if (bad_frame) *bad_frame = -1;
+    CK_API_BEGIN(ctx)
+    if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    std::vector<CkPngHead> heads((size_t)n);
+    std::vector<int> rcs((size_t)n, CK_OK);
+    std::vector<std::string> msgs((size_t)n);
+    auto refused = [&](int f0) {
+        for (size_t f = 0; f < rcs.size(); f++)
+            if (rcs[f] != CK_OK) {
+                if (bad_frame) *bad_frame = f0 + (int)f;
+                (void)hipStreamSynchronize(ctx->stream);
+                return ck_fail(ctx, rcs[f], "frame %d: %s", f0 + (int)f, msgs[f].c_str());
+            }
+        return (int)CK_OK;
+    };
+    ck_parallel_for(n, 16, [&](int f) {
+        char msg[CK_PNG_MSG];
+        rcs[f] = ck_png_walk(data[f], len[f], &heads[f], msg);          // (a NULL stream is refused there)
+        if (rcs[f] != CK_OK) msgs[f] = msg;
+    });
+    CK_TRY(refused(0));
+    const int h = heads[0].h, w = heads[0].w;
+    for (int f = 1; f < n; f++)
+        if (heads[f].h != h || heads[f].w != w) {
+            if (bad_frame) *bad_frame = f;
+            return ck_fail(ctx, CK_ERR_DATA, "frame %d: %dx%d where the batch is %dx%d", f, heads[f].w, heads[f].h, w, h);
+        }
+    const size_t oframe = (size_t)h * w * 3;
+    OutStage<uint8_t> o;
+    CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // per pass: descriptors, palettes and the inflated rows of its frames in one pinned block -> one upload -> the kernel.
+    // A pass takes frames while their rows stay within 256 MB (one frame at least).
+    for (int f0 = 0; f0 < n;) {
+        int m = 0;
+        size_t rows_bytes = 0;
+        while (f0 + m < n && (m == 0 || rows_bytes + up16(heads[f0 + m].inflated()) <= ((size_t)256 << 20))) rows_bytes += up16(heads[f0 + m++].inflated());
+        const size_t a_pal = up16((size_t)m * sizeof(CkPngDesc)), a_rows = a_pal + (size_t)m * 768, total = a_rows + rows_bytes;
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
+        uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
+        CkPngDesc* desc = (CkPngDesc*)hp;
+        size_t at = a_rows;
+        for (int i = 0; i < m; i++) {
+            const CkPngHead& hd = heads[f0 + i];
+            desc[i].off = (int64_t)at; desc[i].rowbytes = hd.rowbytes; desc[i].color_type = hd.color_type; desc[i].depth = hd.bit_depth;
+            desc[i].bpp = hd.bpp; desc[i].palette_n = hd.palette_n;
+            memcpy(hp + a_pal + (size_t)i * 768, hd.palette, 768);
+            at += up16(hd.inflated());
+        }
+        rcs.assign((size_t)m, CK_OK);
+        msgs.assign((size_t)m, std::string());
+        ck_parallel_for(m, 16, [&](int i) {
+            char msg[CK_PNG_MSG];
+            rcs[i] = ck_png_rows(heads[f0 + i], hp + desc[i].off, msg);
+            if (rcs[i] != CK_OK) msgs[i] = msg;
+        });
+        CK_TRY(refused(f0));
+        const void* d_in;
+        CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage, &d_in));
+        CK_TRY(k_png_unfilter(ctx, (uint8_t*)ctx->in_stage.p, (const CkPngDesc*)d_in, (const uint8_t*)d_in + a_pal, m, h, w, o.dev + (size_t)f0 * oframe));
+        f0 += m;
+        if (f0 < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the next pass inflates into the same block
+    }
+    CK_TRY(o.deliver(ctx));
+    return finish(ctx);
+    CK_API_END(ctx)
+}
+
+int ck_png_encode_bound(int h, int w, size_t* bytes)
+{
+    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
+    CK_TRY(check_png_size(nullptr, h, w));
+    *bytes = ck_png_bound(h, w);
+    return CK_OK;
+}
+
+int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len)
+{
+    if (!bgr || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_png_size(nullptr, h, w));
+    if (filter < -1 || filter > 4) return ck_fail(nullptr, CK_ERR_ARG, "filter %d: 0 .. 4, or -1 to choose per row", filter);
+    try {
+        char msg[CK_PNG_MSG];
+        const int rc = ck_png_stage_encode(bgr, n, h, w, filter, out, stride, len, msg);
+        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int filter, uint8_t* out, size_t stride, size_t* len)
+{
+    CK_API_BEGIN(ctx)
+    if (!bgr || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    CK_TRY(check_png_size(ctx, h, w));
+    if (filter < -1 || filter > 4) return ck_fail(ctx, CK_ERR_ARG, "filter %d: 0 .. 4, or -1 to choose per row", filter);
+    if (stride < ck_png_bound(h, w))
+        return ck_fail(ctx, CK_ERR_ARG, "output buffer of %zu bytes per frame: smaller than the bound of %zu for a %dx%d frame", stride, ck_png_bound(h, w), w, h);
+    const CkPngGeom g = ck_png_geom(h, w);
+    const size_t iframe = (size_t)h * w * 3;
+    // a pass: frames whose filtered rows stay within 1 GiB (one frame at least)
+    const size_t fit = ((size_t)1 << 30) / (size_t)g.fbytes;
+    const int pass = fit < 1 ? 1 : fit < (size_t)n ? (int)fit : n;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    for (int f0 = 0; f0 < n; f0 += pass) {
+        const int m = n - f0 < pass ? n - f0 : pass;
+        const size_t bands = (size_t)m * g.bands, tiles = (size_t)m * g.tiles;
+        const void* d_in;
+        CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
+        // the work block: 64-bit arrays first, then the 32-bit ones, the 16-bit ones, the bytes
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t a = at; at = up16(at + bytes); return a; };
+        const size_t a_head = take(((size_t)m + 1) * 8), a_tile_off = take(tiles * 8), a_band_off = take(bands * 8), a_frame_bits = take((size_t)m * 8);
+        const size_t a_out_off = take(((size_t)m + 1) * 8), a_count = take(bands * CK_PNG_SYM_PITCH * 4), a_tile_bits = take(tiles * 4);
+        const size_t a_tile_a = take(tiles * 4), a_tile_b = take(tiles * 4), a_adler = take((size_t)m * 4);
+        const size_t a_band_bits = take(bands * 8), a_band_a = take(bands * 4), a_band_b = take(bands * 4);
+        const size_t a_codes = take(bands * CK_PNG_SYM_PITCH * 2), a_lens = take(bands * CK_PNG_SYM_PITCH), a_filt = take((size_t)m * g.fbytes);
+        CK_TRY(ck_ensure(ctx, ctx->png_work, at));
+        uint8_t* wp = (uint8_t*)ctx->png_work.p;
+        CkPngWork wk;
+        wk.head = (uint64_t*)(wp + a_head); wk.tile_off = (uint64_t*)(wp + a_tile_off); wk.band_off = (uint64_t*)(wp + a_band_off);
+        wk.frame_bits = (uint64_t*)(wp + a_frame_bits); wk.out_off = (uint64_t*)(wp + a_out_off); wk.count = (uint32_t*)(wp + a_count);
+        wk.tile_bits = (uint32_t*)(wp + a_tile_bits); wk.tile_a = (uint32_t*)(wp + a_tile_a); wk.tile_b = (uint32_t*)(wp + a_tile_b);
+        wk.band_bits = (uint64_t*)(wp + a_band_bits); wk.band_a = (uint32_t*)(wp + a_band_a); wk.band_b = (uint32_t*)(wp + a_band_b);
+        wk.adler = (uint32_t*)(wp + a_adler); wk.codes = (uint16_t*)(wp + a_codes); wk.lens = wp + a_lens; wk.filt = wp + a_filt;
+        CK_TRY(k_png_enc_measure(ctx, (const uint8_t*)d_in, m, g, filter, wk));
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ((size_t)m + 1) * 8));
+        uint64_t* words = (uint64_t*)ctx->host_pinned2.p;
+        CK_HIP(ctx, hipMemcpyAsync(words, wk.head, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t total = (size_t)words[0];
+        size_t sum = 0;
+        for (int f = 0; f < m; f++) {
+            if (CK_PNG_CONTAINER + words[1 + f] > stride) return ck_fail(ctx, CK_ERR_STATE, "frame %d: a stream of %llu bytes, above the bound", f0 + f, (unsigned long long)words[1 + f]);
+            sum += up16((size_t)words[1 + f]);
+        }
+        if (sum != total) return ck_fail(ctx, CK_ERR_STATE, "the streams of a pass: %zu bytes where their sizes give %zu", total, sum);
+        CK_TRY(ck_ensure(ctx, ctx->png_pack, total + 16));
+        CK_TRY(k_png_enc_put(ctx, m, g, wk, (uint32_t*)ctx->png_pack.p, total + 16));
+        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
+        CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, ctx->png_pack.p, total, hipMemcpyDeviceToHost, ctx->stream));
+        CK_TRY(finish(ctx));
+        // the container around every stream -- a copy and a CRC-32 over its bytes -- the frames on the worker threads
+        std::vector<size_t> off((size_t)m + 1, 0);
+        for (int f = 0; f < m; f++) off[(size_t)f + 1] = off[f] + up16((size_t)words[1 + f]);
+        ck_parallel_for(m, 16, [&](int f) {
+            len[f0 + f] = ck_png_wrap((const uint8_t*)ctx->host_pinned.p + off[f], (size_t)words[1 + f], h, w, out + (size_t)(f0 + f) * stride);
+        });
     }
     return CK_OK;
     CK_API_END(ctx)

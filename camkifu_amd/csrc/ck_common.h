@@ -22,6 +22,7 @@
 #include "ck_buf.h"        // DevBuf, PinBuf: buffers that free themselves
 #include "ck_cnn_pack.h"   // the classifier's weight arrays and their packs (host only)
 #include "ck_jpeg_enc_stage.h"   // CkEncGeom: the steps of the encoder's Huffman stage (plain C++)
+#include "ck_png_stage.h"        // CkPngGeom: the steps of the PNG encoder (plain C++)
 
 // the context's stream, destroyed with it
 struct CkStream {
@@ -136,6 +137,8 @@ struct ck_ctx {
     DevBuf jenc_bits;    // its unstuffed bits and the FF counts of their byte tiles,
     DevBuf jenc_pack;    // and its streams, one behind the other
     DevBuf jspan;        // CK_JPEG_ENTROPY_DEVICE_SPANS: candidates, entries and flags of a pass (k_jpeg_span.hip)
+    DevBuf png_work;     // the PNG encoder: filtered rows, counters, codes, sizes and offsets of a pass (CkPngWork),
+    DevBuf png_pack;     // and its zlib streams, one behind the other
 
     CnnWeights cnn;
     int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
@@ -333,6 +336,28 @@ int k_jpeg_enc_put(ck_ctx* ctx, const int16_t* d_coef, int m, const CkEncGeom& g
 // headers, stuffed bytes and markers into d_pack (pack_bytes of room), frame f at out_off[f]
 int k_jpeg_enc_stuff(ck_ctx* ctx, int m, const CkEncGeom& g, const CkEncWork& w, const uint32_t* d_buf, uint64_t total_u,
                      const uint32_t* d_ff_off, uint32_t hl, uint8_t* d_pack, uint64_t pack_bytes);
+// PNG (k_png.hip).  Reading: the inflated rows of n images (image i at d_rows + desc[i].off, h rows of 1 + rowbytes) are
+// unfiltered in place and expanded to BGR; palettes: 768 bytes an image.
+constexpr int CK_PNG_CHUNK = 24;           // bytes a lane handles per step: whole pixels at every depth (1 .. 64 bits a pixel)
+constexpr int CK_PNG_GROUP_ROWS = 256;     // rows in flight: the lanes of the workgroup
+struct CkPngDesc {
+    int64_t off, rowbytes;
+    int32_t color_type, depth, bpp, palette_n;
+};
+static_assert(sizeof(CkPngDesc) == 32, "a descriptor row is 32 bytes");
+int k_png_unfilter(ck_ctx* ctx, uint8_t* d_rows, const CkPngDesc* d_desc, const uint8_t* d_palettes, int n, int h, int w, uint8_t* d_bgr);
+// Writing, m frames: where the arrays of a pass lie in HBM -- per band (count, lens, codes: CK_PNG_SYM_PITCH each; band_off),
+// per tile, per frame (out_off: m + 1; head: the bytes of all streams, then the bytes of each)
+struct CkPngWork {
+    uint8_t *filt, *lens;
+    uint16_t* codes;
+    uint32_t *count, *tile_bits, *tile_a, *tile_b, *band_a, *band_b, *adler;
+    uint64_t *tile_off, *band_bits, *band_off, *frame_bits, *out_off, *head;      // tile_off: from the start of the band's block
+};
+// filter, count, build, size, scan: fills all of the above
+int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk);
+// the zlib streams into d_pack (pack_bytes, zeroed here: head[0] and a dword to spare), frame f at out_off[f]
+int k_png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes);
 // overlays (k_overlay.hip): n_work non-empty bins of the plan of ck_overlay.cpp, drawn in place on images of h x w x c
 int k_overlay(ck_ctx* ctx, uint8_t* d_img, int h, int w, int c, const int32_t* d_work, int n_work, const int32_t* d_refs,
               const int32_t* d_recs, const uint8_t* d_text);

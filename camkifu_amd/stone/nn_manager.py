@@ -44,7 +44,7 @@ def _aug_label_table():
 
 
 AUG_LABEL = _aug_label_table()
-SNAPSHOT_SUFFIXES = (".npy", ".jpg", ".jpeg")      # lossless, or a still read through open_capture (the project reads no PNG)
+SNAPSHOT_SUFFIXES = (".npy", ".jpg", ".jpeg", ".png")      # an array, or a still read through open_capture (.png: the reference's own snapshots)
 
 # The trained model file.  The reference downloads the author's keras.h5 into its training directory
 # (stone/nn_manager.py:22, 65-90); that file cannot be fetched here, so the package ships a classifier trained on the
@@ -187,7 +187,7 @@ class NNManager:
         for suffix in SNAPSHOT_SUFFIXES:
             if str(path).lower().endswith(suffix):
                 return str(path)[:-len(suffix)]
-        raise ValueError("a snapshot is a .npy or .jpg file: %s" % (path,))
+        raise ValueError("a snapshot is a .npy, .jpg or .png file: %s" % (path,))
 
     @staticmethod
     def get_ref_game(img_path):

@@ -279,6 +279,51 @@ int ck_jpeg_entropy_encode_opt_device(ck_ctx* ctx, const int16_t* coef, int in_s
  * standard encode).  A copy of its own: ck_jpeg_downloaded_bytes does not count it. */
 int ck_jpeg_encode_histograms(ck_ctx* ctx, int n, uint32_t* counts);
 
+/* ---- lossless stills: PNG   core/vmanager.py:309-325 (cv2.imwrite of snapshot-N.png), :638-660 (cv2.imread), stone/nn_manager.py:134
+ * Reading gives what cv2.imread's default mode gives: BGR, 8 bits; alpha and tRNS are dropped, never composited; 16-bit
+ * samples give their high byte; grey of 1 / 2 / 4 bits is scaled by 255 / 85 / 17; a palette index beyond PLTE is black.
+ *   host: the chunk walk (signature, every chunk's CRC-32, IHDR first, one PLTE in front of IDAT -- passed over in a grey
+ *         image, its entries beyond 2^depth dropped, as libpng does --, consecutive IDAT chunks joined, IEND; ancillary chunks
+ *         skipped, an unknown critical one and an IDAT behind another chunk refused) and an inflate of the library's own -- no libz -- whose verdict is zlib's;
+ *         the frames of a batch on the worker threads.  The filter bytes are checked there (0 .. 4).
+ *   GPU:  the inflated rows go up in one copy; one kernel undoes the filters along anti-diagonals (a lane per row, a chunk of
+ *         24 bytes per step, a barrier between steps) and writes BGR.
+ * Colour types 0, 2, 3, 4, 6 at every bit depth the standard allows them, not interlaced; sides up to 65535 and up to
+ * 2^28 pixels.  Anything else, and any damage, is CK_ERR_DATA with the cause in ck_last_error.
+ * Writing gives 8-bit RGB files with one IDAT: per row the filter with the least sum of |residual| (libpng's heuristic) or a
+ * forced one; per band of 16 rows one deflate block with a dynamic Huffman code of its own, literals only -- no matches, no
+ * runs: a flat image does not go below about one bit a byte.  Filter, count, build, size, scan and put are launches of
+ * their own; the Adler-32 is computed on the GPU too; only the zlib streams come down, the container is put around them
+ * on the host. */
+typedef struct ck_png_info {
+    int32_t h, w;
+    int32_t color_type;        /* 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGB + alpha        */
+    int32_t bit_depth;         /* 1, 2, 4, 8, 16                                                 */
+    int32_t palette_entries;   /* of PLTE, 0 without one                                         */
+    int32_t reserved;
+    long long rowbytes;        /* of an inflated row without its filter byte                     */
+} ck_png_info;
+/* host only: the chunk walk alone -> *info */
+int ck_png_header(const uint8_t* data, size_t len, ck_png_info* info);
+/* host only: everything the host does for a file -- the walk, the inflate, the sizes, the filter bytes -> *info */
+int ck_png_probe(const uint8_t* data, size_t len, ck_png_info* info);
+/* host only: a zlib stream -> its bytes.  The first cap of them go to out, *total counts all of them (call again with more
+ * room when it is above cap); the verdict -- wrapper, blocks, distances, Adler-32 -- is zlib's and does not depend on cap */
+int ck_png_inflate(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total);
+/* n files in HOST memory, all of the first one's height and width, each of its own colour type, depth and palette
+ * -> BGR n x h x w x 3 in out_space.  *bad_frame (nullable): the file a CK_ERR_DATA is about, else -1 */
+int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space, int32_t* bad_frame);
+/* the most bytes ck_png_encode writes for one frame */
+int ck_png_encode_bound(int h, int w, size_t* bytes);
+/* BGR n x h x w x 3 in in_space -> n files at out + f * stride (HOST memory), len[f] bytes each.  filter: 0 .. 4 forces None /
+ * Sub / Up / Avg / Paeth, -1 chooses per row.  stride must be at least ck_png_encode_bound */
+int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int filter, uint8_t* out, size_t stride, size_t* len);
+/* host only: ck_png_encode through the same steps in plain loops over host memory, the same bytes */
+int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len);
+/* the seams of the PNG kernels: rows of an encoder band, bytes of its bit-packing tile, bytes of the unfilter kernel's chunk,
+ * rows of its workgroup */
+int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, int32_t* group_rows);
+
 /* ---- overlays: the finders' debug drawing (cv2.line / circle / rectangle / putText)   core/imgutil.py:71-118,
  * board/boardfinder.py:121-134, stone/stonesfinder.py:779-885, core/video.py:223-271
  * A display list is an ordered list of primitives per image, drawn in place by one kernel in which pixels own the work.

@@ -21,6 +21,7 @@ CK_JPEG_GREY, CK_JPEG_444, CK_JPEG_422, CK_JPEG_420 = 0, 1, 2, 3
 CK_JPEG_ENTROPY_HOST, CK_JPEG_ENTROPY_DEVICE = 0, 1
 CK_JPEG_TABLES_STANDARD, CK_JPEG_TABLES_OPTIMISED = 0, 1
 CK_JPEG_ENTROPY_DEVICE_SPANS = 2
+CK_PNG_MATCH_NONE, CK_PNG_MATCH_RUNS = 0, 1
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
@@ -631,19 +632,54 @@ class Context:
             raise err
         return out
 
-    def png_encode(self, frames, filter=None):
+    _png_matches = "none"
+
+    def png_set_encode_matches(self, mode):
+        """what png_encode makes of repeated bytes from now on: "none" (the default: literals only) or "runs" (inside a band
+        every run of equal filtered bytes is one literal and matches of distance 1 behind it: what zlib's Z_RLE gains on flat
+        images; the same pixels come back)"""
+        modes = {"none": CK_PNG_MATCH_NONE, "runs": CK_PNG_MATCH_RUNS}
+        if mode not in modes:
+            raise CkError("png encode matches: 'none' or 'runs' is needed, got %r" % (mode,))
+        self._chk(lib().ck_png_set_encode_matches(self._h, modes[mode]))
+        self._png_matches = mode
+
+    def png_run_stats(self):
+        """the tokens of this context's last png_encode -> a list with dict(literals, matches) for each of its frames (the
+        end-of-block symbols are not counted; matches is 0 in the literal-only mode), read from the histograms the count
+        step left in HBM; [] where this context has encoded nothing yet or its last png_encode failed"""
+        n = self._png_frames
+        if n == 0:
+            return []
+        lit, mat = (C.c_longlong * n)(), (C.c_longlong * n)()
+        self._chk(lib().ck_png_run_stats(self._h, n, lit, mat))
+        return [dict(literals=int(lit[f]), matches=int(mat[f])) for f in range(n)]
+
+    _png_frames = 0
+
+    def png_encode(self, frames, filter=None, runs=None):
         """BGR frames (n, h, w, 3) or one frame (h, w, 3), numpy or a torch tensor in HBM -> a list of n `bytes`: 8-bit RGB
         PNG files with one IDAT chunk.  filter: None chooses per row the type with the least sum of absolute residuals
-        (libpng's heuristic), 0 .. 4 forces None / Sub / Up / Avg / Paeth.  Filtering, the Huffman codes (one deflate block
-        per band of png_tiles()["band_rows"] rows, literals only), the bit packing and the Adler-32 run on the GPU; only the
-        zlib streams come down, the chunks and their CRCs are put around them on the host."""
+        (libpng's heuristic), 0 .. 4 forces None / Sub / Up / Avg / Paeth.  runs: True / False asks for the runs mode or the
+        literal-only mode for this call, None takes what png_set_encode_matches has set (literals only in a new context).
+        Filtering, the Huffman codes (one deflate block per band of png_tiles()["band_rows"] rows), the bit packing and the
+        Adler-32 run on the GPU; only the zlib streams come down, the chunks and their CRCs are put around them on the host."""
+        if runs is not None and ("runs" if runs else "none") != self._png_matches:
+            was = self._png_matches
+            self.png_set_encode_matches("runs" if runs else "none")
+            try:
+                return self.png_encode(frames, filter)
+            finally:
+                self.png_set_encode_matches(was)
         _check_frames(frames)
         n, h, w = self._shape(frames, 3)
         stride = png_encode_bound(h, w)
         p, sp, keep = self._in(frames)
         out = np.empty(n * stride, np.uint8)             # (pages the files do not reach are never touched)
         lens = (C.c_size_t * n)()
+        self._png_frames = 0
         self._chk(lib().ck_png_encode(self._h, p, n, h, w, sp, _png_filter(filter), out.ctypes.data_as(C.c_void_p), stride, lens))
+        self._png_frames = n
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
     def overlay_draw(self, images, lists):
@@ -1461,16 +1497,23 @@ def _png_filter(filter):
     return int(filter)
 
 
-def png_encode_staged(frames, filter=None):
+def png_encode_staged(frames, filter=None, runs=False):
     """Context.png_encode through the same steps in plain loops on the host (host only): BGR frames (n, h, w, 3) or one
-    frame (h, w, 3) -> a list of n `bytes`, byte for byte what the GPU writes"""
+    frame (h, w, 3) -> a list of n `bytes`, byte for byte what the GPU writes.  runs: False the literal-only mode, True the
+    runs mode, or one of CK_PNG_MATCH_*"""
+    if not isinstance(runs, (bool, int, np.integer)):
+        raise CkError("png runs: True, False or one of CK_PNG_MATCH_* is needed, got %r" % (runs,))
     _check_frames(frames)
     frames = np.ascontiguousarray(frames.numpy() if _is_torch(frames) else frames, np.uint8)
     n, h, w = Context._shape(frames, 3)
     stride = png_encode_bound(h, w)
     out = np.empty(n * stride, np.uint8)
     lens = (C.c_size_t * n)()
-    rc = lib().ck_png_encode_staged(frames.ctypes.data_as(C.c_void_p), n, h, w, _png_filter(filter), out.ctypes.data_as(C.c_void_p), stride, lens)
+    if runs is False:
+        rc = lib().ck_png_encode_staged(frames.ctypes.data_as(C.c_void_p), n, h, w, _png_filter(filter), out.ctypes.data_as(C.c_void_p), stride, lens)
+    else:
+        rc = lib().ck_png_encode_staged_mode(frames.ctypes.data_as(C.c_void_p), n, h, w, _png_filter(filter), int(runs),
+                                             out.ctypes.data_as(C.c_void_p), stride, lens)
     if rc != 0:
         raise _host_error(rc)
     return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]

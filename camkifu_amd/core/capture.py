@@ -304,16 +304,18 @@ def write_jpeg(path, bgr, quality=90, sampling=None, encode=None, restart_interv
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
-def write_png(path, bgr, encode=None, filter=None):
+def write_png(path, bgr, encode=None, filter=None, runs=None):
     """one BGR image (h, w, 3), a numpy array or a tensor in HBM, as a PNG still: 8-bit RGB, lossless, what any viewer and
     cv2.imread open.  encode: a callable (frames, filter=) -> [bytes], by default png_encode of the process-wide Context;
-    filter: None chooses per row (libpng's heuristic), 0 .. 4 forces one type.  -> bytes written"""
+    filter: None chooses per row (libpng's heuristic), 0 .. 4 forces one type; runs: True / False asks the encoder for its
+    runs mode (flat areas shrink as under zlib's Z_RLE) or its literal-only mode, None leaves it what the context has set --
+    the keyword reaches `encode` only when it is not None.  -> bytes written"""
     if len(bgr.shape) != 3 or bgr.shape[2] != 3:
         raise ValueError("write_png takes one (h, w, 3) image, got %r" % (tuple(bgr.shape),))
     if encode is None:
         from .. import capi
         encode = capi.get_context().png_encode
-    data = encode(bgr[None], filter=filter)[0]
+    data = (encode(bgr[None], filter=filter) if runs is None else encode(bgr[None], filter=filter, runs=runs))[0]
     with open(path, "wb") as f:
         f.write(data)
     return len(data)

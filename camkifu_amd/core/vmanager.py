@@ -69,11 +69,14 @@ class VManagerBase(Thread):
     def vid_progress(self, percent):
         """progress listeners (a GUI) hook in here"""
 
-    def snapshot_png(self, save_goban=False, encode=None):
+    def snapshot_png(self, save_goban=False, encode=None, runs=None):
         """snapshot() as a PNG still: lossless like the .npy, and a picture any viewer opens -- the reference's own
-        snapshot-N.png (core/vmanager.py:309-325), encoded on the GPU (`encode`: see capture.write_png).  N counts all three
-        kinds; game-N.sgf goes beside it with save_goban.  -> the snapshot's path, None without an image"""
-        return self._snapshot(save_goban, "png", encode)
+        snapshot-N.png (core/vmanager.py:309-325), encoded on the GPU (`encode`, `runs`: see capture.write_png; runs=None
+        asks for the runs mode where cvconf.png_runs is set).  N counts all three kinds; game-N.sgf goes beside it with
+        save_goban.  -> the snapshot's path, None without an image"""
+        if runs is None and cvconf.png_runs:
+            runs = True
+        return self._snapshot(save_goban, "png", encode, runs)
 
     def snapshot(self, save_goban=False, fmt="npy", encode=None):
         """save the stones finder's canonical goban image as the next free snapshot-N of cvconf.snapshot_dir and, with
@@ -85,7 +88,7 @@ class VManagerBase(Thread):
             raise ValueError("snapshot format %r: npy or jpg" % (fmt,))
         return self._snapshot(save_goban, fmt, encode)
 
-    def _snapshot(self, save_goban, fmt, encode):
+    def _snapshot(self, save_goban, fmt, encode, runs=None):
         import os
         import re
         import numpy as np
@@ -99,7 +102,7 @@ class VManagerBase(Thread):
         name = "snapshot-%d.%s" % (max(taken, default=-1) + 1, fmt)
         if fmt == "png":
             from .capture import write_png
-            write_png(os.path.join(folder, name), img[0] if len(img.shape) == 4 else img, encode=encode)
+            write_png(os.path.join(folder, name), img[0] if len(img.shape) == 4 else img, encode=encode, runs=runs)
         elif fmt == "jpg":
             from .capture import write_jpeg
             from .. import capi

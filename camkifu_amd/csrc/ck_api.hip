@@ -1652,18 +1652,77 @@ int ck_png_encode_bound(int h, int w, size_t* bytes)
     return CK_OK;
 }
 
-int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len)
+int ck_png_encode_staged_mode(const uint8_t* bgr, int n, int h, int w, int filter, int matches, uint8_t* out, size_t stride, size_t* len)
 {
     if (!bgr || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
     CK_TRY(check_png_size(nullptr, h, w));
     if (filter < -1 || filter > 4) return ck_fail(nullptr, CK_ERR_ARG, "filter %d: 0 .. 4, or -1 to choose per row", filter);
+    if (matches != CK_PNG_MATCH_NONE && matches != CK_PNG_MATCH_RUNS) return ck_fail(nullptr, CK_ERR_ARG, "unknown PNG match mode %d", matches);
     try {
         char msg[CK_PNG_MSG];
-        const int rc = ck_png_stage_encode(bgr, n, h, w, filter, out, stride, len, msg);
+        const int rc = ck_png_stage_encode(bgr, n, h, w, filter, out, stride, len, msg, matches == CK_PNG_MATCH_RUNS);
         return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
     } catch (const std::exception& e) {
         return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
     }
+}
+
+int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len)
+{
+    return ck_png_encode_staged_mode(bgr, n, h, w, filter, CK_PNG_MATCH_NONE, out, stride, len);
+}
+
+int ck_png_set_encode_matches(ck_ctx* ctx, int mode)
+{
+    CK_API_BEGIN(ctx)
+    if (mode != CK_PNG_MATCH_NONE && mode != CK_PNG_MATCH_RUNS) return ck_fail(ctx, CK_ERR_ARG, "unknown PNG match mode %d", mode);
+    ctx->png_matches = mode;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+// the histograms the count step of the last pass left in png_work -> png_tokens, two numbers a frame.  known_literals >= 0
+// (the literal-only mode between two passes of one call, where every byte of a frame is one literal token): that number
+// for every frame, nothing is copied
+static int png_read_counts(ck_ctx* ctx, long long known_literals = -1)
+{
+    const int m = ctx->png_count_frames;
+    if (m <= 0) return CK_OK;
+    if (known_literals >= 0 && !ctx->png_count_runs) {
+        for (int f = 0; f < m; f++) { ctx->png_tokens.push_back(known_literals); ctx->png_tokens.push_back(0); }
+        ctx->png_count_frames = 0;
+        return CK_OK;
+    }
+    const size_t pitch = (size_t)ck_png_pitch(ctx->png_count_runs), per = (size_t)ctx->png_count_bands * pitch;
+    std::vector<uint32_t> count((size_t)m * per);
+    CK_HIP(ctx, hipMemcpyAsync(count.data(), (const uint8_t*)ctx->png_work.p + ctx->png_count_at, count.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int f = 0; f < m; f++) {
+        long long lit = 0, match = 0;
+        for (long long band = 0; band < ctx->png_count_bands; band++) {
+            const uint32_t* c = count.data() + (size_t)f * per + (size_t)band * pitch;
+            for (int s = 0; s < 256; s++) lit += c[s];
+            if (ctx->png_count_runs)
+                for (int s = 257; s < CK_PNG_RUN_SYMS; s++) match += c[s];
+        }
+        ctx->png_tokens.push_back(lit);
+        ctx->png_tokens.push_back(match);
+    }
+    ctx->png_count_frames = 0;
+    return CK_OK;
+}
+
+int ck_png_run_stats(ck_ctx* ctx, int n, long long* literals, long long* matches)
+{
+    CK_API_BEGIN(ctx)
+    if (!literals || !matches) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer");
+    CK_TRY(png_read_counts(ctx));
+    if (ctx->png_tokens.empty()) return ck_fail(ctx, CK_ERR_STATE, "no ck_png_encode of this context has completed: there are no tokens to report");
+    if (n <= 0 || (size_t)n * 2 != ctx->png_tokens.size())
+        return ck_fail(ctx, CK_ERR_STATE, "the last ck_png_encode took %zu frames, not %d", ctx->png_tokens.size() / 2, n);
+    for (int f = 0; f < n; f++) { literals[f] = ctx->png_tokens[2 * (size_t)f]; matches[f] = ctx->png_tokens[2 * (size_t)f + 1]; }
+    return CK_OK;
+    CK_API_END(ctx)
 }
 
 int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int filter, uint8_t* out, size_t stride, size_t* len)
@@ -1676,6 +1735,10 @@ int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
         return ck_fail(ctx, CK_ERR_ARG, "output buffer of %zu bytes per frame: smaller than the bound of %zu for a %dx%d frame", stride, ck_png_bound(h, w), w, h);
     const CkPngGeom g = ck_png_geom(h, w);
     const size_t iframe = (size_t)h * w * 3;
+    const int runs = ctx->png_matches == CK_PNG_MATCH_RUNS;
+    const size_t PITCH = (size_t)ck_png_pitch(runs);
+    ctx->png_tokens.clear();
+    ctx->png_count_frames = 0;
     // a pass: frames whose filtered rows stay within 1 GiB (one frame at least)
     const size_t fit = ((size_t)1 << 30) / (size_t)g.fbytes;
     const int pass = fit < 1 ? 1 : fit < (size_t)n ? (int)fit : n;
@@ -1683,16 +1746,21 @@ int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
     for (int f0 = 0; f0 < n; f0 += pass) {
         const int m = n - f0 < pass ? n - f0 : pass;
         const size_t bands = (size_t)m * g.bands, tiles = (size_t)m * g.tiles;
+        // the histograms of the pass before this one are overwritten now: the runs mode reads them first (a copy and a wait
+        // per further pass of a call above 1 GiB); the literal-only mode copies nothing, its tokens are the frame's bytes
+        CK_TRY(png_read_counts(ctx, (long long)g.fbytes));
         const void* d_in;
         CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
         // the work block: 64-bit arrays first, then the 32-bit ones, the 16-bit ones, the bytes
         size_t at = 0;
         auto take = [&](size_t bytes) { const size_t a = at; at = up16(at + bytes); return a; };
         const size_t a_head = take(((size_t)m + 1) * 8), a_tile_off = take(tiles * 8), a_band_off = take(bands * 8), a_frame_bits = take((size_t)m * 8);
-        const size_t a_out_off = take(((size_t)m + 1) * 8), a_count = take(bands * CK_PNG_SYM_PITCH * 4), a_tile_bits = take(tiles * 4);
+        const size_t a_out_off = take(((size_t)m + 1) * 8), a_count = take(bands * PITCH * 4), a_tile_bits = take(tiles * 4);
         const size_t a_tile_a = take(tiles * 4), a_tile_b = take(tiles * 4), a_adler = take((size_t)m * 4);
         const size_t a_band_bits = take(bands * 8), a_band_a = take(bands * 4), a_band_b = take(bands * 4);
-        const size_t a_codes = take(bands * CK_PNG_SYM_PITCH * 2), a_lens = take(bands * CK_PNG_SYM_PITCH), a_filt = take((size_t)m * g.fbytes);
+        const size_t a_codes = take(bands * PITCH * 2), a_lens = take(bands * PITCH), a_filt = take((size_t)m * g.fbytes);
+        // (the runs mode's arrays come last: the literal-only mode's block is what it was)
+        const size_t a_before = runs ? take(tiles * 4) : 0, a_after = runs ? take(tiles * 4) : 0, a_edge = runs ? take(tiles * sizeof(CkPngEdge)) : 0;
         CK_TRY(ck_ensure(ctx, ctx->png_work, at));
         uint8_t* wp = (uint8_t*)ctx->png_work.p;
         CkPngWork wk;
@@ -1701,7 +1769,10 @@ int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
         wk.tile_bits = (uint32_t*)(wp + a_tile_bits); wk.tile_a = (uint32_t*)(wp + a_tile_a); wk.tile_b = (uint32_t*)(wp + a_tile_b);
         wk.band_bits = (uint64_t*)(wp + a_band_bits); wk.band_a = (uint32_t*)(wp + a_band_a); wk.band_b = (uint32_t*)(wp + a_band_b);
         wk.adler = (uint32_t*)(wp + a_adler); wk.codes = (uint16_t*)(wp + a_codes); wk.lens = wp + a_lens; wk.filt = wp + a_filt;
-        CK_TRY(k_png_enc_measure(ctx, (const uint8_t*)d_in, m, g, filter, wk));
+        wk.before = runs ? (uint32_t*)(wp + a_before) : nullptr; wk.after = runs ? (uint32_t*)(wp + a_after) : nullptr;
+        wk.edge = runs ? (CkPngEdge*)(wp + a_edge) : nullptr;
+        CK_TRY(k_png_enc_measure(ctx, (const uint8_t*)d_in, m, g, filter, wk, runs));
+        ctx->png_count_at = a_count; ctx->png_count_frames = m; ctx->png_count_runs = runs; ctx->png_count_bands = g.bands;
         CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ((size_t)m + 1) * 8));
         uint64_t* words = (uint64_t*)ctx->host_pinned2.p;
         CK_HIP(ctx, hipMemcpyAsync(words, wk.head, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1714,7 +1785,7 @@ int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_s
         }
         if (sum != total) return ck_fail(ctx, CK_ERR_STATE, "the streams of a pass: %zu bytes where their sizes give %zu", total, sum);
         CK_TRY(ck_ensure(ctx, ctx->png_pack, total + 16));
-        CK_TRY(k_png_enc_put(ctx, m, g, wk, (uint32_t*)ctx->png_pack.p, total + 16));
+        CK_TRY(k_png_enc_put(ctx, m, g, wk, (uint32_t*)ctx->png_pack.p, total + 16, runs));
         CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
         CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, ctx->png_pack.p, total, hipMemcpyDeviceToHost, ctx->stream));
         CK_TRY(finish(ctx));

@@ -156,6 +156,11 @@ struct ck_ctx {
     size_t jenc_freq_at = 0;         // where the last optimised pass left its counters in jenc_work, and of how many frames
     int jenc_freq_frames = 0;        // (0: the last pass was a standard one) -- ck_jpeg_encode_histograms
     long long jpeg_downloaded = 0;   // bytes the last ck_jpeg_encode / ck_jpeg_entropy_encode_device copied from the device
+    int png_matches = CK_PNG_MATCH_NONE;   // what ck_png_encode makes of repeated bytes (ck_png_set_encode_matches)
+    std::vector<long long> png_tokens;     // ck_png_run_stats: literal and match tokens of the frames of the last ck_png_encode,
+    size_t png_count_at = 0;               // as far as their histograms have been read; those of its last pass are still in
+    int png_count_frames = 0, png_count_runs = 0;   // png_work, at png_count_at, of so many frames, in this mode
+    long long png_count_bands = 0;         // (bands of a frame)
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
@@ -346,18 +351,21 @@ struct CkPngDesc {
 };
 static_assert(sizeof(CkPngDesc) == 32, "a descriptor row is 32 bytes");
 int k_png_unfilter(ck_ctx* ctx, uint8_t* d_rows, const CkPngDesc* d_desc, const uint8_t* d_palettes, int n, int h, int w, uint8_t* d_bgr);
-// Writing, m frames: where the arrays of a pass lie in HBM -- per band (count, lens, codes: CK_PNG_SYM_PITCH each; band_off),
-// per tile, per frame (out_off: m + 1; head: the bytes of all streams, then the bytes of each)
+// Writing, m frames: where the arrays of a pass lie in HBM -- per band (count, lens, codes: ck_png_pitch(runs) each; band_off),
+// per tile (edge, before, after: the runs mode only, else NULL), per frame (out_off: m + 1; head: the bytes of all streams,
+// then the bytes of each)
 struct CkPngWork {
     uint8_t *filt, *lens;
     uint16_t* codes;
     uint32_t *count, *tile_bits, *tile_a, *tile_b, *band_a, *band_b, *adler;
     uint64_t *tile_off, *band_bits, *band_off, *frame_bits, *out_off, *head;      // tile_off: from the start of the band's block
+    CkPngEdge* edge;
+    uint32_t *before, *after;
 };
-// filter, count, build, size, scan: fills all of the above
-int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk);
+// filter, (edges, join,) count, build, size, scan: fills all of the above.  runs: 0 literals only, 1 the runs mode
+int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk, int runs);
 // the zlib streams into d_pack (pack_bytes, zeroed here: head[0] and a dword to spare), frame f at out_off[f]
-int k_png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes);
+int k_png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes, int runs);
 // overlays (k_overlay.hip): n_work non-empty bins of the plan of ck_overlay.cpp, drawn in place on images of h x w x c
 int k_overlay(ck_ctx* ctx, uint8_t* d_img, int h, int w, int c, const int32_t* d_work, int n_work, const int32_t* d_refs,
               const int32_t* d_recs, const uint8_t* d_text);

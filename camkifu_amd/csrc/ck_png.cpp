@@ -424,14 +424,40 @@ size_t ck_png_bound(int h, int w)
     return CK_PNG_CONTAINER + (size_t)ck_png_zlib_bytes(bits) + 16;
 }
 
-int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len, char* msg)
+namespace {
+
+// where the run of every position of a tile starts and ends, from the tile's start (s may be negative, e beyond L)
+void tile_runs(const uint8_t* p, int L, uint32_t before, uint32_t after, int* s, int* e)
+{
+    for (int i = 0; i < L; i++) s[i] = i == 0 ? -(int)before : p[i] == p[i - 1] ? s[i - 1] : i;
+    for (int i = L - 1; i >= 0; i--) e[i] = i == L - 1 ? L + (int)after : p[i + 1] == p[i] ? e[i + 1] : i + 1;
+}
+
+template <int NS>
+void build_band(const uint32_t* count, uint8_t* len, uint16_t* code)
+{
+    uint32_t work[NS];
+    uint16_t order[NS];
+    int m = 0;
+    for (int s = 0; s < NS; s++)
+        if (count[s]) { order[ck_png_rank<NS>(count, s)] = (uint16_t)s; m++; }
+    ck_png_lengths<NS>(count, order, m, work, len, code);
+}
+
+}  // namespace
+
+int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len, char* msg, int runs)
 {
     const CkPngGeom g = ck_png_geom(h, w);
-    std::vector<uint8_t> filt((size_t)g.fbytes), lens((size_t)g.bands * CK_PNG_SYM_PITCH), z;
-    std::vector<uint16_t> codes((size_t)g.bands * CK_PNG_SYM_PITCH);
+    const int PITCH = ck_png_pitch(runs);
+    std::vector<uint8_t> filt((size_t)g.fbytes), lens((size_t)g.bands * PITCH), z;
+    std::vector<uint16_t> codes((size_t)g.bands * PITCH);
     std::vector<uint32_t> tile_bits((size_t)g.tiles), tile_a((size_t)g.tiles), tile_b((size_t)g.tiles);
     std::vector<uint64_t> tile_off((size_t)g.tiles), band_off((size_t)g.bands), band_bits((size_t)g.bands);
     std::vector<uint32_t> band_a((size_t)g.bands), band_b((size_t)g.bands);
+    std::vector<CkPngEdge> edge(runs ? (size_t)g.tiles : 0);
+    std::vector<uint32_t> before(edge.size()), after(edge.size());
+    int rs[CK_PNG_TILE_BYTES], re[CK_PNG_TILE_BYTES];
     for (int f = 0; f < n; f++) {
         const uint8_t* img = bgr + (size_t)f * h * w * 3;
         // filter
@@ -450,28 +476,58 @@ int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uin
             row[0] = (uint8_t)ft;
             for (int64_t i = 0; i < 3 * (int64_t)w; i++) row[1 + i] = ck_png_residual(img, w, y, i, ft);
         }
+        // edges, join (the runs mode)
+        if (runs)
+            for (int64_t band = 0; band < g.bands; band++) {
+                const size_t k = (size_t)(band * g.band_tiles);
+                for (int64_t t = 0; t < g.band_tiles; t++) edge[k + t] = ck_png_edge(filt.data() + ck_png_tile_at(g, band, t), ck_png_tile_len(g, band, t));
+                ck_png_join_band(g, band, edge.data() + k, before.data() + k, after.data() + k);
+            }
         // count, build
         for (int64_t band = 0; band < g.bands; band++) {
-            uint32_t count[CK_PNG_SYMS], work[CK_PNG_SYMS];
-            uint16_t order[CK_PNG_SYMS];
+            uint32_t count[CK_PNG_RUN_SYMS];
             memset(count, 0, sizeof count);
             const uint8_t* p = filt.data() + ck_png_tile_at(g, band, 0);
-            for (int64_t i = 0, e = ck_png_band_bytes(g, band); i < e; i++) count[p[i]]++;
+            if (!runs) {
+                for (int64_t i = 0, e = ck_png_band_bytes(g, band); i < e; i++) count[p[i]]++;
+            } else {
+                for (int64_t t = 0; t < g.band_tiles; t++) {
+                    const size_t k = (size_t)(band * g.band_tiles + t);
+                    const uint8_t* q = p + t * CK_PNG_TILE_BYTES;
+                    const int L = ck_png_tile_len(g, band, t);
+                    tile_runs(q, L, before[k], after[k], rs, re);
+                    for (int i = 0; i < L; i++) {
+                        int tb;
+                        uint32_t tail;
+                        const int sym = ck_png_token(q[i], i - rs[i] - 1, re[i] - rs[i] - 1, &tb, &tail);
+                        if (sym >= 0) count[sym]++;
+                    }
+                }
+            }
             count[256] = 1;
-            int m = 0;
-            for (int s = 0; s < CK_PNG_SYMS; s++)
-                if (count[s]) { order[ck_png_rank(count, s)] = (uint16_t)s; m++; }
-            ck_png_lengths(count, order, m, work, lens.data() + band * CK_PNG_SYM_PITCH, codes.data() + band * CK_PNG_SYM_PITCH);
+            if (runs) build_band<CK_PNG_RUN_SYMS>(count, lens.data() + band * PITCH, codes.data() + band * PITCH);
+            else build_band<CK_PNG_SYMS>(count, lens.data() + band * PITCH, codes.data() + band * PITCH);
         }
         // size
         for (int64_t band = 0; band < g.bands; band++)
             for (int64_t t = 0; t < g.band_tiles; t++) {
                 const uint8_t* p = filt.data() + ck_png_tile_at(g, band, t);
-                const uint8_t* bl = lens.data() + band * CK_PNG_SYM_PITCH;
+                const uint8_t* bl = lens.data() + band * PITCH;
                 const int L = ck_png_tile_len(g, band, t);
-                uint32_t bits = 0, a = 0, b = 0;
-                for (int i = 0; i < L; i++) { bits += bl[p[i]]; a += p[i]; b += (uint32_t)(L - i) * p[i]; }
                 const size_t k = (size_t)(band * g.band_tiles + t);
+                uint32_t bits = 0, a = 0, b = 0;
+                for (int i = 0; i < L; i++) { a += p[i]; b += (uint32_t)(L - i) * p[i]; }
+                if (!runs) {
+                    for (int i = 0; i < L; i++) bits += bl[p[i]];
+                } else {
+                    tile_runs(p, L, before[k], after[k], rs, re);
+                    for (int i = 0; i < L; i++) {
+                        int tb;
+                        uint32_t tail;
+                        const int sym = ck_png_token(p[i], i - rs[i] - 1, re[i] - rs[i] - 1, &tb, &tail);
+                        if (sym >= 0) bits += (uint32_t)(bl[sym] + tb);
+                    }
+                }
                 tile_bits[k] = bits; tile_a[k] = a; tile_b[k] = b;
             }
         // scan
@@ -479,8 +535,8 @@ int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uin
         uint32_t adler = 0;
         for (int64_t band = 0; band < g.bands; band++) {
             const size_t k = (size_t)(band * g.band_tiles);
-            ck_png_scan_band(g, band, tile_bits.data() + k, tile_a.data() + k, tile_b.data() + k, lens[(size_t)band * CK_PNG_SYM_PITCH + 256],
-                             tile_off.data() + k, &band_bits[(size_t)band], &band_a[(size_t)band], &band_b[(size_t)band]);
+            ck_png_scan_band(g, band, tile_bits.data() + k, tile_a.data() + k, tile_b.data() + k, lens[(size_t)band * PITCH + 256],
+                             tile_off.data() + k, &band_bits[(size_t)band], &band_a[(size_t)band], &band_b[(size_t)band], ck_png_hdr_bits(runs));
         }
         ck_png_scan_frame(g, band_bits.data(), band_a.data(), band_b.data(), band_off.data(), &frame_bits, &adler);
         const size_t zlen = (size_t)ck_png_zlib_bytes(frame_bits);
@@ -492,19 +548,34 @@ int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uin
         z.assign(zlen + 8, 0);
         z[0] = 0x78; z[1] = 0x01;
         for (int64_t band = 0; band < g.bands; band++) {
-            const uint8_t* bl = lens.data() + band * CK_PNG_SYM_PITCH;
-            const uint16_t* bc = codes.data() + band * CK_PNG_SYM_PITCH;
-            for (int i = 0; i < CK_PNG_HDR_FIELDS; i++) {
+            const uint8_t* bl = lens.data() + band * PITCH;
+            const uint16_t* bc = codes.data() + band * PITCH;
+            for (int i = 0; i < ck_png_hdr_fields(runs); i++) {
                 uint32_t v;
                 int nb, off;
-                ck_png_hdr_field(i, bl, band == g.bands - 1, &v, &nb, &off);
+                if (runs) ck_png_run_hdr_field(i, bl, band == g.bands - 1, &v, &nb, &off);
+                else ck_png_hdr_field(i, bl, band == g.bands - 1, &v, &nb, &off);
                 ck_png_or_bits(z.data(), 16 + band_off[(size_t)band] + (uint64_t)off, v, nb);
             }
             uint64_t pos = 0;
             for (int64_t t = 0; t < g.band_tiles; t++) {
                 const uint8_t* p = filt.data() + ck_png_tile_at(g, band, t);
-                pos = 16 + band_off[(size_t)band] + tile_off[(size_t)(band * g.band_tiles + t)];
-                for (int i = 0, L = ck_png_tile_len(g, band, t); i < L; i++) { ck_png_or_bits(z.data(), pos, bc[p[i]], bl[p[i]]); pos += bl[p[i]]; }
+                const size_t k = (size_t)(band * g.band_tiles + t);
+                const int L = ck_png_tile_len(g, band, t);
+                pos = 16 + band_off[(size_t)band] + tile_off[k];
+                if (!runs) {
+                    for (int i = 0; i < L; i++) { ck_png_or_bits(z.data(), pos, bc[p[i]], bl[p[i]]); pos += bl[p[i]]; }
+                    continue;
+                }
+                tile_runs(p, L, before[k], after[k], rs, re);
+                for (int i = 0; i < L; i++) {
+                    int tb;
+                    uint32_t tail;
+                    const int sym = ck_png_token(p[i], i - rs[i] - 1, re[i] - rs[i] - 1, &tb, &tail);
+                    if (sym < 0) continue;
+                    ck_png_or_bits(z.data(), pos, bc[sym], bl[sym]); pos += bl[sym];
+                    ck_png_or_bits(z.data(), pos, tail, tb); pos += (uint64_t)tb;
+                }
             }
             ck_png_or_bits(z.data(), pos, bc[256], bl[256]);
         }

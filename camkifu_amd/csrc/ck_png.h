@@ -44,5 +44,6 @@ size_t ck_png_wrap(const uint8_t* z, size_t zlen, int h, int w, uint8_t* out);
 // the most bytes a file of an h x w frame can have: every literal 15 bits
 size_t ck_png_bound(int h, int w);
 // n BGR frames through the steps of ck_png_stage.h on the host -> files at out + f * stride, their sizes in len.
-// filter: 0 .. 4 forces one type, -1 chooses per row.
-int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len, char* msg);
+// filter: 0 .. 4 forces one type, -1 chooses per row.  runs: 0 literals only, 1 the runs mode (runs of equal bytes inside a
+// band as matches of distance 1); ck_png_bound covers both.
+int ck_png_stage_encode(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len, char* msg, int runs = 0);

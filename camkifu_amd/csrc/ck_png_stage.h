@@ -22,6 +22,22 @@
 // The block header: BFINAL, BTYPE = 2, HLIT = 0 (257 codes), HDIST = 0 (one distance code), HCLEN = 15 (all 19 code-length
 // codes); the code-length alphabet gives its symbols 0 .. 15 four bits each and 16 .. 18 none, a complete set, so a code
 // length l is sent as the four bits of l; one distance code of length 0 follows.  CK_PNG_HDR_BITS bits in all.
+//
+// The runs mode (CK_PNG_MATCH_RUNS; `RUNS` below, a compile-time parameter of every step).  A RUN is a maximal interval
+// [s, e) of equal bytes inside one band: runs cross rows and tiles, never a band's edge.  Byte s is a literal; the
+// r = e - s - 1 bytes behind it are r = 258 k + t: k matches of length 258 and distance 1, then one match of length t
+// where t >= 3, or t literals where t is 1 or 2.  So every position is a literal, the head of a match or covered by one
+// (no token), by o = i - s - 1 and r alone: ck_png_run_role.  A token belongs to the tile that holds its first byte.
+//   edges   a tile alone: its first and last byte and the lengths of the runs that touch its first and last position,
+//           capped at the tile.
+//   join    a band alone, its tiles in order (ck_png_join_band): how many bytes just before a tile equal its first byte,
+//           how many just behind it equal its last.  With these and the starts of runs inside the tile every position
+//           knows s and e.
+//   count   over tokens: literals, the end-of-block symbol once, the length symbols 257 .. 285.
+//   build   over CK_PNG_RUN_SYMS symbols; size: the bits of the tokens that start in the tile; scan: as above.
+//   put     a match is the length symbol's code, its extra bits (LSB first), and the distance code, one bit 0.
+// Its block header: HLIT = 29 (286 codes), HDIST = 1: two distance codes of length 1, a complete set in which distance 1 is
+// the code 0 (a single code of length 1 is the incomplete set zlib never writes).  CK_PNG_RUN_HDR_BITS bits in all.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -42,6 +58,17 @@ constexpr int CK_PNG_MAX_BITS = 15;
 constexpr int CK_PNG_HDR_FIELDS = 3 + CK_PNG_SYMS + 1;
 constexpr int CK_PNG_HDR_BITS = 17 + 19 * 3 + CK_PNG_SYMS * 4 + 4;
 constexpr uint32_t CK_PNG_ADLER = 65521;
+// the runs mode: 29 length symbols behind the end-of-block symbol, arrays of a pitch of their own, two distance codes
+constexpr int CK_PNG_RUN_SYMS = 286;
+constexpr int CK_PNG_RUN_PITCH = 288;
+constexpr int CK_PNG_RUN_HDR_FIELDS = 3 + CK_PNG_RUN_SYMS + 2;
+constexpr int CK_PNG_RUN_HDR_BITS = 17 + 19 * 3 + CK_PNG_RUN_SYMS * 4 + 2 * 4;
+constexpr int CK_PNG_MAX_MATCH = 258;
+// what the arrays and the header of a mode need (runs: 0 the literal-only mode, 1 the runs mode)
+CK_HD constexpr int ck_png_syms(int runs) { return runs ? CK_PNG_RUN_SYMS : CK_PNG_SYMS; }
+CK_HD constexpr int ck_png_pitch(int runs) { return runs ? CK_PNG_RUN_PITCH : CK_PNG_SYM_PITCH; }
+CK_HD constexpr int ck_png_hdr_fields(int runs) { return runs ? CK_PNG_RUN_HDR_FIELDS : CK_PNG_HDR_FIELDS; }
+CK_HD constexpr int ck_png_hdr_bits(int runs) { return runs ? CK_PNG_RUN_HDR_BITS : CK_PNG_HDR_BITS; }
 
 struct CkPngGeom {
     int32_t h, w;
@@ -116,10 +143,11 @@ CK_HD inline int ck_png_choose(const uint32_t* sum)
 
 // ---- build ----
 // the place of symbol s among the symbols that occur, in ascending (count, symbol) order; symbols: how many occur
+template <int NS = CK_PNG_SYMS>
 CK_HD inline int ck_png_rank(const uint32_t* count, int s)
 {
     int r = 0;
-    for (int j = 0; j < CK_PNG_SYMS; j++)
+    for (int j = 0; j < NS; j++)
         r += count[j] != 0 && (count[j] < count[s] || (count[j] == count[s] && j < s));
     return r;
 }
@@ -129,15 +157,16 @@ CK_HD inline uint32_t ck_png_reverse(uint32_t code, int bits)
     for (int i = 0; i < bits; i++) r |= ((code >> i) & 1u) << (bits - 1 - i);
     return r;
 }
-// order[0 .. m): the symbols that occur, by ck_png_rank; A: m words of work.  -> len[CK_PNG_SYMS] (0: the symbol does not
+// order[0 .. m): the symbols that occur, by ck_png_rank; A: m words of work.  -> len[NS] (0: the symbol does not
 // occur) and the codes, reversed.  The lengths are those of a Huffman tree over the counts (Moffat and Katajainen's in-place
 // computation over the sorted counts); where the tree is deeper than 15, codes above 15 bits are cut to 15 and, for every
 // unit of 2^-15 the Kraft sum is above 1 then, one 15-bit code is taken away and the longest shorter code is split in two
 // one bit longer -- the sum falls by exactly that unit, the number of codes stays -- and the lengths are handed out again,
 // the longest to the rarest.  m = 1: one code of one bit (the set zlib accepts although it is incomplete).
+template <int NS = CK_PNG_SYMS>
 CK_HD inline void ck_png_lengths(const uint32_t* count, const uint16_t* order, int m, uint32_t* A, uint8_t* len, uint16_t* code)
 {
-    for (int s = 0; s < CK_PNG_SYMS; s++) { len[s] = 0; code[s] = 0; }
+    for (int s = 0; s < NS; s++) { len[s] = 0; code[s] = 0; }
     if (m <= 0) return;
     uint32_t bl[CK_PNG_MAX_BITS + 2];
     for (int l = 0; l <= CK_PNG_MAX_BITS + 1; l++) bl[l] = 0;
@@ -182,8 +211,97 @@ CK_HD inline void ck_png_lengths(const uint32_t* count, const uint16_t* order, i
     uint32_t next_code[CK_PNG_MAX_BITS + 2], c = 0;
     bl[0] = 0;
     for (int l = 1; l <= CK_PNG_MAX_BITS; l++) { c = (c + bl[l - 1]) << 1; next_code[l] = c; }
-    for (int s = 0; s < CK_PNG_SYMS; s++)
+    for (int s = 0; s < NS; s++)
         if (len[s]) code[s] = (uint16_t)ck_png_reverse(next_code[len[s]]++, len[s]);
+}
+
+// ---- runs ----
+enum { CK_PNG_ROLE_LITERAL = 0, CK_PNG_ROLE_HEAD = 1, CK_PNG_ROLE_COVERED = 2 };
+// position i of the run [s, e): o = i - s - 1 (-1: the run's first byte), r = e - s - 1 -> its role, and for the head of a
+// match the match's length
+CK_HD inline int ck_png_run_role(int o, int r, int* len)
+{
+    *len = 0;
+    if (o < 0) return CK_PNG_ROLE_LITERAL;
+    const int full = r - r % CK_PNG_MAX_MATCH, t = r - full;
+    if (o < full) {
+        if (o % CK_PNG_MAX_MATCH) return CK_PNG_ROLE_COVERED;
+        *len = CK_PNG_MAX_MATCH;
+        return CK_PNG_ROLE_HEAD;
+    }
+    if (t < 3) return CK_PNG_ROLE_LITERAL;
+    if (o > full) return CK_PNG_ROLE_COVERED;
+    *len = t;
+    return CK_PNG_ROLE_HEAD;
+}
+// a match length 3 .. 258 -> its symbol 257 .. 285, the number of its extra bits and their value (RFC 1951, 3.2.5): eight
+// symbols without extra bits, then four symbols for every number of extra bits 1 .. 5, and 258 on its own
+CK_HD inline int ck_png_len_symbol(int len, int* extra_bits, uint32_t* extra)
+{
+    *extra_bits = 0; *extra = 0;
+    if (len == CK_PNG_MAX_MATCH) return 285;
+    const int x = len - 3;
+    if (x < 8) return 257 + x;
+    int eb = 1;
+    while (x >> (eb + 3)) eb++;
+    *extra_bits = eb;
+    *extra = (uint32_t)x & ((1u << eb) - 1);
+    return 261 + 4 * eb + ((x >> eb) & 3);
+}
+// the token that starts at a position: the byte x there, o and r as for ck_png_run_role -> its symbol (-1: covered, no
+// token), and what follows the symbol's code: `tail_bits` bits of value `tail` (a match's extra bits, then the distance code 0)
+CK_HD inline int ck_png_token(uint32_t x, int o, int r, int* tail_bits, uint32_t* tail)
+{
+    int len;
+    *tail_bits = 0; *tail = 0;
+    const int role = ck_png_run_role(o, r, &len);
+    if (role == CK_PNG_ROLE_COVERED) return -1;
+    if (role == CK_PNG_ROLE_LITERAL) return (int)x;
+    int eb;
+    const int sym = ck_png_len_symbol(len, &eb, tail);
+    *tail_bits = eb + 1;
+    return sym;
+}
+// what the edges step gives for a tile
+struct CkPngEdge {
+    uint8_t first, last;                                     // its first and last byte
+    uint16_t head, tail;                                     // bytes at its start equal to the first, at its end equal to the last
+};
+CK_HD inline CkPngEdge ck_png_edge(const uint8_t* p, int L)
+{
+    CkPngEdge e;
+    e.first = e.last = 0; e.head = e.tail = 0;
+    if (L <= 0) return e;
+    e.first = p[0]; e.last = p[L - 1];
+    int n = 1;
+    while (n < L && p[n] == e.first) n++;
+    e.head = (uint16_t)n;
+    n = 1;
+    while (n < L && p[L - 1 - n] == e.last) n++;
+    e.tail = (uint16_t)n;
+    return e;
+}
+// a band's tiles in order -> before[t]: how many bytes just before tile t equal its first byte, after[t]: how many just
+// behind it equal its last byte (both inside the band; 0 for an empty tile)
+CK_HD inline void ck_png_join_band(const CkPngGeom& g, int64_t band, const CkPngEdge* edge, uint32_t* before, uint32_t* after)
+{
+    uint32_t run = 0;                                        // the bytes at the end of the tiles so far that equal `v`
+    int v = -1;
+    for (int64_t t = 0; t < g.band_tiles; t++) {
+        const int L = ck_png_tile_len(g, band, t);
+        before[t] = L > 0 && v == edge[t].first ? run : 0;
+        if (L <= 0) continue;
+        if (edge[t].tail == L && v == edge[t].last) run += (uint32_t)L;
+        else { v = edge[t].last; run = edge[t].tail; }
+    }
+    run = 0; v = -1;
+    for (int64_t t = g.band_tiles - 1; t >= 0; t--) {
+        const int L = ck_png_tile_len(g, band, t);
+        after[t] = L > 0 && v == edge[t].last ? run : 0;
+        if (L <= 0) continue;
+        if (edge[t].head == L && v == edge[t].first) run += (uint32_t)L;
+        else { v = edge[t].first; run = edge[t].head; }
+    }
 }
 
 // ---- size, scan ----
@@ -191,9 +309,10 @@ CK_HD inline void ck_png_lengths(const uint32_t* count, const uint16_t* order, i
 // tile starts, in bits from the start of the band's block (its header comes first), the bits of the whole block, and the
 // band's Adler pair: a the sum of its bytes, b the sum of (bytes of the band - i) x_i, both mod 65521
 CK_HD inline void ck_png_scan_band(const CkPngGeom& g, int64_t band, const uint32_t* tile_bits, const uint32_t* tile_a, const uint32_t* tile_b,
-                                   int eob_len, uint64_t* tile_off, uint64_t* band_bits, uint32_t* band_a, uint32_t* band_b)
+                                   int eob_len, uint64_t* tile_off, uint64_t* band_bits, uint32_t* band_a, uint32_t* band_b,
+                                   int hdr_bits = CK_PNG_HDR_BITS)
 {
-    uint64_t pos = CK_PNG_HDR_BITS, A = 0, B = 0;
+    uint64_t pos = (uint64_t)hdr_bits, A = 0, B = 0;
     for (int64_t t = 0; t < g.band_tiles; t++) {
         tile_off[t] = pos;
         pos += tile_bits[t];
@@ -240,6 +359,19 @@ CK_HD inline void ck_png_hdr_field(int i, const uint8_t* len, int bfinal, uint32
         *value = ck_png_reverse(len[i - 3], 4); *nbits = 4; *offset = 74 + 4 * (i - 3);
     } else {                                                 // the one distance code: length 0
         *value = 0; *nbits = 4; *offset = 74 + 4 * CK_PNG_SYMS;
+    }
+}
+// the same for the runs mode's header, field i (0 .. CK_PNG_RUN_HDR_FIELDS); len: CK_PNG_RUN_SYMS code lengths
+CK_HD inline void ck_png_run_hdr_field(int i, const uint8_t* len, int bfinal, uint32_t* value, int* nbits, int* offset)
+{
+    if (i == 0) {                                            // BFINAL, BTYPE 2, HLIT 29, HDIST 1, HCLEN 15
+        *value = (uint32_t)(bfinal & 1) | 2u << 1 | 29u << 3 | 1u << 8 | 15u << 13; *nbits = 17; *offset = 0;
+    } else if (i < 3) {                                      // the code-length code is the same
+        ck_png_hdr_field(i, len, bfinal, value, nbits, offset);
+    } else if (i < 3 + CK_PNG_RUN_SYMS) {
+        *value = ck_png_reverse(len[i - 3], 4); *nbits = 4; *offset = 74 + 4 * (i - 3);
+    } else {                                                 // two distance codes of length 1: distance 1 is the code 0
+        *value = ck_png_reverse(1, 4); *nbits = 4; *offset = 74 + 4 * (i - 3);
     }
 }
 // host sink: OR `nbits` (up to 32) bits of v into zeroed bytes at bit `pos`

@@ -11,7 +11,10 @@
 //
 // Writing: the steps of ck_png_stage.h, a launch each -- filter (a workgroup per row), count (per band), build (per band),
 // size (per tile), scan (per band, then per frame; then the frames' places), put (the bands' headers; the tiles' literals, assembled in
-// LDS and written out whole dwords, the two a tile shares with its neighbours by OR).
+// LDS and written out whole dwords, the two a tile shares with its neighbours by OR).  The mode (literals only, or runs of
+// equal bytes as matches of distance 1) is a compile-time parameter of count, build, size, scan and put; the runs mode has
+// two launches more behind filter -- edges (per tile) and join (per band) -- from which every tile knows how far the runs
+// at its two ends reach beyond it.
 #include "ck_common.h"
 
 constexpr int PNG_TB = 256;
@@ -179,41 +182,166 @@ __global__ __launch_bounds__(PNG_TB) void png_filter_kernel(const uint8_t* __res
     for (long long i = threadIdx.x; i < nb; i += PNG_TB) dst[1 + i] = ck_png_residual(img, g.w, y, i, ft);
 }
 
-__global__ __launch_bounds__(PNG_TB) void png_count_kernel(const uint8_t* __restrict__ filt, CkPngGeom g, uint32_t* __restrict__ count)
+// ---- the runs mode: where the runs of equal bytes start and end ----
+// edges, a tile alone: lane i looks at its four bytes
+__global__ __launch_bounds__(PNG_TB) void png_edges_kernel(const uint8_t* __restrict__ filt, CkPngGeom g, CkPngEdge* __restrict__ edge)
 {
-    __shared__ uint32_t hist[256];
+    __shared__ int lo, hi;                                       // the first position that differs from the first byte, the last that differs from the last
+    const long long f = blockIdx.x / g.tiles, k = blockIdx.x % g.tiles, band = k / g.band_tiles, t = k % g.band_tiles;
+    const int L = ck_png_tile_len(g, band, t);
+    if (threadIdx.x == 0) { lo = L; hi = -1; }
+    __syncthreads();
+    const uint8_t* p = filt + (size_t)f * g.fbytes + ck_png_tile_at(g, band, t);
+    uint32_t first = 0, last = 0;
+    if (L > 0) {
+        first = p[0]; last = p[L - 1];
+        int mn = L, mx = -1;
+        for (int j = 0; j < 4; j++) {
+            const int i = 4 * threadIdx.x + j;
+            if (i < L) {
+                const uint32_t x = p[i];
+                if (x != first && i < mn) mn = i;
+                if (x != last) mx = i;
+            }
+        }
+        if (mn < L) atomicMin(&lo, mn);
+        if (mx >= 0) atomicMax(&hi, mx);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                      // what ck_png_edge gives
+        CkPngEdge e;
+        e.first = (uint8_t)first; e.last = (uint8_t)last;
+        e.head = (uint16_t)(L > 0 ? lo : 0); e.tail = (uint16_t)(L > 0 ? L - 1 - hi : 0);
+        edge[blockIdx.x] = e;
+    }
+}
+
+// join, a lane per band
+__global__ __launch_bounds__(64) void png_join_kernel(CkPngGeom g, CkPngWork wk, long long n_bands)
+{
+    const long long gb = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (gb >= n_bands) return;
+    const size_t k = (size_t)gb * g.band_tiles;
+    ck_png_join_band(g, gb % g.bands, wk.edge + k, wk.before + k, wk.after + k);
+}
+
+// The runs of a lane's four positions 4 lane + j of a tile of L bytes at p: x[j] the bytes, s[j] and e[j] where the run of
+// each starts and ends, counted from the tile's start (s down to -before, e up to L + after).  A position starts a run
+// inside the tile where it is the tile's first or differs from the byte before it; the last start at or before a position
+// and the first start behind it come from two scans over the lanes (lo, hi: PNG_TB words of LDS each).  Every lane of the
+// workgroup calls it, with L > 0.
+__device__ __forceinline__ void png_tile_runs(const uint8_t* __restrict__ p, int L, int before, int after, int* lo, int* hi,
+                                              uint32_t (&x)[4], int (&s)[4], int (&e)[4])
+{
+    constexpr int NONE = 1 << 30;
+    const int lane = threadIdx.x, i0 = 4 * lane;
+    uint32_t prev = i0 > 0 && i0 <= L ? p[i0 - 1] : 0;
+    bool st[4];
+    int last = -1, first = NONE;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int i = i0 + j;
+        x[j] = 0; st[j] = false;
+        if (i < L) {
+            x[j] = p[i];
+            st[j] = i == 0 || x[j] != prev;
+            prev = x[j];
+            if (st[j]) { last = i; if (first == NONE) first = i; }
+        }
+    }
+    __syncthreads();                                             // (the arrays may still be read by a call before this one)
+    lo[lane] = last; hi[lane] = first;
+    __syncthreads();
+    for (int d = 1; d < PNG_TB; d <<= 1) {
+        const int a = lane >= d ? lo[lane - d] : -1, b = lane + d < PNG_TB ? hi[lane + d] : NONE;
+        __syncthreads();
+        if (a > lo[lane]) lo[lane] = a;
+        if (b < hi[lane]) hi[lane] = b;
+        __syncthreads();
+    }
+    int cur = lane > 0 ? lo[lane - 1] : -1, nxt = lane + 1 < PNG_TB ? hi[lane + 1] : NONE;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (st[j]) cur = i0 + j;
+        s[j] = cur <= 0 ? -before : cur;
+    }
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        e[j] = nxt == NONE ? L + after : nxt;
+        if (st[j]) nxt = i0 + j;
+    }
+}
+
+// count.  RUNS: over the tokens of the band's tiles, tile after tile
+template <int RUNS>
+__global__ __launch_bounds__(PNG_TB) void png_count_kernel(const uint8_t* __restrict__ filt, CkPngGeom g, uint32_t* __restrict__ count,
+                                                           const uint32_t* __restrict__ before, const uint32_t* __restrict__ after)
+{
+    __shared__ uint32_t hist[RUNS ? CK_PNG_RUN_SYMS : 256];
     const long long f = blockIdx.x / g.bands, band = blockIdx.x % g.bands;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
     const uint8_t* p = filt + (size_t)f * g.fbytes + ck_png_tile_at(g, band, 0);
-    for (long long i = threadIdx.x, e = ck_png_band_bytes(g, band); i < e; i += PNG_TB) atomicAdd(&hist[p[i]], 1u);
-    __syncthreads();
-    uint32_t* out = count + (size_t)blockIdx.x * CK_PNG_SYM_PITCH;
-    out[threadIdx.x] = hist[threadIdx.x];
-    if (threadIdx.x == 0) out[256] = 1;
+    uint32_t* out = count + (size_t)blockIdx.x * ck_png_pitch(RUNS);
+    if constexpr (!RUNS) {
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (long long i = threadIdx.x, e = ck_png_band_bytes(g, band); i < e; i += PNG_TB) atomicAdd(&hist[p[i]], 1u);
+        __syncthreads();
+        out[threadIdx.x] = hist[threadIdx.x];
+        if (threadIdx.x == 0) out[256] = 1;
+    } else {
+        __shared__ int lo[PNG_TB], hi[PNG_TB];
+        for (int i = threadIdx.x; i < CK_PNG_RUN_SYMS; i += PNG_TB) hist[i] = 0;
+        __syncthreads();
+        for (long long t = 0; t < g.band_tiles; t++) {
+            const int L = ck_png_tile_len(g, band, t);
+            if (L == 0) break;
+            const size_t k = (size_t)blockIdx.x * g.band_tiles + t;
+            uint32_t x[4];
+            int s[4], e[4];
+            png_tile_runs(p + t * CK_PNG_TILE_BYTES, L, (int)before[k], (int)after[k], lo, hi, x, s, e);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int i = 4 * threadIdx.x + j;
+                if (i < L) {
+                    int tb;
+                    uint32_t tail;
+                    const int sym = ck_png_token(x[j], i - s[j] - 1, e[j] - s[j] - 1, &tb, &tail);
+                    if (sym >= 0) atomicAdd(&hist[sym], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < CK_PNG_RUN_SYMS; i += PNG_TB) out[i] = i == 256 ? 1u : hist[i];
+    }
 }
 
 constexpr int PNG_BUILD_TB = 320;
-static_assert(PNG_BUILD_TB >= CK_PNG_HDR_FIELDS + 2, "a lane per header field, one for the end-of-block code, one for the zlib wrapper");
+static_assert(PNG_BUILD_TB >= CK_PNG_HDR_FIELDS + 2 && PNG_BUILD_TB >= CK_PNG_RUN_HDR_FIELDS + 2,
+              "a lane per header field, one for the end-of-block code, one for the zlib wrapper");
+template <int RUNS>
 __global__ __launch_bounds__(PNG_BUILD_TB) void png_build_kernel(const uint32_t* __restrict__ count, uint8_t* __restrict__ lens, uint16_t* __restrict__ codes)
 {
-    __shared__ uint32_t cnt[CK_PNG_SYMS], work[CK_PNG_SYMS];
-    __shared__ uint16_t order[CK_PNG_SYMS];
+    constexpr int NS = ck_png_syms(RUNS), PITCH = ck_png_pitch(RUNS);
+    __shared__ uint32_t cnt[NS], work[NS];
+    __shared__ uint16_t order[NS];
     __shared__ int m;
     const int s = threadIdx.x;
     if (s == 0) m = 0;
-    if (s < CK_PNG_SYMS) cnt[s] = count[(size_t)blockIdx.x * CK_PNG_SYM_PITCH + s];
+    if (s < NS) cnt[s] = count[(size_t)blockIdx.x * PITCH + s];
     __syncthreads();
-    if (s < CK_PNG_SYMS && cnt[s]) {
-        order[ck_png_rank(cnt, s)] = (uint16_t)s;
+    if (s < NS && cnt[s]) {
+        order[ck_png_rank<NS>(cnt, s)] = (uint16_t)s;
         atomicAdd(&m, 1);
     }
     __syncthreads();
-    if (s == 0) ck_png_lengths(cnt, order, m, work, lens + (size_t)blockIdx.x * CK_PNG_SYM_PITCH, codes + (size_t)blockIdx.x * CK_PNG_SYM_PITCH);
+    if (s == 0) ck_png_lengths<NS>(cnt, order, m, work, lens + (size_t)blockIdx.x * PITCH, codes + (size_t)blockIdx.x * PITCH);
 }
 
+// size.  RUNS: the bits of the tokens that start in the tile
+template <int RUNS>
 __global__ __launch_bounds__(PNG_TB) void png_size_kernel(const uint8_t* __restrict__ filt, CkPngGeom g, const uint8_t* __restrict__ lens,
-                                                          uint32_t* __restrict__ tile_bits, uint32_t* __restrict__ tile_a, uint32_t* __restrict__ tile_b)
+                                                          uint32_t* __restrict__ tile_bits, uint32_t* __restrict__ tile_a, uint32_t* __restrict__ tile_b,
+                                                          const uint32_t* __restrict__ before, const uint32_t* __restrict__ after)
 {
     __shared__ uint32_t acc[3];
     const long long f = blockIdx.x / g.tiles, k = blockIdx.x % g.tiles, band = k / g.band_tiles, t = k % g.band_tiles;
@@ -221,11 +349,29 @@ __global__ __launch_bounds__(PNG_TB) void png_size_kernel(const uint8_t* __restr
     if (threadIdx.x < 3) acc[threadIdx.x] = 0;
     __syncthreads();
     const uint8_t* p = filt + (size_t)f * g.fbytes + ck_png_tile_at(g, band, t);
-    const uint8_t* bl = lens + (size_t)(f * g.bands + band) * CK_PNG_SYM_PITCH;
+    const uint8_t* bl = lens + (size_t)(f * g.bands + band) * ck_png_pitch(RUNS);
     uint32_t bits = 0, a = 0, b = 0;
-    for (int j = 0; j < 4; j++) {
-        const int i = 4 * threadIdx.x + j;
-        if (i < L) { const uint32_t x = p[i]; bits += bl[x]; a += x; b += (uint32_t)(L - i) * x; }
+    if constexpr (!RUNS) {
+        for (int j = 0; j < 4; j++) {
+            const int i = 4 * threadIdx.x + j;
+            if (i < L) { const uint32_t x = p[i]; bits += bl[x]; a += x; b += (uint32_t)(L - i) * x; }
+        }
+    } else if (L > 0) {
+        __shared__ int lo[PNG_TB], hi[PNG_TB];
+        uint32_t x[4];
+        int s[4], e[4];
+        png_tile_runs(p, L, (int)before[blockIdx.x], (int)after[blockIdx.x], lo, hi, x, s, e);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int i = 4 * threadIdx.x + j;
+            if (i < L) {
+                int tb;
+                uint32_t tail;
+                const int sym = ck_png_token(x[j], i - s[j] - 1, e[j] - s[j] - 1, &tb, &tail);
+                if (sym >= 0) bits += (uint32_t)(bl[sym] + tb);
+                a += x[j]; b += (uint32_t)(L - i) * x[j];
+            }
+        }
     }
     atomicAdd(&acc[0], bits); atomicAdd(&acc[1], a); atomicAdd(&acc[2], b);
     __syncthreads();
@@ -233,13 +379,14 @@ __global__ __launch_bounds__(PNG_TB) void png_size_kernel(const uint8_t* __restr
 }
 
 // a lane per band, then a lane per frame over its bands
+template <int RUNS>
 __global__ __launch_bounds__(64) void png_scan_band_kernel(CkPngGeom g, CkPngWork wk, long long n_bands)
 {
     const long long gb = (long long)blockIdx.x * 64 + threadIdx.x;
     if (gb >= n_bands) return;
     const size_t k = (size_t)gb * g.band_tiles;
-    ck_png_scan_band(g, gb % g.bands, wk.tile_bits + k, wk.tile_a + k, wk.tile_b + k, wk.lens[(size_t)gb * CK_PNG_SYM_PITCH + 256], wk.tile_off + k,
-                     wk.band_bits + gb, wk.band_a + gb, wk.band_b + gb);
+    ck_png_scan_band(g, gb % g.bands, wk.tile_bits + k, wk.tile_a + k, wk.tile_b + k, wk.lens[(size_t)gb * ck_png_pitch(RUNS) + 256], wk.tile_off + k,
+                     wk.band_bits + gb, wk.band_a + gb, wk.band_b + gb, ck_png_hdr_bits(RUNS));
 }
 
 __global__ void png_scan_kernel(CkPngGeom g, CkPngWork wk)
@@ -270,21 +417,24 @@ __device__ __forceinline__ void png_or_bits(uint32_t* buf, uint64_t pos, uint32_
     if (s + nbits > 32) atomicOr(&buf[(pos >> 5) + 1], v >> (32 - s));
 }
 
+template <int RUNS>
 __global__ __launch_bounds__(PNG_BUILD_TB) void png_put_header_kernel(CkPngGeom g, CkPngWork wk, uint32_t* __restrict__ pack)
 {
+    constexpr int FIELDS = ck_png_hdr_fields(RUNS), PITCH = ck_png_pitch(RUNS);
     const size_t gb = blockIdx.x, f = gb / g.bands, band = gb % g.bands;
-    const uint8_t* bl = wk.lens + gb * CK_PNG_SYM_PITCH;
+    const uint8_t* bl = wk.lens + gb * PITCH;
     const uint64_t frame = wk.out_off[f] * 8;
     const int i = threadIdx.x;
-    if (i < CK_PNG_HDR_FIELDS) {
+    if (i < FIELDS) {
         uint32_t v;
         int nb, off;
-        ck_png_hdr_field(i, bl, band == (size_t)g.bands - 1, &v, &nb, &off);
+        if constexpr (RUNS) ck_png_run_hdr_field(i, bl, band == (size_t)g.bands - 1, &v, &nb, &off);
+        else ck_png_hdr_field(i, bl, band == (size_t)g.bands - 1, &v, &nb, &off);
         png_or_bits(pack, frame + 16 + wk.band_off[gb] + (uint64_t)off, v, nb);
-    } else if (i == CK_PNG_HDR_FIELDS) {                         // the end-of-block code, behind the band's last tile
+    } else if (i == FIELDS) {                                    // the end-of-block code, behind the band's last tile
         const size_t last = f * g.tiles + band * g.band_tiles + g.band_tiles - 1;
-        png_or_bits(pack, frame + 16 + wk.band_off[gb] + wk.tile_off[last] + wk.tile_bits[last], wk.codes[gb * CK_PNG_SYM_PITCH + 256], bl[256]);
-    } else if (i == CK_PNG_HDR_FIELDS + 1 && band == 0) {        // the zlib wrapper: 78 01 in front, the Adler-32 behind, high byte first
+        png_or_bits(pack, frame + 16 + wk.band_off[gb] + wk.tile_off[last] + wk.tile_bits[last], wk.codes[gb * PITCH + 256], bl[256]);
+    } else if (i == FIELDS + 1 && band == 0) {                   // the zlib wrapper: 78 01 in front, the Adler-32 behind, high byte first
         png_or_bits(pack, frame, 0x0178u, 16);
         const uint32_t ad = wk.adler[f];
         const uint32_t sw = ad >> 24 | (ad >> 8 & 0xff00u) | (ad << 8 & 0xff0000u) | ad << 24;
@@ -292,7 +442,11 @@ __global__ __launch_bounds__(PNG_BUILD_TB) void png_put_header_kernel(CkPngGeom 
     }
 }
 
+// The bits of a tile's tokens.  RUNS: a match of up to 21 bits belongs to the tile that holds its first byte; the bytes it
+// covers there hold no token, so only a match at the tile's last byte adds more than that byte's 15 bits: a tile has at
+// most 1024 * 15 + 6 bits, which the words below hold beside the 31 bits of the tile's place in its first word.
 constexpr int PNG_TILE_WORDS = (CK_PNG_TILE_BYTES * CK_PNG_MAX_BITS + 31 + 31) / 32 + 3;
+template <int RUNS>
 __global__ __launch_bounds__(PNG_TB) void png_put_kernel(CkPngGeom g, CkPngWork wk, uint32_t* __restrict__ pack)
 {
     __shared__ uint32_t words[PNG_TILE_WORDS];
@@ -304,13 +458,32 @@ __global__ __launch_bounds__(PNG_TB) void png_put_kernel(CkPngGeom g, CkPngWork 
     const int sh = (int)(P & 31);
     for (int i = threadIdx.x; i < PNG_TILE_WORDS; i += PNG_TB) words[i] = 0;
     const uint8_t* p = wk.filt + f * g.fbytes + ck_png_tile_at(g, band, t);
-    const uint8_t* bl = wk.lens + (f * g.bands + band) * CK_PNG_SYM_PITCH;
-    const uint16_t* bc = wk.codes + (f * g.bands + band) * CK_PNG_SYM_PITCH;
+    const uint8_t* bl = wk.lens + (f * g.bands + band) * ck_png_pitch(RUNS);
+    const uint16_t* bc = wk.codes + (f * g.bands + band) * ck_png_pitch(RUNS);
     uint64_t acc = 0;
     uint32_t nb = 0;
-    for (int j = 0; j < 4; j++) {
-        const int i = 4 * threadIdx.x + j;
-        if (i < L) { const uint32_t x = p[i]; acc |= (uint64_t)bc[x] << nb; nb += bl[x]; }
+    // RUNS: a lane's four positions can hold three literals and a match, 66 bits: the tokens are kept apart (their symbols,
+    // -1: none, and what follows the symbol's code) and go to the words one by one
+    int sym[4] = {-1, -1, -1, -1}, tb[4] = {0, 0, 0, 0};
+    uint32_t tail[4] = {0, 0, 0, 0};
+    if constexpr (!RUNS) {
+        for (int j = 0; j < 4; j++) {
+            const int i = 4 * threadIdx.x + j;
+            if (i < L) { const uint32_t x = p[i]; acc |= (uint64_t)bc[x] << nb; nb += bl[x]; }
+        }
+    } else {
+        __shared__ int lo[PNG_TB], hi[PNG_TB];
+        uint32_t x[4];
+        int s[4], e[4];
+        png_tile_runs(p, L, (int)wk.before[gt], (int)wk.after[gt], lo, hi, x, s, e);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int i = 4 * threadIdx.x + j;
+            if (i < L) {
+                sym[j] = ck_png_token(x[j], i - s[j] - 1, e[j] - s[j] - 1, &tb[j], &tail[j]);
+                if (sym[j] >= 0) nb += (uint32_t)(bl[sym[j]] + tb[j]);
+            }
+        }
     }
     scan[threadIdx.x] = nb;
     __syncthreads();
@@ -320,13 +493,25 @@ __global__ __launch_bounds__(PNG_TB) void png_put_kernel(CkPngGeom g, CkPngWork 
         scan[threadIdx.x] += v;
         __syncthreads();
     }
-    if (nb) {
-        const uint32_t q = (uint32_t)sh + scan[threadIdx.x] - nb;
-        const int s = (int)(q & 31);
-        const uint64_t hi = s ? acc >> (32 - s) : acc >> 32;
-        atomicOr(&words[q >> 5], (uint32_t)acc << s);
-        if ((uint32_t)hi) atomicOr(&words[(q >> 5) + 1], (uint32_t)hi);
-        if (hi >> 32) atomicOr(&words[(q >> 5) + 2], (uint32_t)(hi >> 32));
+    if constexpr (!RUNS) {
+        if (nb) {
+            const uint32_t q = (uint32_t)sh + scan[threadIdx.x] - nb;
+            const int s = (int)(q & 31);
+            const uint64_t hi = s ? acc >> (32 - s) : acc >> 32;
+            atomicOr(&words[q >> 5], (uint32_t)acc << s);
+            if ((uint32_t)hi) atomicOr(&words[(q >> 5) + 1], (uint32_t)hi);
+            if (hi >> 32) atomicOr(&words[(q >> 5) + 2], (uint32_t)(hi >> 32));
+        }
+    } else {
+        uint32_t q = (uint32_t)sh + scan[threadIdx.x] - nb;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (sym[j] >= 0) {
+                png_or_bits(words, q, bc[sym[j]], bl[sym[j]]);
+                q += bl[sym[j]];
+                png_or_bits(words, q, tail[j], tb[j]);
+                q += (uint32_t)tb[j];
+            }
     }
     __syncthreads();
     const int nw = (int)(((uint32_t)sh + scan[PNG_TB - 1] + 31) >> 5);
@@ -337,7 +522,8 @@ __global__ __launch_bounds__(PNG_TB) void png_put_kernel(CkPngGeom g, CkPngWork 
     }
 }
 
-int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk)
+template <int RUNS>
+static int png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk)
 {
     const unsigned bands = (unsigned)(m * g.bands), tiles = (unsigned)(m * g.tiles);
     {
@@ -345,24 +531,35 @@ int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom&
         hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)m * g.h), dim3(PNG_TB), 0, ctx->stream, d_bgr, g, filter, wk.filt);
         CK_HIP(ctx, hipGetLastError());
     }
+    if constexpr (RUNS) {
+        {
+            TimeScope ts(ctx, "png_edges");
+            hipLaunchKernelGGL(png_edges_kernel, dim3(tiles), dim3(PNG_TB), 0, ctx->stream, (const uint8_t*)wk.filt, g, wk.edge);
+            CK_HIP(ctx, hipGetLastError());
+        }
+        TimeScope ts(ctx, "png_join");
+        hipLaunchKernelGGL(png_join_kernel, dim3((bands + 63) / 64), dim3(64), 0, ctx->stream, g, wk, (long long)bands);
+        CK_HIP(ctx, hipGetLastError());
+    }
     {
         TimeScope ts(ctx, "png_count");
-        hipLaunchKernelGGL(png_count_kernel, dim3(bands), dim3(PNG_TB), 0, ctx->stream, (const uint8_t*)wk.filt, g, wk.count);
+        hipLaunchKernelGGL(png_count_kernel<RUNS>, dim3(bands), dim3(PNG_TB), 0, ctx->stream, (const uint8_t*)wk.filt, g, wk.count,
+                           (const uint32_t*)wk.before, (const uint32_t*)wk.after);
         CK_HIP(ctx, hipGetLastError());
     }
     {
         TimeScope ts(ctx, "png_build");
-        hipLaunchKernelGGL(png_build_kernel, dim3(bands), dim3(PNG_BUILD_TB), 0, ctx->stream, (const uint32_t*)wk.count, wk.lens, wk.codes);
+        hipLaunchKernelGGL(png_build_kernel<RUNS>, dim3(bands), dim3(PNG_BUILD_TB), 0, ctx->stream, (const uint32_t*)wk.count, wk.lens, wk.codes);
         CK_HIP(ctx, hipGetLastError());
     }
     {
         TimeScope ts(ctx, "png_size");
-        hipLaunchKernelGGL(png_size_kernel, dim3(tiles), dim3(PNG_TB), 0, ctx->stream, (const uint8_t*)wk.filt, g, (const uint8_t*)wk.lens, wk.tile_bits,
-                           wk.tile_a, wk.tile_b);
+        hipLaunchKernelGGL(png_size_kernel<RUNS>, dim3(tiles), dim3(PNG_TB), 0, ctx->stream, (const uint8_t*)wk.filt, g, (const uint8_t*)wk.lens, wk.tile_bits,
+                           wk.tile_a, wk.tile_b, (const uint32_t*)wk.before, (const uint32_t*)wk.after);
         CK_HIP(ctx, hipGetLastError());
     }
     TimeScope ts(ctx, "png_scan");
-    hipLaunchKernelGGL(png_scan_band_kernel, dim3((bands + 63) / 64), dim3(64), 0, ctx->stream, g, wk, (long long)bands);
+    hipLaunchKernelGGL(png_scan_band_kernel<RUNS>, dim3((bands + 63) / 64), dim3(64), 0, ctx->stream, g, wk, (long long)bands);
     CK_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(png_scan_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, g, wk);
     CK_HIP(ctx, hipGetLastError());
@@ -371,13 +568,24 @@ int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom&
     return CK_OK;
 }
 
-int k_png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes)
+int k_png_enc_measure(ck_ctx* ctx, const uint8_t* d_bgr, int m, const CkPngGeom& g, int filter, const CkPngWork& wk, int runs)
+{
+    return runs ? png_enc_measure<1>(ctx, d_bgr, m, g, filter, wk) : png_enc_measure<0>(ctx, d_bgr, m, g, filter, wk);
+}
+
+template <int RUNS>
+static int png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes)
 {
     CK_HIP(ctx, hipMemsetAsync(d_pack, 0, pack_bytes, ctx->stream));
     TimeScope ts(ctx, "png_put");
-    hipLaunchKernelGGL(png_put_header_kernel, dim3((unsigned)(m * g.bands)), dim3(PNG_BUILD_TB), 0, ctx->stream, g, wk, d_pack);
+    hipLaunchKernelGGL(png_put_header_kernel<RUNS>, dim3((unsigned)(m * g.bands)), dim3(PNG_BUILD_TB), 0, ctx->stream, g, wk, d_pack);
     CK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(png_put_kernel, dim3((unsigned)(m * g.tiles)), dim3(PNG_TB), 0, ctx->stream, g, wk, d_pack);
+    hipLaunchKernelGGL(png_put_kernel<RUNS>, dim3((unsigned)(m * g.tiles)), dim3(PNG_TB), 0, ctx->stream, g, wk, d_pack);
     CK_HIP(ctx, hipGetLastError());
     return CK_OK;
+}
+
+int k_png_enc_put(ck_ctx* ctx, int m, const CkPngGeom& g, const CkPngWork& wk, uint32_t* d_pack, uint64_t pack_bytes, int runs)
+{
+    return runs ? png_enc_put<1>(ctx, m, g, wk, d_pack, pack_bytes) : png_enc_put<0>(ctx, m, g, wk, d_pack, pack_bytes);
 }

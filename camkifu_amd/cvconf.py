@@ -21,6 +21,7 @@ sfinders = [
     ("None", "None"),
 ]
 snapshot_dir = "."                          # where VManagerBase.snapshot writes snapshot-N.npy (or .jpg) / game-N.sgf
+png_runs = False                            # VManagerBase.snapshot_png: the PNG encoder's runs mode (flat areas as deflate matches)
 bf_loc = None
 sf_loc = None
 annotate = False                            # VidProcessor._show draws the metadata lines on the image before it queues it

@@ -292,7 +292,7 @@ int ck_jpeg_encode_histograms(ck_ctx* ctx, int n, uint32_t* counts);
  * 2^28 pixels.  Anything else, and any damage, is CK_ERR_DATA with the cause in ck_last_error.
  * Writing gives 8-bit RGB files with one IDAT: per row the filter with the least sum of |residual| (libpng's heuristic) or a
  * forced one; per band of 16 rows one deflate block with a dynamic Huffman code of its own, literals only -- no matches, no
- * runs: a flat image does not go below about one bit a byte.  Filter, count, build, size, scan and put are launches of
+ * runs: a flat image does not go below about one bit a byte (unless ck_png_set_encode_matches asks for runs).  Filter, count, build, size, scan and put are launches of
  * their own; the Adler-32 is computed on the GPU too; only the zlib streams come down, the container is put around them
  * on the host. */
 typedef struct ck_png_info {
@@ -320,6 +320,19 @@ int ck_png_encode_bound(int h, int w, size_t* bytes);
 int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int filter, uint8_t* out, size_t stride, size_t* len);
 /* host only: ck_png_encode through the same steps in plain loops over host memory, the same bytes */
 int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len);
+/* The runs mode, on request: inside a band every maximal run of n equal filtered bytes is one literal and, for the n - 1
+ * bytes behind it, matches of distance 1 -- as many of length 258 as fit, then one of the rest where it is 3 or more, else
+ * one or two literals: what zlib's Z_RLE (cv2.imwrite's strategy) gains on flat images.  Runs cross rows, never a band's
+ * edge.  The block header then declares 286 literal/length codes and two distance codes of one bit; the same pixels come
+ * back, ck_png_encode_bound holds for both modes, and the literal-only mode's bytes are what they were. */
+enum { CK_PNG_MATCH_NONE = 0, CK_PNG_MATCH_RUNS = 1 };
+/* what ck_png_encode writes from now on; a new context has CK_PNG_MATCH_NONE */
+int ck_png_set_encode_matches(ck_ctx* ctx, int mode);
+/* host only: ck_png_encode_staged in either mode (matches: CK_PNG_MATCH_*) */
+int ck_png_encode_staged_mode(const uint8_t* bgr, int n, int h, int w, int filter, int matches, uint8_t* out, size_t stride, size_t* len);
+/* the tokens of the last ck_png_encode of this context, which took n frames: literals[f] and matches[f] of frame f (the
+ * end-of-block symbols are not counted), read from the histograms its count step left in HBM */
+int ck_png_run_stats(ck_ctx* ctx, int n, long long* literals, long long* matches);
 /* the seams of the PNG kernels: rows of an encoder band, bytes of its bit-packing tile, bytes of the unfilter kernel's chunk,
  * rows of its workgroup */
 int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, int32_t* group_rows);

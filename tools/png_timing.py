@@ -11,9 +11,18 @@ Images: goban images (380 x 380: camkifu_amd/synth.py scenes through the perspec
    1, 8 and 32 frames a call.
 5. bytes: the files of png_encode against Pillow's default save(.., "PNG") and against zlib level 1 with Z_RLE over the same
    filtered rows (the stand-in for cv2.imwrite), goban images and a 1080p frame.
+6. --runs: the encoder's runs mode beside its default mode, a round of the one after a round of the other: bytes per frame
+   (runs mode, default mode, the Z_RLE stand-in) on goban images, the same images annotated with core/annotate.py's goban
+   list, 1080p synth frames and an all-zero 1080p frame; kernel time per frame of every step (png_edges and png_join among
+   them); png_encode frames/s at 1, 8 and 32 frames a call.
+   (Without --runs a `runs` section the output file already holds is kept and marked `carried_over`.)
+7. --baseline FILE: FILE is what another build's run of this tool wrote, the parent commit's for instance.  The default
+   mode's medians of this run (sections 3 and 4, and the `none` legs of the runs section) are listed against the baseline's
+   [min .. max], each with `inside` and the distance of the medians in per cent, and the baseline's figures are copied beside
+   them (`default_mode_against_baseline`): whether a compile-time mode parameter has leaked into the default path.
 Every timed leg is warmed up and runs `--reps` rounds: median / min / max.
 
-    python tools/png_timing.py [--reps 5] [--out profiles/png_timing.json]
+    python tools/png_timing.py [--reps 5] [--runs] [--baseline FILE] [--out profiles/png_timing.json]
 
 There is no CPU fallback: without a GPU the first device call raises."""
 import argparse
@@ -89,9 +98,114 @@ def _bytes(ours, frames):
     return res
 
 
+RUN_KERNELS = ("png_filter", "png_edges", "png_join", "png_count", "png_build", "png_size", "png_scan", "png_put")
+MODES = ("none", "runs")
+
+
+def _rle_bytes(data):
+    co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_RLE)
+    return 57 + len(co.compress(zlib.decompress(_idat(data))) + co.flush())
+
+
+def _runs_section(ctx, dev, small, big, reps):
+    """the runs mode beside the default mode, in this process and in alternating rounds: bytes, kernel times, frames/s"""
+    import torch
+    from camkifu_amd.core import annotate
+    from camkifu_amd.stone.stonesfinder import PosGrid
+    from camkifu_amd import capi, synth
+    grid = PosGrid(380)
+    fg = np.zeros((19, 19), np.int64)
+    fg[8:11, 8:11] = 1 << 20                                 # nine agitated zones: translucent red rectangles
+    lists = [annotate.goban_list(synth.scene(480, 640, seed=synth.SEED + k)["stones"], fg, grid, k + 1, 8, "B[D4] W[Q16]") for k in range(8)]
+    sets = {"gobans_380x380": small[:8].contiguous(), "gobans_annotated_380x380": ctx.overlay_draw(small[:8].clone(), lists),
+            "synth_1920x1080": big[:2].contiguous(), "zeros_1920x1080": torch.zeros((1, 1080, 1920, 3), dtype=torch.uint8, device=dev)}
+    res = dict(bytes_per_frame={}, note="zlib_level_1_rle_same_rows: zlib level 1 with Z_RLE over the rows our encoder filtered, plus the "
+               "57 bytes of the container: the stand-in for cv2.imwrite")
+    for k, fr in sets.items():
+        runs, plain = ctx.png_encode(fr, runs=True), ctx.png_encode(fr, runs=False)
+        if not np.array_equal(ctx.png_decode(runs), fr.cpu().numpy()):
+            raise SystemExit("runs mode: %s does not round trip" % k)
+        rle = int(np.mean([_rle_bytes(d) for d in runs]))
+        r = int(np.mean([len(d) for d in runs]))
+        res["bytes_per_frame"][k] = dict(runs=r, default=int(np.mean([len(d) for d in plain])), zlib_level_1_rle_same_rows=rle,
+                                         runs_over_rle=round(r / rle, 3))
+    ctx.png_encode(sets["gobans_annotated_380x380"], runs=True)
+    st = ctx.png_run_stats()
+    res["tokens_per_frame_annotated_gobans"] = dict(literals=int(np.mean([s["literals"] for s in st])), matches=int(np.mean([s["matches"] for s in st])))
+    res["staged_encoder_same_bytes"] = bool(capi.png_encode_staged(small[:2].cpu().numpy(), runs=True) == ctx.png_encode(small[:2], runs=True))
+    timed = {"380x380": small, "1920x1080": big}
+    # kernel times: a round is one call in each mode
+    ker = {k: {m: {n: [] for n in RUN_KERNELS} for m in MODES} for k in timed}
+    for k, fr in timed.items():
+        fr8 = fr[:8].contiguous()
+        for m in MODES:
+            ctx.png_encode(fr8, runs=(m == "runs"))
+        ctx.timing_enable(True)
+        for _ in range(reps):
+            for m in MODES:
+                ctx.png_set_encode_matches(m)
+                ctx.timing_reset()
+                ctx.png_encode(fr8)
+                for n in RUN_KERNELS:
+                    ker[k][m][n].append(ctx.timing_get(n)[0] / 8)
+        ctx.timing_enable(False)
+        ctx.png_set_encode_matches("none")
+    res["encoder_kernel_ms_per_frame"] = {k: {m: {n: spread_of(v) for n, v in ker[k][m].items() if m == "runs" or n not in ("png_edges", "png_join")}
+                                              for m in MODES} for k in timed}
+    # frames/s: a round is `calls` calls in each mode
+    res["png_encode_frames_per_s"] = {}
+    for k, fr in timed.items():
+        res["png_encode_frames_per_s"][k] = {}
+        for b in (1, 8, 32):
+            frb, calls = fr[:b].contiguous(), max(2, 64 // b)
+            fps = {m: [] for m in MODES}
+            for m in MODES:
+                ctx.png_encode(frb, runs=(m == "runs"))
+            for _ in range(reps):
+                for m in MODES:
+                    ctx.png_set_encode_matches(m)
+                    t0 = time.perf_counter()
+                    for _ in range(calls):
+                        ctx.png_encode(frb)
+                    fps[m].append(b * calls / (time.perf_counter() - t0))
+            ctx.png_set_encode_matches("none")
+            res["png_encode_frames_per_s"][k]["%d_frames_a_call" % b] = {
+                m: dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1), rounds=len(v)) for m, v in fps.items()}
+    return res
+
+
+def _against_baseline(out, base):
+    """the default mode's medians of this run -- sections 3 and 4, measured by the same loops as the baseline's, and the
+    `none` legs of the runs section -- against the baseline's [min .. max] of the same quantity: every figure, whether it lies
+    inside, and how far the median is from the baseline's median in per cent"""
+    rows = []
+
+    def row(what, median, b, lo, hi, mid):
+        rows.append(dict(what=what, median=median, baseline_median=b[mid], baseline_min=b[lo], baseline_max=b[hi],
+                         inside=bool(b[lo] <= median <= b[hi]), off_pct=round(100.0 * (median - b[mid]) / b[mid], 1)))
+
+    for k, ker in base.get("encoder_kernel_ms_per_frame", {}).items():
+        for n, b in ker.items():
+            row("section 3, %s %s" % (k, n), out["encoder_kernel_ms_per_frame"][k][n]["median_ms"], b, "min_ms", "max_ms", "median_ms")
+            if "runs" in out:
+                row("runs section, none, %s %s" % (k, n), out["runs"]["encoder_kernel_ms_per_frame"][k]["none"][n]["median_ms"], b, "min_ms", "max_ms", "median_ms")
+    for k, per in base.get("frames_per_s", {}).items():
+        for calls, legs in per.items():
+            b = legs["png_encode"]
+            row("section 4, png_encode %s %s" % (k, calls), out["frames_per_s"][k][calls]["png_encode"]["median"], b, "min", "max", "median")
+            if "runs" in out:
+                row("runs section, none, png_encode %s %s" % (k, calls), out["runs"]["png_encode_frames_per_s"][k][calls]["none"]["median"], b, "min", "max", "median")
+    return dict(rows=rows, outside=[r["what"] for r in rows if not r["inside"]],
+                note="the baseline is another build's run of this tool, by --baseline; its spread is that of 5 rounds inside one process, "
+                     "so a difference between two processes shows here as `outside` even where the code is the same")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--runs", action="store_true", help="add the `runs` section: the runs mode beside the default mode")
+    ap.add_argument("--baseline", help="the file another build's run of this tool wrote (the parent commit's, say): the default "
+                    "mode's figures of this run are listed against its spread under `default_mode_against_baseline`")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png_timing.json"))
     args = ap.parse_args(argv)
     if args.reps < 5:
@@ -150,8 +264,23 @@ def main(argv=None):
         # 5. bytes
         out["bytes_per_frame"] = {"380x380": _bytes(files["380x380"][:8], small[:8].cpu().numpy()),
                                   "1920x1080": _bytes(files["1920x1080"][:2], big[:2].cpu().numpy())}
+        # 6. the runs mode beside the default mode
+        if args.runs:
+            out["runs"] = _runs_section(ctx, dev, small, big, args.reps)
     finally:
         ctx.close()
+    if args.baseline:
+        with open(args.baseline) as f:
+            base = json.load(f)
+        out["default_mode_against_baseline"] = dict(_against_baseline(out, base), baseline_file=os.path.basename(args.baseline),
+                                                    baseline=dict(encoder_kernel_ms_per_frame=base["encoder_kernel_ms_per_frame"],
+                                                                  png_encode_frames_per_s={k: {c: legs["png_encode"] for c, legs in per.items()}
+                                                                                           for k, per in base["frames_per_s"].items()}))
+    if not args.runs and os.path.exists(args.out):           # a section this run did not measure stays, and says so
+        with open(args.out) as f:
+            before = json.load(f)
+        if "runs" in before:
+            out["runs"] = dict(before["runs"], carried_over="from an earlier run of this tool with --runs: not measured with the other sections")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)

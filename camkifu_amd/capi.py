@@ -22,6 +22,7 @@ CK_JPEG_ENTROPY_HOST, CK_JPEG_ENTROPY_DEVICE = 0, 1
 CK_JPEG_TABLES_STANDARD, CK_JPEG_TABLES_OPTIMISED = 0, 1
 CK_JPEG_ENTROPY_DEVICE_SPANS = 2
 CK_PNG_MATCH_NONE, CK_PNG_MATCH_RUNS = 0, 1
+CK_PNG_INFLATE_HOST, CK_PNG_INFLATE_DEVICE = 0, 1
 CK_CNN_FP32, CK_CNN_BF16, CK_CNN_F16X2, CK_CNN_F16Q8 = 0, 1, 2, 3
 CK_CNN_DEFAULT = CK_CNN_F16X2            # what a new context computes in
 CK_BOARD_LINES, CK_BOARD_NO_CONTOUR, CK_BOARD_TOO_SMALL = 0, 1, 2
@@ -606,13 +607,66 @@ class Context:
                      int(restart_interval), out.ctypes.data_as(C.c_void_p), stride, lens))
         return [out[f * stride:f * stride + lens[f]].tobytes() for f in range(n)]
 
-    def png_decode(self, streams, to_device=None, out=None):
+    _png_inflate = "host"
+
+    def png_set_inflate(self, mode):
+        """where png_decode inflates from now on: "host" (the default: the library's worker threads) or "device" (a wave per
+        zlib stream on the GPU; only the compressed bytes go up).  Both accept and refuse the same files with the same
+        message and give the same pixels; one stream keeps one wave busy, so the device mode is for batches."""
+        modes = {"host": CK_PNG_INFLATE_HOST, "device": CK_PNG_INFLATE_DEVICE}
+        if mode not in modes:
+            raise CkError("png inflate: 'host' or 'device' is needed, got %r" % (mode,))
+        self._chk(lib().ck_png_set_inflate(self._h, modes[mode]))
+        self._png_inflate = mode
+
+    def png_inflate_device(self, streams, cap=None):
+        """the inflate kernel alone: zlib streams (bytes-like objects or uint8 arrays in host memory), one wave each in one
+        launch -> a list with dict(data, total, cause, produced) for each: the first `cap` bytes (an int for all streams or
+        one for each; None: 65536), the count of all bytes (0 for a refused stream), 0 or the cause of the refusal (the
+        CK_INF_* of csrc/ck_png_inflate_stage.h, as png_inflate_staged(verdict=True) gives it) and the bytes inflated in
+        front of what was refused.  data is None for a refused stream: it does not fail the call."""
+        ptrs, lens, keep = _jpeg_streams(streams)
+        n = len(keep)
+        caps = [65536 if cap is None else int(cap)] * n if cap is None or isinstance(cap, (int, np.integer)) else [int(c) for c in cap]
+        if len(caps) != n or min(caps) < 0:
+            raise CkError("png_inflate_device: one cap >= 0 for each of the %d streams is needed" % n)
+        stride = max(16, max(caps))
+        out = np.empty(n * stride, np.uint8)
+        total, cause, produced = (C.c_size_t * n)(), (C.c_int32 * n)(), (C.c_longlong * n)()
+        self._chk(lib().ck_png_inflate_device(self._h, ptrs, lens, n, out.ctypes.data_as(C.c_void_p), (C.c_size_t * n)(*caps), stride,
+                                              total, cause, produced))
+        return [dict(data=None if cause[f] else out[f * stride:f * stride + min(caps[f], total[f])].tobytes(), total=int(total[f]),
+                     cause=int(cause[f]), produced=int(produced[f])) for f in range(n)]
+
+    def png_uploaded_bytes(self):
+        """the bytes this context's last png_decode copied to the GPU, all passes: inflated rows in the host mode, zlib
+        streams in the device mode, descriptors and palettes in both"""
+        b = C.c_longlong(0)
+        self._chk(lib().ck_png_uploaded_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def png_inflate_stats(self):
+        """the inflate kernel's counts for this context's last png_decode in device mode or png_inflate_device ->
+        dict(streams, steps, tokens, bytes): window steps, literals and matches applied, bytes produced"""
+        v = (C.c_longlong * 4)()
+        self._chk(lib().ck_png_inflate_stats(self._h, v))
+        return dict(zip(("streams", "steps", "tokens", "bytes"), (int(x) for x in v)))
+
+    def png_decode(self, streams, to_device=None, out=None, inflate=None):
         """PNG files (a list of bytes-like objects or uint8 arrays in host memory, all of the first one's height and width,
         each of its own colour type, bit depth and palette) -> BGR frames (n, h, w, 3), what cv2.imread gives: alpha dropped,
         16-bit samples cut to their high byte.  The chunk walk and the inflate run on the host (the frames of a batch in
         parallel), the unfiltering and the expansion to BGR in one kernel.  `to_device`: a torch device to leave the frames
-        in HBM; `out`: a preallocated (n, h, w, 3) array / tensor to fill.  CkError with code CK_ERR_DATA and a message that
+        in HBM; `out`: a preallocated (n, h, w, 3) array / tensor to fill.  inflate: "host" / "device" for this call, None
+        takes what png_set_inflate has set (the host in a new context).  CkError with code CK_ERR_DATA and a message that
         names the frame and the cause for a file the reader refuses or that is damaged; its index is the error's `bad_frame`."""
+        if inflate is not None and inflate != self._png_inflate:
+            was = self._png_inflate
+            self.png_set_inflate(inflate)
+            try:
+                return self.png_decode(streams, to_device, out)
+            finally:
+                self.png_set_inflate(was)
         ptrs, lens, keep = _jpeg_streams(streams)
         n = len(keep)
         info = PngInfo()
@@ -1478,6 +1532,42 @@ def png_inflate(data):
         if total.value <= cap:
             return out[:total.value].tobytes()
         cap = total.value
+
+
+def png_inflate_staged(data, cap=None, rows=None, verdict=False):
+    """png_inflate through the steps of the device inflate in plain loops on the host, in the kernel's order (host only): the
+    same bytes, and CkError with the same message.  cap: keep only the first `cap` bytes (None: all).  rows: (h, rowbytes) --
+    the stream holds h rows of 1 + rowbytes bytes, and the PNG reader's two checks (enough bytes, filter bytes up to 4)
+    follow the inflate.  verdict=True: no error is raised; -> dict(data (None for a refused stream), total, cause,
+    produced, message)"""
+    ptrs, lens, keep = _jpeg_streams([data])
+    h, rowbytes = (0, 0) if rows is None else (int(rows[0]), int(rows[1]))
+    room = max(1 << 16, 8 * keep[0].size) if cap is None else int(cap)
+    while True:
+        out = np.empty(max(room, 1), np.uint8)
+        total, cause, produced = C.c_size_t(0), C.c_int32(0), C.c_longlong(0)
+        rc = lib().ck_png_inflate_staged(C.c_void_p(keep[0].ctypes.data), keep[0].size, out.ctypes.data_as(C.c_void_p), room, C.byref(total),
+                                         h, rowbytes, C.byref(cause), C.byref(produced))
+        if rc != 0 and (not verdict or rc != CK_ERR_DATA):
+            raise _host_error(rc)
+        if rc == 0 and cap is None and total.value > room:
+            room = total.value
+            continue
+        got = None if rc else out[:min(room, total.value)].tobytes()
+        if not verdict:
+            return got
+        return dict(data=got, total=total.value, cause=cause.value, produced=produced.value,
+                    message=(lib().ck_last_error(None) or b"").decode() if rc else "")
+
+
+def png_inflate_geometry():
+    """the seams of the inflate kernel -> dict(window_bits: the bit offsets a window step decodes at once; flush_bytes: the
+    bytes that leave the ring of 2 * flush_bytes at a time); host only"""
+    v = [C.c_int32(0) for _ in range(2)]
+    rc = lib().ck_png_inflate_geometry(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise _host_error(rc)
+    return dict(window_bits=v[0].value, flush_bytes=v[1].value)
 
 
 def png_encode_bound(h, w):

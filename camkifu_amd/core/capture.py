@@ -321,6 +321,39 @@ def write_png(path, bgr, encode=None, filter=None, runs=None):
     return len(data)
 
 
+def read_pngs(paths, to_device=None, inflate=None):
+    """PNG stills -> their BGR images, in the order of `paths`: the files are grouped by (height, width) and every group is
+    decoded in one png_decode of the process-wide Context -- the call in which the device inflate has a batch to work on.
+    to_device: a torch device to leave the images in HBM; inflate: "host" / "device", None takes cvconf.png_inflate.
+    -> a list of (h, w, 3) arrays (views into their group's batch).  OSError for a file that cannot be read, CkError for
+    one the reader refuses: its `bad_frame` is the index into `paths`."""
+    from .. import capi, cvconf
+    ctx = capi.get_context()
+    files = []
+    for p in paths:
+        with open(p, "rb") as f:
+            files.append(f.read())
+    groups = {}
+    for k, data in enumerate(files):
+        try:
+            info = capi.png_header(data)
+        except capi.CkError as e:
+            e.bad_frame = k
+            raise
+        groups.setdefault((info["h"], info["w"]), []).append(k)
+    images = [None] * len(files)
+    for members in groups.values():
+        try:
+            batch = ctx.png_decode([files[k] for k in members], to_device=to_device, inflate=cvconf.png_inflate if inflate is None else inflate)
+        except capi.CkError as e:
+            if e.bad_frame is not None:
+                e.bad_frame = members[e.bad_frame]
+            raise
+        for i, k in enumerate(members):
+            images[k] = batch[i]
+    return images
+
+
 class MjpegWriter:
     """Motion-JPEG into a RIFF 'AVI ' file, streamed: write(frames) encodes a batch -- (n, h, w, 3) BGR, a numpy array or a
     tensor in HBM -- and appends one '00dc' chunk per frame; close() patches the RIFF, movi, avih and strh fields that depend
@@ -596,7 +629,12 @@ class ImageCapture:
             if decode is None:
                 from .. import capi
                 ctx = capi.get_context()
-                decode = ctx.png_decode if data[:8] == PNG_SIGNATURE else ctx.jpeg_decode
+                decode = ctx.jpeg_decode
+                if data[:8] == PNG_SIGNATURE:
+                    from .. import cvconf
+                    decode = ctx.png_decode                  # (the keyword reaches it only when cvconf asks for the device inflate)
+                    if cvconf.png_inflate != "host":
+                        decode = lambda streams: ctx.png_decode(streams, inflate=cvconf.png_inflate)
             self.img = np.asarray(decode([data]))[0]
         except (OSError, RuntimeError) as exc:
             self.error = exc

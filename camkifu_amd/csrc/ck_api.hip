@@ -19,6 +19,7 @@
 #include "ck_jpeg_span.h"
 #include "ck_jpeg_enc.h"
 #include "ck_png.h"
+#include "ck_png_inflate_stage.h"
 #include "ck_overlay.h"
 
 thread_local std::string g_ck_create_error;
@@ -1574,6 +1575,109 @@ int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, 
     return CK_OK;
 }
 
+int ck_png_inflate_geometry(int32_t* window_bits, int32_t* flush_bytes)
+{
+    if (!window_bits || !flush_bytes) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    *window_bits = CK_INF_WINDOW; *flush_bytes = CK_INF_FLUSH;
+    return CK_OK;
+}
+
+int ck_png_inflate_staged(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total, int h, long long rowbytes,
+                          int32_t* cause, long long* produced)
+{
+    if (!data || !total || (!out && cap)) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
+    if (h < 0 || rowbytes < 0 || (h > 0 && rowbytes == 0)) return ck_fail(nullptr, CK_ERR_ARG, "bad rows: %d of 1 + %lld bytes", h, rowbytes);
+    try {
+        char msg[CK_PNG_MSG];
+        CkInfRecord rec;
+        const int rc = ck_png_unzip_staged_rows(data, len, out, cap, total, &rec, msg, h, rowbytes);
+        if (cause) *cause = rec.cause;
+        if (produced) *produced = rec.produced;
+        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
+    } catch (const std::exception& e) {
+        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
+    }
+}
+
+int ck_png_set_inflate(ck_ctx* ctx, int mode)
+{
+    CK_API_BEGIN(ctx)
+    if (mode != CK_PNG_INFLATE_HOST && mode != CK_PNG_INFLATE_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown PNG inflate mode %d", mode);
+    ctx->png_inflate = mode;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_png_uploaded_bytes(ck_ctx* ctx, long long* bytes)
+{
+    CK_API_BEGIN(ctx)
+    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
+    *bytes = ctx->png_uploaded;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+int ck_png_inflate_stats(ck_ctx* ctx, long long* stats)
+{
+    CK_API_BEGIN(ctx)
+    if (!stats) return ck_fail(ctx, CK_ERR_ARG, "stats is NULL");
+    for (int k = 0; k < 4; k++) stats[k] = ctx->png_inf_stats[k];
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
+static void png_inflate_count(ck_ctx* ctx, const std::vector<CkInfRecord>& recs)
+{
+    for (const CkInfRecord& r : recs) {
+        ctx->png_inf_stats[0] += 1; ctx->png_inf_stats[1] += r.steps; ctx->png_inf_stats[2] += r.tokens; ctx->png_inf_stats[3] += r.produced;
+    }
+}
+
+int ck_png_inflate_device(ck_ctx* ctx, const uint8_t* const* z, const size_t* zlen, int n, uint8_t* out, const size_t* cap, size_t stride,
+                          size_t* total, int32_t* cause, long long* produced)
+{
+    CK_API_BEGIN(ctx)
+    if (!z || !zlen || !out || !cap || !total || !cause || !produced || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    size_t z_bytes = 0, most = 0;
+    for (int f = 0; f < n; f++) {
+        if (!z[f] && zlen[f]) return ck_fail(ctx, CK_ERR_ARG, "stream %d is NULL", f);
+        if (cap[f] > stride) return ck_fail(ctx, CK_ERR_ARG, "stream %d: room for %zu bytes, above the stride of %zu", f, cap[f], stride);
+        z_bytes += up16(zlen[f]);
+        most = cap[f] > most ? cap[f] : most;
+    }
+    const size_t dstride = up16(most), a_z = up16((size_t)n * sizeof(CkInfJob)), a_rec = a_z + z_bytes,
+                 a_out = a_rec + up16((size_t)n * sizeof(CkInfRecord)), all = a_out + (size_t)n * dstride;
+    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, a_rec > (size_t)n * dstride ? a_rec : (size_t)n * dstride));
+    CK_TRY(ck_ensure(ctx, ctx->png_inf, all));
+    uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
+    CkInfJob* jobs = (CkInfJob*)hp;
+    size_t zat = a_z;
+    for (int f = 0; f < n; f++) {
+        jobs[f].z_off = (int64_t)zat; jobs[f].zlen = (int64_t)zlen[f]; jobs[f].out_off = (int64_t)(a_out + (size_t)f * dstride);
+        jobs[f].cap = (int64_t)cap[f]; jobs[f].need = 0; jobs[f].pitch = 0;
+        if (zlen[f]) memcpy(hp + zat, z[f], zlen[f]);
+        zat += up16(zlen[f]);
+    }
+    uint8_t* dev = (uint8_t*)ctx->png_inf.p;
+    CK_HIP(ctx, hipMemcpyAsync(dev, hp, a_rec, hipMemcpyHostToDevice, ctx->stream));
+    CK_TRY(k_png_inflate(ctx, dev, dev, (const CkInfJob*)dev, (CkInfRecord*)(dev + a_rec), n));
+    std::vector<CkInfRecord> recs((size_t)n);
+    CK_HIP(ctx, hipMemcpyAsync(recs.data(), dev + a_rec, (size_t)n * sizeof(CkInfRecord), hipMemcpyDeviceToHost, ctx->stream));
+    if (dstride) CK_HIP(ctx, hipMemcpyAsync(hp, dev + a_out, (size_t)n * dstride, hipMemcpyDeviceToHost, ctx->stream));
+    CK_TRY(finish(ctx));
+    for (int k = 0; k < 4; k++) ctx->png_inf_stats[k] = 0;
+    png_inflate_count(ctx, recs);
+    for (int f = 0; f < n; f++) {
+        const CkInfRecord& r = recs[(size_t)f];
+        cause[f] = r.cause; produced[f] = r.produced; total[f] = r.cause == CK_INF_OK ? (size_t)r.produced : 0;
+        const size_t have = r.cause != CK_INF_OK ? 0 : (size_t)r.produced < cap[f] ? (size_t)r.produced : cap[f];   // (a refused stream's pending bytes never left the ring)
+        if (have) memcpy(out + (size_t)f * stride, hp + (size_t)f * dstride, have);
+    }
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
 int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space, int32_t* bad_frame)
 {
     if (bad_frame) *bad_frame = -1;
@@ -1607,6 +1711,58 @@ int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, in
     OutStage<uint8_t> o;
     CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    ctx->png_uploaded = 0;
+    if (ctx->png_inflate == CK_PNG_INFLATE_DEVICE) {
+        // per pass: descriptors, palettes, jobs and the zlib streams in one pinned block -> one upload -> the inflate kernel
+        // writes the rows behind them -> the verdict records come down -> the unfilter kernel, unless a frame was refused
+        for (int k = 0; k < 4; k++) ctx->png_inf_stats[k] = 0;
+        for (int f0 = 0; f0 < n;) {
+            int m = 0;
+            size_t rows_bytes = 0, z_bytes = 0;
+            while (f0 + m < n && (m == 0 || rows_bytes + up16(heads[f0 + m].inflated()) <= ((size_t)256 << 20))) {
+                z_bytes += up16(heads[f0 + m].zlen);
+                rows_bytes += up16(heads[f0 + m++].inflated());
+            }
+            const size_t a_pal = up16((size_t)m * sizeof(CkPngDesc)), a_jobs = a_pal + (size_t)m * 768, a_z = a_jobs + up16((size_t)m * sizeof(CkInfJob)),
+                         a_rec = a_z + z_bytes, a_rows = a_rec + up16((size_t)m * sizeof(CkInfRecord)), total = a_rows + rows_bytes;
+            CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, a_rec));     // (the records and the rows exist on the device only)
+            CK_TRY(ck_ensure(ctx, ctx->in_stage, total));
+            uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
+            CkPngDesc* desc = (CkPngDesc*)hp;
+            CkInfJob* jobs = (CkInfJob*)(hp + a_jobs);
+            size_t at = a_rows, zat = a_z;
+            for (int i = 0; i < m; i++) {
+                const CkPngHead& hd = heads[f0 + i];
+                desc[i].off = (int64_t)at; desc[i].rowbytes = hd.rowbytes; desc[i].color_type = hd.color_type; desc[i].depth = hd.bit_depth;
+                desc[i].bpp = hd.bpp; desc[i].palette_n = hd.palette_n;
+                memcpy(hp + a_pal + (size_t)i * 768, hd.palette, 768);
+                jobs[i].z_off = (int64_t)zat; jobs[i].zlen = (int64_t)hd.zlen; jobs[i].out_off = (int64_t)at;
+                jobs[i].cap = jobs[i].need = (int64_t)hd.inflated(); jobs[i].pitch = 1 + hd.rowbytes;
+                if (hd.zlen) memcpy(hp + zat, hd.z, hd.zlen);
+                at += up16(hd.inflated()); zat += up16(hd.zlen);
+            }
+            uint8_t* dev = (uint8_t*)ctx->in_stage.p;
+            CK_HIP(ctx, hipMemcpyAsync(dev, hp, a_rec, hipMemcpyHostToDevice, ctx->stream));
+            ctx->png_uploaded += (long long)a_rec;
+            CK_TRY(k_png_inflate(ctx, dev, dev, (const CkInfJob*)(dev + a_jobs), (CkInfRecord*)(dev + a_rec), m));
+            std::vector<CkInfRecord> recs((size_t)m);
+            CK_HIP(ctx, hipMemcpyAsync(recs.data(), dev + a_rec, (size_t)m * sizeof(CkInfRecord), hipMemcpyDeviceToHost, ctx->stream));
+            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            png_inflate_count(ctx, recs);
+            for (int i = 0; i < m; i++)
+                if (recs[(size_t)i].cause != CK_INF_OK) {
+                    char msg[CK_PNG_MSG];
+                    ck_png_inflate_message(recs[(size_t)i], heads[f0 + i].h, (long long)heads[f0 + i].rowbytes, msg);
+                    if (bad_frame) *bad_frame = f0 + i;
+                    return ck_fail(ctx, CK_ERR_DATA, "frame %d: %s", f0 + i, msg);
+                }
+            CK_TRY(k_png_unfilter(ctx, dev, (const CkPngDesc*)dev, dev + a_pal, m, h, w, o.dev + (size_t)f0 * oframe));
+            f0 += m;
+            if (f0 < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next pass uploads into the same block
+        }
+        CK_TRY(o.deliver(ctx));
+        return finish(ctx);
+    }
     // per pass: descriptors, palettes and the inflated rows of its frames in one pinned block -> one upload -> the kernel.
     // A pass takes frames while their rows stay within 256 MB (one frame at least).
     for (int f0 = 0; f0 < n;) {
@@ -1635,6 +1791,7 @@ int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, in
         CK_TRY(refused(f0));
         const void* d_in;
         CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage, &d_in));
+        ctx->png_uploaded += (long long)total;
         CK_TRY(k_png_unfilter(ctx, (uint8_t*)ctx->in_stage.p, (const CkPngDesc*)d_in, (const uint8_t*)d_in + a_pal, m, h, w, o.dev + (size_t)f0 * oframe));
         f0 += m;
         if (f0 < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the next pass inflates into the same block

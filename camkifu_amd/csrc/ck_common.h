@@ -139,6 +139,7 @@ struct ck_ctx {
     DevBuf jspan;        // CK_JPEG_ENTROPY_DEVICE_SPANS: candidates, entries and flags of a pass (k_jpeg_span.hip)
     DevBuf png_work;     // the PNG encoder: filtered rows, counters, codes, sizes and offsets of a pass (CkPngWork),
     DevBuf png_pack;     // and its zlib streams, one behind the other
+    DevBuf png_inf;      // ck_png_inflate_device: jobs, records and streams of a call (ck_png_decode keeps them in in_stage)
 
     CnnWeights cnn;
     int* cnn_flag_dev = nullptr;     // cnn_flag as the device sees it
@@ -161,6 +162,9 @@ struct ck_ctx {
     size_t png_count_at = 0;               // as far as their histograms have been read; those of its last pass are still in
     int png_count_frames = 0, png_count_runs = 0;   // png_work, at png_count_at, of so many frames, in this mode
     long long png_count_bands = 0;         // (bands of a frame)
+    int png_inflate = CK_PNG_INFLATE_HOST;  // where ck_png_decode inflates (ck_png_set_inflate)
+    long long png_uploaded = 0;            // ck_png_uploaded_bytes: of the last ck_png_decode
+    long long png_inf_stats[4] = {0, 0, 0, 0};   // ck_png_inflate_stats
     uint64_t rng_state = 0xffffffffULL;   // cv::RNG of the stones thread (theRNG()): ck_cluster_stones draws from it
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
@@ -351,6 +355,14 @@ struct CkPngDesc {
 };
 static_assert(sizeof(CkPngDesc) == 32, "a descriptor row is 32 bytes");
 int k_png_unfilter(ck_ctx* ctx, uint8_t* d_rows, const CkPngDesc* d_desc, const uint8_t* d_palettes, int n, int h, int w, uint8_t* d_bgr);
+// The device inflate (k_png_inflate.hip): a wave per zlib stream.  Stream i lies at d_z + z_off; its first `cap` bytes go to
+// d_out + out_off (a multiple of 16); pitch > 0: it holds rows of `pitch` bytes, `need` bytes of them, whose filter bytes
+// are checked.  One verdict record (ck_png_inflate_stage.h) a stream.
+struct CkInfJob {
+    int64_t z_off, zlen, out_off, cap, need, pitch;
+};
+struct CkInfRecord;
+int k_png_inflate(ck_ctx* ctx, const uint8_t* d_z, uint8_t* d_out, const CkInfJob* d_jobs, CkInfRecord* d_rec, int n);
 // Writing, m frames: where the arrays of a pass lie in HBM -- per band (count, lens, codes: ck_png_pitch(runs) each; band_off),
 // per tile (edge, before, after: the runs mode only, else NULL), per frame (out_off: m + 1; head: the bytes of all streams,
 // then the bytes of each)

@@ -1,6 +1,7 @@
 // ck_png.cpp -- the host half of the PNG reader and writer: see ck_png.h.  Plain C++ (tools/sanitize/png_fuzz.cpp links it alone).
 #include "ck_png.h"
 #include "ck_png_stage.h"
+#include "ck_png_inflate_stage.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -397,6 +398,177 @@ int ck_png_rows(const CkPngHead& hd, uint8_t* rows, char* msg)
     for (int y = 0; y < hd.h; y++)
         if (rows[(size_t)y * pitch] > 4) return refuse(msg, "row %d: filter type %d", y, rows[(size_t)y * pitch]);
     return CK_OK;
+}
+
+// ---- the staged inflate: the steps of ck_png_inflate_stage.h in plain loops, in the kernel's order ----
+void ck_png_inflate_message(const CkInfRecord& r, int h, long long rowbytes, char* msg)
+{
+    static const char* const TOKEN[] = {"invalid literal/length code or the data ends inside one", "invalid literal/length code",
+                                        "the data ends inside a length", "invalid distance code or the data ends inside one",
+                                        "invalid distance code", "the data ends inside a distance", "a distance beyond the bytes produced so far"};
+    static const char* const BUILD[] = {"no code-length code", "over-subscribed code set", "incomplete code set", "a code table without room"};
+    const size_t need = (size_t)(h > 0 ? h : 0) * (size_t)(1 + rowbytes);
+    msg[0] = 0;
+    switch (r.cause) {
+    case CK_INF_OK: break;
+    case CK_INF_ZLIB_SHORT: refuse(msg, "zlib stream of %zu bytes", (size_t)r.arg0); break;
+    case CK_INF_ZLIB_CHECK: refuse(msg, "zlib header: the check bits do not hold"); break;
+    case CK_INF_ZLIB_METHOD: refuse(msg, "zlib header: compression method %d, not deflate", (int)r.arg0); break;
+    case CK_INF_ZLIB_WINDOW: refuse(msg, "zlib header: window size code %d", (int)r.arg0); break;
+    case CK_INF_ZLIB_DICT: refuse(msg, "zlib header: a preset dictionary"); break;
+    case CK_INF_BLOCK_ENDS: refuse(msg, "the deflate data ends before a block header"); break;
+    case CK_INF_BLOCK_TYPE3: refuse(msg, "deflate block type 3"); break;
+    case CK_INF_STORED_LENS_END: refuse(msg, "the data ends inside a stored block's lengths"); break;
+    case CK_INF_STORED_LENS: refuse(msg, "stored block: LEN %u and NLEN %u do not agree", r.arg0, r.arg1); break;
+    case CK_INF_STORED_ENDS: refuse(msg, "the data ends inside a stored block"); break;
+    case CK_INF_DYN_ENDS: refuse(msg, "the data ends inside a dynamic block's header"); break;
+    case CK_INF_DYN_COUNTS: refuse(msg, "dynamic block: %u literal/length codes, %u distance codes", r.arg0, r.arg1); break;
+    case CK_INF_CL_ENDS: refuse(msg, "the data ends inside the code-length code"); break;
+    case CK_INF_CL_NONE: case CK_INF_CL_OVER: case CK_INF_CL_INCOMPLETE: case CK_INF_CL_ROOM:
+        refuse(msg, "code-length code: %s", BUILD[r.cause - CK_INF_CL_NONE]); break;
+    case CK_INF_CLSYM: refuse(msg, "invalid code-length code or the data ends inside one"); break;
+    case CK_INF_REPEAT_FIRST: refuse(msg, "code-length repeat with nothing before it"); break;
+    case CK_INF_REPEAT_ENDS: refuse(msg, "the data ends inside a code-length repeat"); break;
+    case CK_INF_REPEAT_PAST: refuse(msg, "code-length repeat past the last code"); break;
+    case CK_INF_NO_EOB: refuse(msg, "dynamic block without an end-of-block code"); break;
+    case CK_INF_LIT_NONE: case CK_INF_LIT_OVER: case CK_INF_LIT_INCOMPLETE: case CK_INF_LIT_ROOM:
+        refuse(msg, "literal/length code: %s", BUILD[r.cause - CK_INF_LIT_NONE]); break;
+    case CK_INF_DIST_NONE: case CK_INF_DIST_OVER: case CK_INF_DIST_INCOMPLETE: case CK_INF_DIST_ROOM:
+        refuse(msg, "distance code: %s", BUILD[r.cause - CK_INF_DIST_NONE]); break;
+    case CK_INF_TOK_LITLEN: case CK_INF_TOK_LITLEN_SYMBOL: case CK_INF_TOK_LENGTH_ENDS: case CK_INF_TOK_DIST: case CK_INF_TOK_DIST_SYMBOL:
+    case CK_INF_TOK_DIST_ENDS: case CK_INF_TOK_FAR:
+        refuse(msg, "%s (after %zu bytes)", TOKEN[r.cause - CK_INF_TOK_LITLEN], (size_t)r.produced); break;
+    case CK_INF_ADLER_ENDS: refuse(msg, "the zlib stream ends before its Adler-32"); break;
+    case CK_INF_ADLER: refuse(msg, "Adler-32 %08x where the data has %08x", r.arg0, r.arg1); break;
+    case CK_INF_ROWS_SHORT:
+        refuse(msg, "IDAT data too short: %zu bytes where %d rows of 1 + %lld need %zu", (size_t)r.produced, h, rowbytes, need); break;
+    case CK_INF_ROW_FILTER: refuse(msg, "row %d: filter type %d", (int)r.arg0, (int)r.arg1); break;
+    default: refuse(msg, "inflate cause %d", r.cause); break;
+    }
+}
+
+namespace {
+
+// what a wave of the kernel keeps in LDS and in registers
+struct Staged {
+    uint8_t ring[CK_INF_RING];
+    uint16_t lit[CK_INF_LIT_CAP], dist[CK_INF_DIST_CAP], cl[CK_INF_CL_CAP];
+    uint8_t lens[320];
+    CkInfAdlerWork aw;
+    uint64_t tok[CK_INF_WINDOW];
+    uint32_t q[CK_INF_WINDOW];
+    uint8_t* out = nullptr;
+    uint64_t cap = 0, need = 0, pitch = 0;
+    uint64_t produced = 0, flushed = 0;
+    uint32_t A = 1, B = 0;
+    int64_t bad_row = -1;
+    uint32_t bad_type = 0;
+
+    // positions [flushed, to), at most CK_INF_FLUSH of them, leave the ring
+    void flush(uint64_t to)
+    {
+        const int L = (int)(to - flushed);
+        for (int t = 0; t < ck_inf_chunk_tiles(L); t++) {
+            const int left = L - t * CK_PNG_TILE_BYTES;
+            ck_inf_tile_pair(ring, flushed + (uint64_t)t * CK_PNG_TILE_BYTES, left < CK_PNG_TILE_BYTES ? left : CK_PNG_TILE_BYTES, &aw.a[1 + t], &aw.b[1 + t]);
+        }
+        ck_inf_adler_chunk(&aw, L, &A, &B);
+        for (uint64_t p = flushed; p < to && p < cap; p++) out[p] = ring[p & (CK_INF_RING - 1)];
+        if (pitch && bad_row < 0) bad_row = ck_inf_row_check(ring, flushed, to, need, pitch, 0, 1, &bad_type);
+        flushed = to;
+    }
+    void drain()
+    {
+        while (produced - flushed >= (uint64_t)CK_INF_FLUSH) flush(flushed + CK_INF_FLUSH);
+    }
+};
+
+void staged_run(const CkInfIn& in, Staged& s, CkInfRecord* rec)
+{
+    *rec = CkInfRecord();
+    rec->cause = ck_inf_wrapper(in, &rec->arg0);
+    if (rec->cause) return;
+    rec->arg0 = 0;
+    const uint64_t bits = ck_inf_bits(in);
+    uint64_t pos = 16;
+    for (int last = 0; !last;) {
+        CkInfBlock b;
+        ck_inf_block(in, pos, s.lit, s.dist, s.cl, s.lens, &b);
+        if (b.cause) { rec->cause = b.cause; rec->arg0 = b.arg0; rec->arg1 = b.arg1; rec->produced = (int64_t)s.produced; return; }
+        last = b.last;
+        pos = b.pos;
+        if (b.type == 0) {                                   // a stored block, a piece of the ring at a time
+            for (uint32_t done = 0; done < b.stored;) {
+                const uint32_t m = b.stored - done < (uint32_t)CK_INF_STEP_BYTES ? b.stored - done : (uint32_t)CK_INF_STEP_BYTES;
+                for (uint32_t i = 0; i < m; i++) s.ring[(s.produced + i) & (CK_INF_RING - 1)] = in.z[(pos >> 3) + done + i];
+                s.produced += m; done += m;
+                s.drain();
+            }
+            pos += (uint64_t)b.stored * 8;
+            continue;
+        }
+        for (;;) {                                           // window steps
+            for (int o = 0; o < CK_INF_WINDOW; o++)
+                s.tok[o] = ck_inf_token(ck_inf_peek(in, pos + (uint64_t)o), (int64_t)(bits - pos) - o, s.lit, s.dist);
+            CkInfWalk w;
+            ck_inf_walk([&](uint32_t o) { return s.tok[o]; }, [&](uint32_t o, uint32_t at) { s.q[o] = at; }, s.produced, CK_INF_WINDOW, &w);
+            const uint64_t n = s.produced;
+            if (!w.far)
+                for (int o = 0; o < CK_INF_WINDOW; o++)
+                    if ((w.taken[o >> 6] >> (o & 63) & 1) && ck_inf_kind(s.tok[o]) == CK_INF_LITERAL)
+                        s.ring[(n + s.q[o]) & (CK_INF_RING - 1)] = (uint8_t)ck_inf_val(s.tok[o]);
+            for (int o = 0; o < CK_INF_WINDOW; o++) {
+                if (!(w.taken[o >> 6] >> (o & 63) & 1)) continue;
+                const uint64_t at = n + s.q[o], v = ck_inf_val(s.tok[o]);
+                if (ck_inf_kind(s.tok[o]) == CK_INF_LITERAL) {
+                    if (w.far) s.ring[at & (CK_INF_RING - 1)] = (uint8_t)v;
+                    continue;
+                }
+                for (uint32_t i = 0, len = ck_inf_len(s.tok[o]); i < len; i++)
+                    s.ring[(at + i) & (CK_INF_RING - 1)] = s.ring[(at - v + i % v) & (CK_INF_RING - 1)];
+            }
+            s.produced += w.bytes; pos += w.advance;
+            rec->steps++; rec->tokens += w.tokens;
+            s.drain();
+            if (w.end == CK_INF_REFUSED) { rec->cause = (int32_t)w.cause; rec->produced = (int64_t)s.produced; return; }
+            if (w.end == CK_INF_EOB) break;
+        }
+    }
+    if (s.produced > s.flushed) s.flush(s.produced);
+    rec->produced = (int64_t)s.produced;
+    const uint64_t tail = (pos + 7) >> 3;
+    if (in.bytes - tail < 4) { rec->cause = CK_INF_ADLER_ENDS; return; }
+    const uint32_t want = be32(in.z + tail), got = s.B << 16 | s.A;
+    if (want != got) { rec->cause = CK_INF_ADLER; rec->arg0 = want; rec->arg1 = got; return; }
+    if (!s.pitch) return;
+    if (s.produced < s.need) { rec->cause = CK_INF_ROWS_SHORT; return; }
+    if (s.bad_row >= 0) { rec->cause = CK_INF_ROW_FILTER; rec->arg0 = (uint32_t)s.bad_row; rec->arg1 = s.bad_type; }
+}
+
+}  // namespace
+
+int ck_png_unzip_staged_rows(const uint8_t* z, size_t zlen, uint8_t* out, size_t cap, size_t* total, CkInfRecord* record, char* msg, int h, long long rowbytes)
+{
+    *total = 0;
+    std::vector<Staged> st(1);
+    Staged& s = st[0];
+    s.out = out; s.cap = out ? cap : 0;
+    if (h > 0) { s.pitch = (uint64_t)(1 + rowbytes); s.need = (uint64_t)h * s.pitch; }
+    CkInfIn in;
+    in.z = z; in.bytes = z ? zlen : 0;
+    CkInfRecord rec;
+    staged_run(in, s, &rec);
+    if (!z) rec.arg0 = (uint32_t)zlen;
+    if (record) *record = rec;
+    ck_png_inflate_message(rec, h, rowbytes, msg);
+    if (rec.cause) return CK_ERR_DATA;
+    *total = (size_t)rec.produced;
+    return CK_OK;
+}
+
+int ck_png_unzip_staged(const uint8_t* z, size_t zlen, uint8_t* out, size_t cap, size_t* total, CkInfRecord* record, char* msg)
+{
+    return ck_png_unzip_staged_rows(z, zlen, out, cap, total, record, msg, 0, 0);
 }
 
 // ---- writing ----

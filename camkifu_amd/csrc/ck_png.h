@@ -37,6 +37,15 @@ int ck_png_unzip(const uint8_t* z, size_t zlen, uint8_t* out, size_t cap, size_t
 // the filtered rows of a walked file -> rows (hd.inflated() bytes); refuses a short stream and a filter byte above 4
 int ck_png_rows(const CkPngHead& hd, uint8_t* rows, char* msg);
 
+// The same inflate through the steps of ck_png_inflate_stage.h in plain loops, in the order the kernel of k_png_inflate.hip
+// runs them: the same bytes, status and message as ck_png_unzip for every input.  record (nullable) receives the verdict.
+struct CkInfRecord;
+int ck_png_unzip_staged(const uint8_t* z, size_t zlen, uint8_t* out, size_t cap, size_t* total, CkInfRecord* record, char* msg);
+// with h > 0 the two checks of ck_png_rows follow the inflate: h rows of 1 + rowbytes bytes, filter bytes up to 4
+int ck_png_unzip_staged_rows(const uint8_t* z, size_t zlen, uint8_t* out, size_t cap, size_t* total, CkInfRecord* record, char* msg, int h, long long rowbytes);
+// a verdict record -> the text ck_png_unzip / ck_png_rows give for it (h, rowbytes: for the two causes of ck_png_rows)
+void ck_png_inflate_message(const CkInfRecord& r, int h, long long rowbytes, char* msg);
+
 // ---- writing ----
 // a whole file around a zlib stream of zlen bytes: signature, IHDR (8-bit RGB), one IDAT, IEND
 constexpr size_t CK_PNG_CONTAINER = 8 + 25 + 12 + 12;

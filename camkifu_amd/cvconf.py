@@ -21,6 +21,7 @@ sfinders = [
     ("None", "None"),
 ]
 snapshot_dir = "."                          # where VManagerBase.snapshot writes snapshot-N.npy (or .jpg) / game-N.sgf
+png_inflate = "host"                        # ImageCapture, read_pngs: where PNG files are inflated ("device": a wave per file on the GPU, for batches)
 png_runs = False                            # VManagerBase.snapshot_png: the PNG encoder's runs mode (flat areas as deflate matches)
 bf_loc = None
 sf_loc = None

@@ -336,6 +336,31 @@ int ck_png_run_stats(ck_ctx* ctx, int n, long long* literals, long long* matches
 /* the seams of the PNG kernels: rows of an encoder band, bytes of its bit-packing tile, bytes of the unfilter kernel's chunk,
  * rows of its workgroup */
 int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, int32_t* group_rows);
+/* The device inflate, on request: one wave per zlib stream decodes, for every bit offset of a window, the token that would
+ * start there, follows the chain of real tokens, and applies them to a ring of 32768 bytes in LDS, from which the inflated
+ * rows go to where the unfilter kernel reads them; only the zlib streams go up.  It accepts and refuses the same files as
+ * the host mode, with the same frame, message and pixels.  A single stream can use one wave only: the mode is for batches. */
+enum { CK_PNG_INFLATE_HOST = 0, CK_PNG_INFLATE_DEVICE = 1 };
+/* where ck_png_decode inflates from now on; a new context has CK_PNG_INFLATE_HOST */
+int ck_png_set_inflate(ck_ctx* ctx, int mode);
+/* host only: ck_png_inflate through the steps of the device inflate in plain loops, in the kernel's order: the same bytes,
+ * status and message.  h > 0: the stream holds h rows of 1 + rowbytes bytes, and the two checks of the PNG reader (enough
+ * bytes, filter bytes up to 4) follow.  cause (nullable): 0 or the cause of the refusal; produced (nullable): the bytes
+ * inflated, for a refused stream those in front of what was refused */
+int ck_png_inflate_staged(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total, int h, long long rowbytes,
+                          int32_t* cause, long long* produced);
+/* the inflate kernel alone on n zlib streams in HOST memory: the first cap[f] bytes of stream f go to out + f * stride (HOST
+ * memory), total[f] counts all of them (0 for a refused stream), cause[f] and produced[f] are those of ck_png_inflate_staged.
+ * A refused stream does not fail the call; nothing is written to out for it */
+int ck_png_inflate_device(ck_ctx* ctx, const uint8_t* const* z, const size_t* zlen, int n, uint8_t* out, const size_t* cap, size_t stride,
+                          size_t* total, int32_t* cause, long long* produced);
+/* the bytes the last ck_png_decode of this context copied to the device, all passes, in either mode */
+int ck_png_uploaded_bytes(ck_ctx* ctx, long long* bytes);
+/* the last ck_png_decode in device mode or ck_png_inflate_device of this context: stats[0] streams, [1] window steps,
+ * [2] tokens (literals and matches), [3] bytes produced */
+int ck_png_inflate_stats(ck_ctx* ctx, long long* stats);
+/* the seams of the inflate kernel: the bit offsets of a window step, the bytes that leave the ring at a time */
+int ck_png_inflate_geometry(int32_t* window_bits, int32_t* flush_bytes);
 
 /* ---- overlays: the finders' debug drawing (cv2.line / circle / rectangle / putText)   core/imgutil.py:71-118,
  * board/boardfinder.py:121-134, stone/stonesfinder.py:779-885, core/video.py:223-271

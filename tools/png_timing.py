@@ -16,6 +16,13 @@ Images: goban images (380 x 380: camkifu_amd/synth.py scenes through the perspec
    list, 1080p synth frames and an all-zero 1080p frame; kernel time per frame of every step (png_edges and png_join among
    them); png_encode frames/s at 1, 8 and 32 frames a call.
    (Without --runs a `runs` section the output file already holds is kept and marked `carried_over`.)
+6b. --inflate: the section `device_inflate`, measured alone (the rest of the output file stays): png_decode with the device
+   inflate beside the host inflate (16 threads), a round of the one after a round of the other.  Files as png_encode writes
+   them in its default and runs modes, and the same filtered rows deflated by zlib level 6.  Kernel time of png_inflate per
+   image at 1, 8, 32 and 128 images a call, tokens per window step, bytes per microsecond per wave; png_decode frames/s and
+   bytes uploaded per frame in both modes.  --inflate-variant NAME files the kernel legs of another build of the library,
+   loaded through CK_HIP_LIB (-DCK_PNG_INFLATE_OPL=2 or 4: offsets a lane; -DCK_PNG_INFLATE_SERIAL=1: only lane 0 decodes,
+   one token a step), each beside this build's figure for the same leg; --inflate-sizes / --inflate-batches narrow the legs.
 7. --baseline FILE: FILE is what another build's run of this tool wrote, the parent commit's for instance.  The default
    mode's medians of this run (sections 3 and 4, and the `none` legs of the runs section) are listed against the baseline's
    [min .. max], each with `inside` and the distance of the medians in per cent, and the baseline's figures are copied beside
@@ -174,6 +181,78 @@ def _runs_section(ctx, dev, small, big, reps):
     return res
 
 
+def _rewrap(data, level):
+    """the file with the same filtered rows deflated by zlib at `level`: matches at real distances"""
+    import struct
+    at = data.index(b"IDAT")
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+    return data[:at - 4] + chunk(b"IDAT", zlib.compress(zlib.decompress(_idat(data)), level)) + chunk(b"IEND", b"")
+
+
+INFLATE_BATCHES = (1, 8, 32, 128)
+
+
+def _inflate_kernel(ctx, dev, files, b, reps):
+    """HIP-event time of png_inflate and the kernel's own counts for b files a call"""
+    fl = [files[i % len(files)] for i in range(b)]
+    ctx.png_decode(fl, to_device=dev, inflate="device")
+    ctx.timing_enable(True)
+    ms, launches = [], 1
+    for _ in range(reps):
+        ctx.timing_reset()
+        ctx.png_decode(fl, to_device=dev, inflate="device")
+        t, launches = ctx.timing_get("png_inflate")
+        ms.append(t / b)
+    ctx.timing_enable(False)
+    st = ctx.png_inflate_stats()
+    per_launch_us = float(np.median(ms)) * b / max(1, launches) * 1e3
+    return dict(kernel_ms_per_image=spread_of(ms), launches_a_call=int(launches), tokens_per_step=round(st["tokens"] / max(1, st["steps"]), 2),
+                bytes_per_us_per_wave=round(st["bytes"] / b / per_launch_us, 2))
+
+
+def _inflate_section(ctx, dev, small, big, reps, kernel_only=False, sizes=("380x380", "1920x1080"), batches=INFLATE_BATCHES):
+    """the device inflate beside the host inflate, in this process and in alternating rounds"""
+    from camkifu_amd import capi
+    res = dict(geometry=capi.png_inflate_geometry(), contents={},
+               note="encoder_default / encoder_runs: files of png_encode in its two modes; zlib_level_6: the same filtered rows deflated by zlib "
+                    "level 6.  kernel_ms_per_image: HIP-event time of png_inflate over the images of a call, which run side by side, a wave "
+                    "each.  bytes_per_us_per_wave: the bytes of one image over the time of one launch.  variants: the kernel legs of other builds "
+                    "(-DCK_PNG_INFLATE_OPL=2 / 4: offsets a lane; -DCK_PNG_INFLATE_SERIAL=1: only lane 0 decodes, one token a step), "
+                    "each with its kernel time over this build's (`over_main`).  Frames are left in HBM (to_device) in both modes.")
+    for size, frames in (("380x380", small[:32]), ("1920x1080", big[:8])):
+        if size not in sizes:
+            continue
+        default = ctx.png_encode(frames.contiguous(), runs=False)
+        sets = {"encoder_default": default, "encoder_runs": ctx.png_encode(frames.contiguous(), runs=True), "zlib_level_6": [_rewrap(d, 6) for d in default]}
+        for name, files in sets.items():
+            if not np.array_equal(ctx.png_decode(files[:2], inflate="device"), ctx.png_decode(files[:2], inflate="host")):
+                raise SystemExit("device inflate: %s %s differs from the host mode" % (size, name))
+            leg = dict(file_bytes=int(np.mean([len(d) for d in files])), kernel={}, png_decode_frames_per_s={}, uploaded_bytes_per_frame={})
+            for b in batches:
+                leg["kernel"]["%d_images_a_call" % b] = _inflate_kernel(ctx, dev, files, b, reps)
+            for b in (() if kernel_only else batches):
+                fl = [files[i % len(files)] for i in range(b)]
+                fps, calls = {"host": [], "device": []}, {}
+                for m in fps:
+                    t0 = time.perf_counter()
+                    ctx.png_decode(fl, to_device=dev, inflate=m)
+                    calls[m] = max(1, min(64 // b if b < 64 else 1, int(0.4 / max(1e-6, time.perf_counter() - t0))))
+                    leg["uploaded_bytes_per_frame"][m] = int(ctx.png_uploaded_bytes() / b)
+                for _ in range(reps):
+                    for m in fps:
+                        t0 = time.perf_counter()
+                        for _ in range(calls[m]):
+                            ctx.png_decode(fl, to_device=dev, inflate=m)
+                        fps[m].append(b * calls[m] / (time.perf_counter() - t0))
+                leg["png_decode_frames_per_s"]["%d_frames_a_call" % b] = {
+                    m: dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1), rounds=len(v), calls_a_round=calls[m]) for m, v in fps.items()}
+            res["contents"].setdefault(size, {})[name] = leg
+            print("device_inflate: %s %s done" % (size, name), file=sys.stderr, flush=True)
+    return res
+
+
 def _against_baseline(out, base):
     """the default mode's medians of this run -- sections 3 and 4, measured by the same loops as the baseline's, and the
     `none` legs of the runs section -- against the baseline's [min .. max] of the same quantity: every figure, whether it lies
@@ -204,6 +283,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--runs", action="store_true", help="add the `runs` section: the runs mode beside the default mode")
+    ap.add_argument("--inflate", action="store_true", help="measure the `device_inflate` section alone: the device inflate beside the host "
+                    "inflate; the other sections of the output file stay as they are")
+    ap.add_argument("--inflate-variant", help="with --inflate: measure the kernel legs alone and file them under device_inflate.variants "
+                    "by this name (a library built with another CK_PNG_INFLATE_OPL, loaded through CK_HIP_LIB)")
+    ap.add_argument("--inflate-batches", default="1,8,32,128", help="with --inflate: the images a call to measure")
+    ap.add_argument("--inflate-sizes", default="380x380,1920x1080", help="with --inflate: the image sizes to measure")
     ap.add_argument("--baseline", help="the file another build's run of this tool wrote (the parent commit's, say): the default "
                     "mode's figures of this run are listed against its spread under `default_mode_against_baseline`")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png_timing.json"))
@@ -223,6 +308,29 @@ def main(argv=None):
             sc = synth.scene(480, 640, seed=synth.SEED + k)
             gobans.append(ctx.warp_perspective(sc["frame"].numpy(), capi.get_perspective_transform(sc["corners"], dst)))
         small = torch.from_numpy(np.stack(gobans)).to(dev)
+        if args.inflate:
+            sec = _inflate_section(ctx, dev, small, big, args.reps, kernel_only=bool(args.inflate_variant), sizes=args.inflate_sizes.split(","),
+                                   batches=tuple(int(b) for b in args.inflate_batches.split(",")))
+            before = {}
+            if os.path.exists(args.out):
+                with open(args.out) as f:
+                    before = json.load(f)
+            if args.inflate_variant:
+                main = before.get("device_inflate", {}).get("contents", {})
+                for size, per in sec["contents"].items():     # the variant's kernel time over the shipped build's, leg by leg
+                    for name, leg in per.items():
+                        ours = main.get(size, {}).get(name, {}).get("kernel", {})
+                        leg["over_main"] = {b: round(k["kernel_ms_per_image"]["median_ms"] / ours[b]["kernel_ms_per_image"]["median_ms"], 2)
+                                            for b, k in leg["kernel"].items() if b in ours}
+                before.setdefault("device_inflate", {}).setdefault("variants", {})[args.inflate_variant] = sec
+            else:
+                before["device_inflate"] = dict(sec, variants=before.get("device_inflate", {}).get("variants", {}), device=out["device"], rounds=args.reps,
+                                                measured="alone, by --inflate: the other sections of this file are from earlier runs of this tool")
+            with open(args.out, "w") as f:
+                json.dump(before, f, indent=1)
+                f.write("\n")
+            print(json.dumps(sec))
+            return before
         sets = {"380x380": small, "1920x1080": big}
         files = {k: ctx.png_encode(v) for k, v in sets.items()}
         out["round_trip_exact"] = {k: bool(np.array_equal(ctx.png_decode(files[k][:4]), sets[k][:4].cpu().numpy())) for k in sets}

@@ -231,6 +231,14 @@ class Context:
         self._chk(lib().ck_timing_get(self._h, name.encode(), C.byref(ms), C.byref(cnt)))
         return ms.value, cnt.value
 
+    def scratch_fill(self, byte):
+        """a testing aid (ck_debug_scratch_fill): every byte of the context's scratch memory becomes `byte`, which must
+        change no later result -> (bytes filled, buffers filled)"""
+        nbytes, nbufs = C.c_longlong(0), C.c_int(0)
+        self._chk(lib().ck_debug_scratch_fill(self._h, int(byte), C.byref(nbytes), C.byref(nbufs)))
+        self._png_frames = 0                     # (the token counters went with the scratch: png_run_stats() is [] again)
+        return int(nbytes.value), int(nbufs.value)
+
     # ---- helpers ---------------------------------------------------------------------------
     @staticmethod
     def _shape(img, cn):

@@ -345,6 +345,51 @@ int ck_timing_get(ck_ctx* ctx, const char* name, double* total_ms, int* launches
     CK_API_END(ctx)
 }
 
+// Overwrite whatever a call may find in scratch memory (include/camkifu_amd.h).  The weight packs, the MOG2 models (their
+// rate staging included: it belongs to the model) and a trainer's w, m, v are state and are not touched; cnn_flag is a
+// flag the split-precision kernels only ever raise, cleared by the host before each batch, and is no scratch either.
+int ck_debug_scratch_fill(ck_ctx* ctx, int byte, long long* bytes_filled, int* buffers_filled)
+{
+    CK_API_BEGIN(ctx)
+    if (byte < 0 || byte > 255) return ck_fail(ctx, CK_ERR_ARG, "fill byte %d: 0 .. 255", byte);
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    long long bytes = 0;
+    int buffers = 0;
+    hipError_t bad = hipSuccess;
+    auto fill = [&](DevBuf& b) {
+        if (!b.p || !b.cap || bad != hipSuccess) return;
+        bad = hipMemsetAsync(b.p, byte, b.cap, ctx->stream);
+        bytes += (long long)b.cap; buffers++;
+    };
+    ck_for_each_scratch(*ctx, fill);
+    // A trainer: what a call writes before it reads it.  g is among them: ck_train_grads / ck_train_step write all twelve
+    // arrays of it (tr_reduce with accumulate = 0 for the first chunk) and ck_train_apply copies all twelve in before
+    // tr_adam reads them; no entry point reads the gradients of an earlier call.
+    for (CkTrainer& tr : ctx->trainers) {
+        if (!tr.alive) continue;
+        DevBuf* const per_call[] = { &tr.g, &tr.lab, &tr.a1, &tr.a2, &tr.p1, &tr.a3, &tr.a4, &tr.p2, &tr.h1, &tr.lg, &tr.dlg, &tr.dh1,
+                                     &tr.dp2, &tr.dz4, &tr.dz3, &tr.dp1, &tr.dz2, &tr.dz1, &tr.part, &tr.lossv, &tr.mask1, &tr.mask2,
+                                     &tr.mask3 };
+        for (DevBuf* b : per_call) fill(*b);
+    }
+    if (bad != hipSuccess) return ck_fail(ctx, CK_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(bad));
+    for (PinBuf* b : { &ctx->host_pinned, &ctx->host_pinned2, &ctx->rec_host }) {
+        if (!b->p || !b->cap) continue;
+        memset(b->p, byte, b->cap);
+        bytes += (long long)b->cap; buffers++;
+    }
+    // the two results that lie in scratch between calls: gone with it
+    ctx->jenc_freq_frames = 0;
+    ctx->jenc_freq_at = 0;
+    ctx->png_tokens.clear();
+    ctx->png_count_frames = 0;
+    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes_filled) *bytes_filled = bytes;
+    if (buffers_filled) *buffers_filled = buffers;
+    return CK_OK;
+    CK_API_END(ctx)
+}
+
 static int check_img(ck_ctx* ctx, const void* p, int n, int h, int w)
 {
     if (!p) return ck_fail(ctx, CK_ERR_ARG, "image pointer is NULL");

@@ -1,6 +1,7 @@
 // ck_common.h -- internal declarations shared by the HIP translation units of libck_hip.so
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -169,6 +170,31 @@ struct ck_ctx {
 
     ~ck_ctx();           // the events; every buffer frees itself, then the stream goes (ck_api.hip)
 };
+
+// Every scratch DevBuf of a context, once.  Scratch carries nothing from one entry-point call to the next, so
+// ck_debug_scratch_fill may overwrite all of it between calls; it is the only user of this list -- teardown needs none,
+// the buffers free themselves.  The weight packs, the MOG2 models and the trainers hold state and are not scratch.
+#define CK_CTX_SCRATCH_BUFS 41
+template <class F>
+void ck_for_each_scratch(ck_ctx& c, F f)
+{
+    DevBuf* const all[] = {
+        &c.in_stage, &c.in_stage2, &c.planes, &c.trange, &c.edges, &c.map, &c.labels, &c.labels2, &c.runs, &c.ghost,
+        &c.misc, &c.bflag, &c.comp, &c.lists, &c.pts, &c.accum, &c.peaks, &c.goban, &c.act0, &c.act1, &c.act2,
+        &c.ybuf, &c.lblbuf, &c.confbuf, &c.rlblbuf, &c.rconfbuf, &c.fgcbuf, &c.out_stage, &c.mats, &c.pyr0, &c.pyr1,
+        &c.rec_stage, &c.harvest, &c.harvest_src, &c.jenc_work, &c.jenc_bits, &c.jenc_pack, &c.jspan,
+        &c.png_work, &c.png_pack, &c.png_inf,
+    };
+    static_assert(sizeof all / sizeof all[0] == CK_CTX_SCRATCH_BUFS, "one entry per scratch buffer");
+    for (DevBuf* b : all) f(*b);
+}
+// The scratch buffers are declared in one block, from in_stage up to the weight packs.  A DevBuf added there changes the
+// size of the block and stops the build here until the list above (or a reason to leave it out) has it too.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(ck_ctx, cnn) - offsetof(ck_ctx, in_stage) == CK_CTX_SCRATCH_BUFS * sizeof(DevBuf),
+              "a DevBuf joined or left the scratch block of ck_ctx: decide about it in ck_for_each_scratch");
+#pragma clang diagnostic pop
 
 extern thread_local std::string g_ck_create_error;
 

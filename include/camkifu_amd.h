@@ -77,6 +77,14 @@ int  ck_timing_reset(ck_ctx* ctx);
 /* name: "median", "canny_nms", "ccl", "hough_vote", "warp", "cnn", ...; returns total ms
  * and number of launches recorded since the last reset */
 int  ck_timing_get(ck_ctx* ctx, const char* name, double* total_ms, int* launches);
+/* A testing aid.  Scratch memory carries nothing from one entry-point call to the next, so overwriting it between calls
+ * must change no result: this call waits for the context's stream, sets every byte of every scratch buffer of the context
+ * (device and pinned host alike, each over its whole capacity) and of the per-call buffers of its live trainers to `byte`
+ * (0 .. 255, else CK_ERR_ARG), and waits again.  The classifier's weights, the MOG2 models and a trainer's weights and Adam
+ * moments are state and stay as they are.  The two results that lie in scratch between calls on purpose are dropped with
+ * it: ck_jpeg_encode_histograms and ck_png_run_stats answer afterwards as before the first encode (CK_ERR_STATE).
+ * bytes_filled / buffers_filled (nullable): how much was overwritten, in how many buffers. */
+int  ck_debug_scratch_fill(ck_ctx* ctx, int byte, long long* bytes_filled, int* buffers_filled);
 
 /* ---- K1  cv2.medianBlur(frame, 15)                              board/bf_auto.py:72 */
 int ck_median15(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space,

@@ -47,6 +47,7 @@ def test_every_export_is_called_with_the_types_the_header_declares():
     assert L.ck_mog2_apply.argtypes[4] is c.c_double
     assert L.ck_jpeg_probe.argtypes[1] is c.c_size_t
     assert L.ck_rng_set.argtypes[1] is c.c_uint64
+    assert list(L.ck_debug_scratch_fill.argtypes) == [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
     assert tuple(L.ck_policy_watch.argtypes[4:6]) == (c.c_double, c.c_longlong)
     harvest = list(L.ck_harvest_patches.argtypes)
     assert harvest.count(c.c_uint32) == 1 and harvest.count(c.c_longlong) == 1

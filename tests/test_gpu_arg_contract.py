@@ -216,6 +216,9 @@ def _model_cases():
     add("train_destroy_bad_handle", lambda e: e.L.ck_train_destroy(e.h, 99), ARG, "bad trainer handle 99")
     add("train_destroy_twice", lambda e: e.L.ck_train_destroy(e.h, e.tr_dead), ARG, "bad trainer handle %d")
     add("timing_get_name_null", lambda e: e.L.ck_timing_get(e.h, None, None, None), ARG, None)
+    add("scratch_fill_null_ctx", lambda e: e.L.ck_debug_scratch_fill(None, 0, None, None), ARG, None)
+    add("scratch_fill_byte_256", lambda e: e.L.ck_debug_scratch_fill(e.h, 256, None, None), ARG, "fill byte 256: 0 .. 255")
+    add("scratch_fill_byte_neg", lambda e: e.L.ck_debug_scratch_fill(e.h, -1, None, None), ARG, "fill byte -1: 0 .. 255")
     return c
 
 

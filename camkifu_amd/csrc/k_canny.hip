@@ -100,6 +100,9 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
         }
     }
     if (thr) { low = thr[2 * f]; high = thr[2 * f + 1]; }
+    // the dword stores of map and edges below need the ADDRESS on a dword, not the index: `edges_zero` may be a caller's
+    // device pointer of any alignment (ck_board_edges, ck_goban_canny, ck_canny).  Off a dword, bytes are stored.
+    const unsigned misaligned = ((unsigned)reinterpret_cast<uintptr_t>(map) | (unsigned)reinterpret_cast<uintptr_t>(edges_zero)) & 3u;
     // pixel tile: columns ox-8 .. ox+71 (20 dwords per row: five 16-byte loads; the gradient needs ox-2 .. ox+65), rows
     // oy-2 .. oy+PTH+1, border replicated.  The candidate buffer of the last phase reuses its space.
     constexpr int LWD = PLWD;
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
                 const int y = oy + (q >> 4), x0 = ox + (q & 15) * 4;
                 if (y >= h) break;
                 const size_t idx = ((size_t)f * h + y) * w + x0;
-                if (x0 + 3 < w && ((idx & 3) == 0)) {
+                if (x0 + 3 < w && ((((unsigned)idx | misaligned) & 3u) == 0)) {
                     *reinterpret_cast<uint32_t*>(map + idx) = 0x01010101u;
                     *reinterpret_cast<uint32_t*>(edges_zero + idx) = 0u;
                 } else {
@@ -303,7 +306,7 @@ __global__ __launch_bounds__(256) void canny_nms_packed_kernel(const uint8_t* __
             const size_t idx = ((size_t)f * h + y) * w + x0;
             // the edge image of the hysteresis pass starts out all zero: cleared here, next to the map store,
             // instead of by a memset of its own
-            if (x0 + 3 < w && ((idx & 3) == 0)) {
+            if (x0 + 3 < w && ((((unsigned)idx | misaligned) & 3u) == 0)) {
                 *reinterpret_cast<uint32_t*>(map + idx) = mapw;
                 *reinterpret_cast<uint32_t*>(edges_zero + idx) = 0u;
             } else {

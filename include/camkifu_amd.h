@@ -42,6 +42,38 @@ enum { CK_BOARD_LINES = 0,        /* lines were searched (n_lines may be 0)     
 
 typedef struct ck_ctx ck_ctx;
 
+/* ---- Alignment of device memory -------------------------------------------------------
+ * An INPUT pointer in CK_DEVICE space may have ANY alignment of its element type: a uint8 image may start at any byte, an
+ * int16 / uint16 array at any even address, an int32 / float array at any multiple of 4 -- a slice frames[1:], a row range
+ * of a byte buffer, a tensor carved out of a pool.  So may these OUTPUTS: the `bgr` of ck_i420_to_bgr, ck_i420_to_bgr_pyr,
+ * ck_jpeg_reconstruct, ck_jpeg_decode and ck_png_decode, the `out` of ck_pyr_down and ck_warp_perspective, the `edges` of
+ * ck_board_edges, ck_goban_canny and ck_canny and the latter's `map_out`.  The kernels pick their wide (dword, 16-byte) forms
+ * by the address where a store needs it and load unaligned elsewhere; the result is the same bytes either way, and for
+ * these arguments no byte in front of or behind them is written.  Every OTHER device output (labels, confidences, masks,
+ * counts, ghost maps, ...) has only ever been run on 16 bytes: keep it there.  (Host pointers go through the context's
+ * staging buffers: no alignment is asked of them.)
+ *
+ * The exceptions, each refused before anything of the caller's is written, with the message ck_last_error gives:
+ *
+ *   entry point                     argument  bytes  refused with
+ *   ck_jpeg_reconstruct             coef      16     CK_ERR_ARG "coefficients and quant tables must lie on 16 bytes"
+ *   ck_jpeg_reconstruct             quant     16     CK_ERR_ARG "coefficients and quant tables must lie on 16 bytes"
+ *   ck_jpeg_coefficients_device     coef      16     CK_ERR_ARG "coefficients and quant tables must lie on 16 bytes"
+ *   ck_jpeg_coefficients_device     quant     16     CK_ERR_ARG "coefficients and quant tables must lie on 16 bytes"
+ *   ck_jpeg_forward                 coef      16     CK_ERR_ARG "coefficients must lie on 16 bytes"
+ *   ck_jpeg_entropy_encode_device   coef      16     CK_ERR_ARG "coefficients must lie on 16 bytes"
+ *   ck_harvest_patches              goban     4      CK_ERR_ARG "goban images in device memory must be 4-byte aligned"
+ *   ck_harvest_patches              x         8      CK_ERR_ARG "x in device memory must be 8-byte aligned, src 4-byte aligned"
+ *   ck_harvest_patches              src       4      CK_ERR_ARG "x in device memory must be 8-byte aligned, src 4-byte aligned"
+ *   ck_augment_patches              x         4      CK_ERR_ARG "patches in device memory must be 4-byte aligned"
+ *   ck_augment_patches              x_out     4      CK_ERR_ARG "patches in device memory must be 4-byte aligned"
+ *   ck_board_detect_records         rec       8      CK_ERR_ARG "records must be 8-byte aligned"
+ *   ck_cnn_regions_records          rec       8      CK_ERR_ARG "records must be 8-byte aligned"
+ *
+ * (the coefficient arrays are read and written 16 bytes at a time, a patch a dword at a time, a record's doubles as
+ * doubles.)  tests/test_gpu_alignment.py holds the inputs and the outputs named above to this at every offset within
+ * 16 bytes. */
+
 typedef struct ck_board_result {
     int32_t status;        /* CK_BOARD_*                                              */
     int32_t n_contours;    /* len(contours) returned by findContours(RETR_EXTERNAL)   */

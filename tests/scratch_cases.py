@@ -7,6 +7,12 @@
     grow(c)     the same entry point on at least twice the frames (and a larger image where it takes a shape): it only
                 leaves the context's buffers larger than the case needs
 
+run takes two things more, for tests/test_gpu_alignment.py: `place`, a function (k, array) -> what the call gets in place of
+argument k of the method's device-capable arguments (numbered as in tests/handover_cases.py; None: the arrays themselves),
+and keywords such as `out=` for the methods that take them.  The rows of HOST_STREAM_ROWS that decode or inflate take
+host streams only: they have no device-capable argument and never call `place` (jpeg_decode_*, jpeg_coefficients_device,
+png_decode_*, png_inflate_device); the three further jpeg_encode rows keep their frames in host memory.
+
 Methods with state: a MOG2 row's case feeds ONE model a long run and then a short one and is compared over the whole
 history; a trainer row takes a fresh handle per run; the cluster row resets the generator.  The classifier rows run the
 exact network "gather" of tests/cnn_exact_cases.py, whose answer is the same bits in every mode, and go through all four
@@ -33,6 +39,11 @@ def expected(name, make):
 class Row:
     def __init__(self, name, run, check, grow):
         self.name, self.run, self.check, self.grow = name, run, check, grow
+
+
+def placed(args, place):
+    """the device-capable arguments of a call as `place` hands them over (None: as they are)"""
+    return list(args) if place is None else [place(k, a) for k, a in enumerate(args)]
 
 
 def _np(a):
@@ -159,7 +170,7 @@ def build(ck, ora):
 
     def of(name):
         """the handover case `name` on its content A"""
-        return lambda c: H[name].run(c, H[name].a)
+        return lambda c, place=None, **kw: H[name].run(c, placed(H[name].a, place), **kw)
 
     def grown(name, *args):
         """the handover case's call on other arguments"""
@@ -286,10 +297,10 @@ def build(ck, ora):
     def encode_row(name, tables, entropy):
         ref = jopt if tables == "optimised" else jenc
 
-        def run(c):
+        def run(c, place=None):
             c.jpeg_set_encode_entropy(entropy)
             try:
-                return c.jpeg_encode(frames_of("jpeg_encode"), quality=85, restart_interval=1, optimize=tables == "optimised")
+                return c.jpeg_encode(placed([frames_of("jpeg_encode")], place)[0], quality=85, restart_interval=1, optimize=tables == "optimised")
             finally:
                 c.jpeg_set_encode_entropy("host")
 
@@ -323,12 +334,12 @@ def build(ck, ora):
         return [jenc.encode(f, 90, jenc.S420, 2) for f in frames]
 
     def decode_row(mode):
-        def run(c):
+        def run(c, place=None, **kw):
             c.jpeg_set_entropy(mode)
             if mode == "device-spans":
                 c.jpeg_set_span_bytes(8)
             try:
-                return c.jpeg_decode(small_jpeg())
+                return c.jpeg_decode(small_jpeg(), **kw)
             finally:
                 c.jpeg_set_entropy("host")
 
@@ -350,7 +361,7 @@ def build(ck, ora):
         for f, (_, cf, q) in enumerate(want):
             _eq(coef[f], np.asarray(cf, np.int16), "coefficients of frame %d" % f)
             _eq(quant[f], np.asarray(q, np.uint16), "quant tables of frame %d" % f)
-    add("jpeg_coefficients_device", lambda c: c.jpeg_coefficients_device(small_jpeg()), check_coefficients,
+    add("jpeg_coefficients_device", lambda c, place=None: c.jpeg_coefficients_device(small_jpeg()), check_coefficients,
         lambda c: c.jpeg_coefficients_device(big_jpeg()[1]))
 
     # ---- PNG ----------------------------------------------------------------------------------------------------------
@@ -368,7 +379,7 @@ def build(ck, ora):
             for f, (data, bgr) in enumerate(small_png()):
                 assert np.array_equal(png_ref.decode(data), bgr)           # (the two statements of the reference agree)
                 _eq(_np(got)[f], bgr, "png_decode %s frame %d" % (inflate, f))
-        add("png_decode_" + inflate, lambda c: c.png_decode([d for d, _ in small_png()], inflate=inflate), check,
+        add("png_decode_" + inflate, lambda c, place=None, **kw: c.png_decode([d for d, _ in small_png()], inflate=inflate, **kw), check,
             lambda c: c.png_decode(big_png(), inflate=inflate))
     png_decode_row("host")
     png_decode_row("device")
@@ -382,7 +393,7 @@ def build(ck, ora):
 
     def png_encode_row(runs):
         name = "png_encode_runs" if runs else "png_encode"
-        add(name, lambda c: c.png_encode(png_frames()[0], runs=runs),
+        add(name, lambda c, place=None: c.png_encode(placed([png_frames()[0]], place)[0], runs=runs),
             lambda got: _eq_list(got, expected(name, lambda: capi.png_encode_staged(png_frames()[0], None, runs=runs)), name),
             lambda c: c.png_encode(png_frames()[1], runs=runs))
     png_encode_row(False)
@@ -398,7 +409,7 @@ def build(ck, ora):
     def check_inflate(got):
         for f, (r, want) in enumerate(zip(got, z_streams()[0])):
             assert (r["cause"], r["total"], r["produced"]) == (0, len(want), len(want)) and r["data"] == want, ("png_inflate_device", f)
-    add("png_inflate_device", lambda c: c.png_inflate_device(z_streams()[1]), check_inflate, lambda c: c.png_inflate_device(z_streams()[2]))
+    add("png_inflate_device", lambda c, place=None: c.png_inflate_device(z_streams()[1]), check_inflate, lambda c: c.png_inflate_device(z_streams()[2]))
 
     # ---- overlays ------------------------------------------------------------------------------------------------------
     def check_overlay(got):
@@ -427,14 +438,16 @@ def build(ck, ora):
                 m[h - 1, :] = 0
             return m.reshape(h // 20, 20, w // 20, 20).sum((1, 3), dtype=np.int32)
 
-        def run(c):
+        def run(c, place=None):
+            def put(a):
+                return placed([np.ascontiguousarray(a)], place)[0]
             hd = c.mog2_create(h, w)
             try:
                 if name == "mog2_apply":
-                    got = [_np(c.mog2_apply(hd, frames[t], rates[t])) for t in range(7)]
+                    got = [_np(c.mog2_apply(hd, put(frames[t]), rates[t])) for t in range(7)]
                 else:
-                    got = list(_np(c.mog2_band_run(hd, frames[long_run], rates[long_run], last_band))) + \
-                        list(_np(c.mog2_band_run(hd, frames[short_run], rates[short_run], last_band)))
+                    got = list(_np(c.mog2_band_run(hd, put(frames[long_run]), rates[long_run], last_band))) + \
+                        list(_np(c.mog2_band_run(hd, put(frames[short_run]), rates[short_run], last_band)))
                 return got, c.mog2_state(hd)
             finally:
                 c.mog2_destroy(hd)
@@ -467,10 +480,11 @@ def build(ck, ora):
     W, gather = exact_net()
     more_gobans = np.concatenate([gather, hc._noise(40, (2, 380, 380, 3)) // 64])
 
-    def with_exact(call):
-        def run(c):
+    def with_exact(call, gobans=gather):
+        def run(c, place=None):
             c.cnn_set_weights(W)
-            return in_every_mode(c, lambda: call(c))
+            g = placed([gobans], place)[0]
+            return in_every_mode(c, lambda: call(c, g))
         return run
 
     def check_modes(check_one):
@@ -485,12 +499,12 @@ def build(ck, ora):
         check_y(y, ref, "cnn_predict " + m)
         _eq(stones, ref["stones"], "cnn_predict stones " + m)
         check_conf(conf, y, "cnn_predict conf " + m, grid=True)
-    add("cnn_predict", with_exact(lambda c: c.cnn_predict(gather)), check_modes(check_predict), with_exact(lambda c: c.cnn_predict(more_gobans)))
+    add("cnn_predict", with_exact(lambda c, g: c.cnn_predict(g)), check_modes(check_predict), with_exact(lambda c, g: c.cnn_predict(g), more_gobans))
 
     def check_maps(got, ref, m):
         for k, a in zip(("pool2", "pool4"), got):
             assert np.array_equal(a.view(np.uint32), _bits(ref[k])), "cnn_maps %s %s: %d elements differ" % (k, m, int((a.view(np.uint32) != _bits(ref[k])).sum()))
-    add("cnn_maps", with_exact(lambda c: c.cnn_maps(gather)), check_modes(check_maps), with_exact(lambda c: c.cnn_maps(more_gobans)))
+    add("cnn_maps", with_exact(lambda c, g: c.cnn_maps(g)), check_modes(check_maps), with_exact(lambda c, g: c.cnn_maps(g), more_gobans))
 
     def check_regions(got, ref, m):
         # the confidences follow from y, which this call does not return: a cnn_predict of the same mode gives it
@@ -498,21 +512,26 @@ def build(ck, ora):
         _eq(_np(rl).reshape(1, 100), ref["labels"], "cnn_regions labels " + m)
         check_y(y, ref, "cnn_regions y " + m)
         check_conf(rc, y, "cnn_regions conf " + m)
-    add("cnn_regions", with_exact(lambda c: tuple(c.cnn_regions(gather)) + (c.cnn_predict(gather)[0],)), check_modes(check_regions),
-        with_exact(lambda c: c.cnn_regions(more_gobans)))
+    add("cnn_regions", with_exact(lambda c, g: tuple(c.cnn_regions(g)) + (c.cnn_predict(g)[0],)), check_modes(check_regions),
+        with_exact(lambda c, g: c.cnn_regions(g), more_gobans))
 
-    def run_set_weights(c):
+    def run_set_weights(c, place=None):
         c.cnn_set_weights(hc.weights(2))                           # another network first: every pack is written again
-        c.cnn_set_weights(W)
+        c.cnn_set_weights(dict(zip(capi.WEIGHT_ORDER, placed([W[k] for k in capi.WEIGHT_ORDER], place))))
         return in_every_mode(c, lambda: tuple(c.cnn_regions(gather)) + (c.cnn_predict(gather)[0],))
     add("cnn_set_weights", run_set_weights, check_modes(check_regions), lambda c: c.cnn_set_weights(hc.weights(3)))
 
-    def run_region_records(c):
+    def run_region_records(c, place=None):
         c.cnn_set_weights(W)
         rec = np.full((1, capi.REC_BYTES), 0xEE, np.uint8)
+        g = placed([gather], place)[0]
 
         def call():
-            return c.cnn_regions_records(gather, rec.copy().view(capi.REC_DTYPE).reshape(1)), c.cnn_predict(gather)[0]
+            rows = rec.copy() if place is None else place(1, rec.copy())       # (a buffer of its own for every mode)
+            rows = rows.view(capi.REC_DTYPE).reshape(1) if isinstance(rows, np.ndarray) else rows
+            got = c.cnn_regions_records(g, rows)
+            assert got is rows
+            return _np(got).view(capi.REC_DTYPE).reshape(1), c.cnn_predict(g)[0]
         return in_every_mode(c, call)
 
     def check_region_records(got, ref, m):
@@ -523,7 +542,7 @@ def build(ck, ora):
         part = np.ascontiguousarray(rec).view(np.uint8).reshape(-1)[:capi.REC_DTYPE.fields["region_conf"][1]]
         assert (part == 0xEE).all() and (rec["pad"] == 0xEE).all()                 # the board half stays as the caller left it
     add("cnn_regions_records", run_region_records, check_modes(check_region_records),
-        with_exact(lambda c: c.cnn_regions_records(more_gobans, np.zeros(3, capi.REC_DTYPE))))
+        with_exact(lambda c, g: c.cnn_regions_records(g, np.zeros(3, capi.REC_DTYPE)), more_gobans))
 
     # ---- the stones path on frames: the warp, then the exact network (and a background model) -------------------------------
     scenes = frames_of("stones_detect")
@@ -532,9 +551,10 @@ def build(ck, ora):
         gobans = expected("warped gobans", lambda: np.stack([ora.warp_perspective(f, hc.M_BOARD, (380, 380)) for f in scenes]))
         return gobans, exact_answer("warped", gobans)
 
-    def run_stones_detect(c):
+    def run_stones_detect(c, place=None):
         c.cnn_set_weights(W)
-        return c.stones_detect(scenes, hc.M_BOARD), c.cnn_predict(c.warp_perspective(scenes, hc.M_BOARD))[0]
+        s = placed([scenes], place)[0]
+        return c.stones_detect(s, hc.M_BOARD), c.cnn_predict(c.warp_perspective(s, hc.M_BOARD))[0]
 
     def check_stones_detect(got):
         (labels, conf), y = got
@@ -548,12 +568,13 @@ def build(ck, ora):
         c.stones_detect(big, hc.M_BOARD)
     add("stones_detect", run_stones_detect, check_stones_detect, grow_stones)
 
-    def run_stones_run(c):
+    def run_stones_run(c, place=None):
         c.cnn_set_weights(W)
+        s = placed([scenes], place)[0]
         hd = c.mog2_create(380, 380)
         try:
-            return (c.stones_run(scenes, hc.M_BOARD, want_grid=True), c.stones_run(scenes, hc.M_BOARD, mog2=hd, learning_rates=[-1.0, 0.05]),
-                    c.cnn_predict(c.warp_perspective(scenes, hc.M_BOARD))[0])
+            return (c.stones_run(s, hc.M_BOARD, want_grid=True), c.stones_run(s, hc.M_BOARD, mog2=hd, learning_rates=[-1.0, 0.05]),
+                    c.cnn_predict(c.warp_perspective(s, hc.M_BOARD))[0])
         finally:
             c.mog2_destroy(hd)
 
@@ -587,11 +608,13 @@ def build(ck, ora):
     x65, y65 = tc.cases()["n65"]
     W0 = tc.weights()
 
-    def on_trainer(call, weights=W0):
-        def run(c):
-            hd = c.train_create(weights)
+    def on_trainer(call, args=(), create_placed=False):
+        """call(c, hd, *args as `place` hands them over); create_placed: the trainer's own weights are the arguments"""
+        def run(c, place=None):
+            a = placed(args, place)
+            hd = c.train_create(dict(zip(tr.ORDER, a)) if create_placed else W0)
             try:
-                return call(c, hd)
+                return call(c, hd) if create_placed else call(c, hd, *a)
             finally:
                 c.train_destroy(hd)
         return run
@@ -603,12 +626,12 @@ def build(ck, ora):
         assert masks is None and abs(loss - l_ref) / abs(l_ref) <= TOL, ("train_grads", loss, l_ref)
         for k, e in tr.grad_error(grads, g_ref).items():
             assert e <= TOL, ("train_grads", k, e)
-    add("train_grads", on_trainer(lambda c, hd: c.train_grads(hd, x3, y3, dropout=False)), check_grads,
+    add("train_grads", on_trainer(lambda c, hd, x: c.train_grads(hd, x, y3, dropout=False), [x3]), check_grads,
         on_trainer(lambda c, hd: c.train_grads(hd, x65, y65, dropout=True, seed=3)))
 
-    def run_step(c, hd):
-        _, grads, _ = c.train_grads(hd, x3, y3, dropout=False)
-        loss = c.train_step(hd, x3, y3, lr=0.001, dropout=False)
+    def run_step(c, hd, x):
+        _, grads, _ = c.train_grads(hd, x, y3, dropout=False)
+        loss = c.train_step(hd, x, y3, lr=0.001, dropout=False)
         return loss, grads, c.train_weights(hd), c.train_adam_state(hd)
 
     def check_adam(w, m, v, steps, grads, what):
@@ -624,19 +647,19 @@ def build(ck, ora):
         loss, grads, w, (m, v, steps) = got
         check_grads((loss, grads, None))
         check_adam(w, m, v, steps, grads, "train_step")
-    add("train_step", on_trainer(run_step), check_step, on_trainer(lambda c, hd: c.train_step(hd, x65, y65, dropout=True, seed=4)))
+    add("train_step", on_trainer(run_step, [x3]), check_step, on_trainer(lambda c, hd: c.train_step(hd, x65, y65, dropout=True, seed=4)))
     given = {k: (np.random.default_rng(41 + i).standard_normal(W0[k].shape) * 1e-2).astype(np.float32) for i, k in enumerate(tr.ORDER)}
 
-    def run_apply(c, hd):
-        c.train_apply(hd, given, lr=0.001)
+    def run_apply(c, hd, *grads):
+        c.train_apply(hd, dict(zip(tr.ORDER, grads)), lr=0.001)
         return c.train_weights(hd), c.train_adam_state(hd)
-    add("train_apply", on_trainer(run_apply), lambda got: check_adam(got[0], got[1][0], got[1][1], got[1][2], given, "train_apply"),
+    add("train_apply", on_trainer(run_apply, [given[k] for k in tr.ORDER]), lambda got: check_adam(got[0], got[1][0], got[1][1], got[1][2], given, "train_apply"),
         on_trainer(lambda c, hd: c.train_grads(hd, x65, y65)))
 
     def check_create(got):
         for k in tr.ORDER:
             assert np.array_equal(_bits(got[k]), _bits(W0[k])), ("train_create", k)
-    add("train_create", on_trainer(lambda c, hd: c.train_weights(hd)), check_create, on_trainer(lambda c, hd: c.train_grads(hd, x65, y65)))
+    add("train_create", on_trainer(lambda c, hd: c.train_weights(hd), [W0[k] for k in tr.ORDER], create_placed=True), check_create, on_trainer(lambda c, hd: c.train_grads(hd, x65, y65)))
 
     # ---- training data ------------------------------------------------------------------------------------------------------
     goban_h, calm_h = H["harvest_patches"].a
@@ -676,9 +699,9 @@ def build(ck, ora):
     mask16 = cr.circle_mask(rects16, cc.SIDE)
     whole = next(c for c in cc.cases() if c[0] == "columns")
 
-    def run_cluster(c):
+    def run_cluster(c, place=None):
         c.rng_state = 0xffffffff
-        return c.cluster_stones(imgs16, rects16, mask16, jobs=jobs16, want_all=True), c.rng_state
+        return c.cluster_stones(placed([imgs16], place)[0], rects16, mask16, jobs=jobs16, want_all=True), c.rng_state
 
     def check_cluster(got):
         from tests.test_gpu_cluster import _same
@@ -699,7 +722,7 @@ def build(ck, ora):
             for g, r in zip(g_map, r_map):
                 pix = set(map(tuple, g["pix"].tolist()))
                 assert len(pix) == len(g["pix"]) and pix == r["pix"], ("contours_external", f, r["start"])
-    add("contours_external", lambda c: c.contours_external(maps, want_points=True), check_contours,
+    add("contours_external", lambda c, place=None: c.contours_external(placed([maps], place)[0], want_points=True), check_contours,
         lambda c: c.contours_external(_edge_maps(4, 144, 200, 6), want_points=True))
     # the goban image of tests/handover_cases.py under noise of +-10 levels: on the synthetic images of tests/stone_cases.py
     # every gradient is far from both thresholds and Canny's map is the same at any Otsu level; here a level one off moves
@@ -714,7 +737,7 @@ def build(ck, ora):
         for key in sorted(set(found) | set(ref["found"])):
             assert found.get(key) == ref["found"].get(key), ("find_intersections", key)
         _eq(grid, ref["grid"], "find_intersections grid")
-    add("find_intersections", lambda c: c.find_intersections(gimg, mtx, rects, want_lines=True), check_grid,
+    add("find_intersections", lambda c, place=None: c.find_intersections(placed([gimg], place)[0], mtx, rects, want_lines=True), check_grid,
         lambda c: c.find_intersections(np.stack([gimg, K.goban_image(3, 4), gimg[::-1].copy()]), mtx, rects))
     return T
 

@@ -2,7 +2,11 @@
 makes before it launches anything -- the error number and a fragment of the message ck_last_error gives.  The calls go
 through ctypes directly, past the checks of capi.Context.  Every pointer that is not NULL points at a buffer large
 enough for the shapes used (2 frames of 8 x 8), so no case hands a kernel a bad pointer even if a check were lost; an
-invalid OUTPUT space is not tested for that reason (the library treats it as device memory, unchecked)."""
+invalid OUTPUT space is not tested for that reason (the library treats it as device memory, unchecked).
+
+The refusals by ALIGNMENT (include/camkifu_amd.h, "Alignment of device memory"; tests/align_cases.REFUSALS) follow the same rule:
+the pointer that is off points into a 1 MiB block of device memory of this file's own, so a lost check hands the kernel a
+valid, merely misaligned pointer."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +17,7 @@ pytestmark = pytest.mark.gpu
 ARG, STATE = 1, 4            # CK_ERR_ARG, CK_ERR_STATE
 HOST, DEV = 0, 1
 BAD_SPACE = 7
+S444 = 1                     # CK_JPEG_444 (Env asserts it)
 
 
 def _p(a):
@@ -46,8 +51,28 @@ class Env:
         self.patches = rng.integers(0, 256, (2, 40, 40, 3), dtype=np.uint8)
         self.lab = np.array([3, 80], np.uint8)
         self.lab_bad = np.array([3, 81], np.uint8)
+        # ---- for the refusals by alignment: device memory of this file's own, and valid arguments around the pointer that is off
+        import torch
+        assert capi.CK_JPEG_444 == S444
+        self.dev_in = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda:0")
+        self.dev_out = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda:0")
+        assert self.dev_in.data_ptr() % 16 == 0 and self.dev_out.data_ptr() % 16 == 0
+        torch.cuda.synchronize()
+        self.quant = np.ascontiguousarray(capi.jpeg_quant(90), np.uint16)
+        self.jpeg_ptrs, self.jpeg_lens, self.jpeg_keep = capi._jpeg_streams([bytes(64), bytes(64)])
+        self.jpeg_geom = capi.JpegInfo(8, 8, S444, 0, capi.jpeg_blocks(8, 8, S444))
+        self.jpeg_stride = capi.jpeg_encode_bound(8, 8, S444)
+        self.jpeg_len = (C.c_size_t * 2)()
+        self.fg = np.zeros((1, 361), np.int32)
+        self.state_of = np.zeros(1, np.int32)
+        self.positions = np.zeros((1, 361), np.uint8)
+        self.found = C.c_int32(0)
+        self.codes = np.array([1, 6], np.uint8)
+        self.ck_net = capi.Context(0)                                     # a second context WITH weights: the records of the classifier
+        self.ck_net.cnn_set_weights(w)
 
     def close(self):
+        self.ck_net.close()
         self.ck.close()
 
 
@@ -222,7 +247,56 @@ def _model_cases():
     return c
 
 
-CASES = _img_cases() + _model_cases()
+def _din(e, off=0):
+    return C.c_void_p(e.dev_in.data_ptr() + off)
+
+
+def _dout(e, off=0):
+    return C.c_void_p(e.dev_out.data_ptr() + off)
+
+
+def _harvest(e, goban, in_space, x, src, out_space):
+    """one goban image, room for two patches; labels at 64 KiB and src from 128 KiB of the output block"""
+    labels = _dout(e, 1 << 16) if out_space == DEV else _p(e.out[1 << 16:])
+    return e.L.ck_harvest_patches(e.h, goban, 1, in_space, _p(e.fg), HOST, _p(e.state_of), _p(e.positions), 1, 16, 256, 0, 0,
+                                  x, labels, src, 2, out_space, C.byref(e.found))
+
+
+def _alignment_cases():
+    """one case per refusal by alignment: everything else about the call is valid"""
+    c = []
+    add = lambda name, fn, frag: c.append((name, fn, ARG, frag))
+    I = lambda e: _p(e.buf)
+    O = lambda e: _p(e.out)
+    Q = lambda e: _p(e.quant)
+    both = "coefficients and quant tables must lie on 16 bytes"
+    add("jpeg_reconstruct_coef_off_16", lambda e: e.L.ck_jpeg_reconstruct(e.h, _din(e, 2), _din(e, 1 << 16), 2, 8, 8, S444, DEV, O(e), HOST), both)
+    add("jpeg_reconstruct_quant_off_16", lambda e: e.L.ck_jpeg_reconstruct(e.h, _din(e), _din(e, (1 << 16) + 8), 2, 8, 8, S444, DEV, O(e), HOST), both)
+    add("jpeg_coefficients_device_coef_off_16",
+        lambda e: e.L.ck_jpeg_coefficients_device(e.h, e.jpeg_ptrs, e.jpeg_lens, 2, C.byref(e.jpeg_geom), _dout(e, 4), _dout(e, 1 << 16), DEV, C.byref(e.found)), both)
+    add("jpeg_coefficients_device_quant_off_16",
+        lambda e: e.L.ck_jpeg_coefficients_device(e.h, e.jpeg_ptrs, e.jpeg_lens, 2, C.byref(e.jpeg_geom), _dout(e), _dout(e, (1 << 16) + 2), DEV, C.byref(e.found)), both)
+    add("jpeg_forward_coef_off_16", lambda e: e.L.ck_jpeg_forward(e.h, I(e), 2, 8, 8, HOST, Q(e), S444, _dout(e, 8), DEV),
+        "coefficients must lie on 16 bytes")
+    add("jpeg_entropy_encode_device_coef_off_16",
+        lambda e: e.L.ck_jpeg_entropy_encode_device(e.h, _din(e, 2), DEV, Q(e), 2, 8, 8, S444, 0, O(e), e.jpeg_stride, e.jpeg_len),
+        "coefficients must lie on 16 bytes")
+    add("harvest_goban_off_4", lambda e: _harvest(e, _din(e, 2), DEV, O(e), _p(e.out[1 << 17:]), HOST),
+        "goban images in device memory must be 4-byte aligned")
+    add("harvest_x_off_8", lambda e: _harvest(e, _p(e.goban), HOST, _dout(e, 4), _dout(e, 1 << 17), DEV),
+        "x in device memory must be 8-byte aligned, src 4-byte aligned")
+    add("harvest_src_off_4", lambda e: _harvest(e, _p(e.goban), HOST, _dout(e), _dout(e, (1 << 17) + 2), DEV),
+        "x in device memory must be 8-byte aligned, src 4-byte aligned")
+    add("augment_x_off_4", lambda e: e.L.ck_augment_patches(e.h, _din(e, 1), 2, DEV, _p(e.codes), O(e), HOST),
+        "patches in device memory must be 4-byte aligned")
+    add("augment_x_out_off_4", lambda e: e.L.ck_augment_patches(e.h, _p(e.patches), 2, HOST, _p(e.codes), _dout(e, 2), DEV),
+        "patches in device memory must be 4-byte aligned")
+    add("board_records_rec_off_8", lambda e: e.L.ck_board_detect_records(e.h, I(e), 2, 8, 8, HOST, -1, _dout(e, 4), DEV),
+        "records must be 8-byte aligned")
+    return c
+
+
+CASES = _img_cases() + _model_cases() + _alignment_cases()
 assert len({c[0] for c in CASES}) == len(CASES)
 
 
@@ -237,6 +311,21 @@ def test_refused_with_its_code_and_message(env, name, call, code, frag):
     if "%d" in frag:
         frag = frag % (env.tr_dead if "trainer" in frag else env.mog_dead)
     assert frag in env.L.ck_last_error(env.h).decode()
+
+
+def test_region_records_refuse_rows_off_8_bytes(env):
+    """k_records_put_regions: reached only with weights, so on the second context; the rows stay as they were"""
+    import torch
+    L, h = env.L, env.ck_net._h
+    env.dev_out.fill_(0xEE)
+    torch.cuda.synchronize()
+    assert L.ck_cnn_regions_records(h, _p(env.goban), 1, HOST, _dout(env, 4), DEV) == ARG
+    assert b"records must be 8-byte aligned" in L.ck_last_error(h)
+    assert bool((env.dev_out == 0xEE).all())
+    assert L.ck_cnn_regions_records(h, _p(env.goban), 1, HOST, _dout(env, 8), DEV) == 0
+    assert not bool((env.dev_out[8:8 + 1440] == 0xEE).all()) and bool((env.dev_out[8 + 1440:] == 0xEE).all())
+    env.dev_out.zero_()
+    torch.cuda.synchronize()
 
 
 def test_create_refusals():

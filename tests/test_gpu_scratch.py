@@ -41,7 +41,6 @@ not kept:
         the codes are OR-ed into dwords of the stream at offsets that come from the scans, not from the stream
         -> test_entry_point_whatever_scratch_holds[png_encode] and [png_encode_runs], test_the_hook_itself"""
 import ctypes as C
-import functools
 import time
 
 import numpy as np
@@ -50,6 +49,7 @@ import pytest
 from tests import scratch_cases as sc
 from tests import train_cases as tc
 from tests import train_ref as tr
+from tests.align_cases import stops_at_a_hip_error
 
 pytestmark = pytest.mark.gpu
 
@@ -73,20 +73,6 @@ def ctx():
     c = capi.Context(0)
     yield c
     c.close()
-
-
-def stops_at_a_hip_error(test):
-    """a HIP error ends the session: nothing more is started on a card that has faulted"""
-    @functools.wraps(test)
-    def run(*args, **kw):
-        from camkifu_amd import capi
-        try:
-            return test(*args, **kw)
-        except capi.CkError as e:
-            if e.code == capi.CK_ERR_HIP:
-                pytest.exit("HIP error, the session ends here: %s" % e, returncode=3)
-            raise
-    return run
 
 
 @pytest.mark.parametrize("name", sc.NAMES)

@@ -36,7 +36,7 @@ the three pixels above the first pixel of a component are background.
 import numpy as np
 import pytest
 
-from . import stone_cases as K, stone_ref as R
+from . import align_cases as ac, stone_cases as K, stone_ref as R
 
 pytestmark = pytest.mark.gpu
 GRID_NAMES = sorted(K.GRID_PATHS)
@@ -73,14 +73,11 @@ def contour_refs(contour_cases):
 
 
 def _dev(a, misalign=0):
-    """a device copy; with `misalign`, one that starts that many bytes past an allocation (a contiguous view)"""
+    """a device copy; with `misalign`, one that starts that many bytes past 16 bytes, between guard bands (tests/align_cases.py)"""
     import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
     if not misalign:
-        return t.cuda()
-    flat = torch.zeros(t.numel() + 16, dtype=torch.uint8, device="cuda")
-    flat[misalign:misalign + t.numel()] = t.reshape(-1).cuda()
-    out = flat[misalign:misalign + t.numel()].view(t.shape)
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    out = ac.place(a, misalign)
     assert out.data_ptr() % 4 == misalign % 4 and out.is_contiguous()
     return out
 
@@ -162,7 +159,10 @@ def test_contours_external_from_an_unaligned_device_pointer(ck, contour_cases, c
     batch = contour_cases[name]
     assert batch.shape[2] % 4 == 0
     for off in (1, 2, 3):
-        _check_contours(ck.contours_external(_dev(batch, misalign=off), want_points=True), contour_refs[name], "%s + %d" % (name, off))
+        maps = _dev(batch, misalign=off)
+        _check_contours(ck.contours_external(maps, want_points=True), contour_refs[name], "%s + %d" % (name, off))
+        ac.untouched(maps)
+        ac.unchanged(maps, batch)
 
 
 def test_contours_external_refusals(ck, contour_cases, contour_refs):

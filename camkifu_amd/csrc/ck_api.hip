@@ -13,13 +13,9 @@
 #include <chrono>
 
 #include "ck_common.h"
+#include "ck_api_util.h"
+#include "ck_stage_layout.h"
 #include "ck_stonegeom.h"
-#include "ck_jpeg.h"
-#include "ck_jpeg_strand.h"
-#include "ck_jpeg_span.h"
-#include "ck_jpeg_enc.h"
-#include "ck_png.h"
-#include "ck_png_inflate_stage.h"
 #include "ck_overlay.h"
 
 thread_local std::string g_ck_create_error;
@@ -88,24 +84,16 @@ int ck_from_device(ck_ctx* ctx, void* dst, const void* dev, size_t bytes, int sp
     return CK_OK;
 }
 
-// The mirror of ck_to_device for a result of `bytes` that the caller wants at `user`: open() gives the device pointer the
-// kernels write -- `user` itself, or `stage` when the caller's memory is the host's -- and deliver() then copies it home.
-// A space other than CK_HOST is taken for device memory, unchecked, as it always was.  A NULL `user` stays NULL.
-template <class T>
-struct OutStage {
-    T* dev = nullptr;
-    T* user = nullptr;
-    size_t bytes = 0;
-    int open(ck_ctx* ctx, T* user_ptr, size_t nbytes, int space, DevBuf& stage)
-    {
-        dev = user_ptr;
-        if (!user_ptr || space != CK_HOST) return CK_OK;
-        CK_TRY(ck_ensure(ctx, stage, nbytes));
-        dev = (T*)stage.p; user = user_ptr; bytes = nbytes;
-        return CK_OK;
-    }
-    int deliver(ck_ctx* ctx) const { return user ? ck_from_device(ctx, user, dev, bytes, CK_HOST) : CK_OK; }
-};
+int ck_coef_on_16(ck_ctx* ctx, const void* coef)
+{
+    if ((uintptr_t)coef & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
+    return CK_OK;
+}
+int ck_coef_quant_on_16(ck_ctx* ctx, const void* coef, const void* quant)
+{
+    if (((uintptr_t)coef | (uintptr_t)quant) & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients and quant tables must lie on 16 bytes");
+    return CK_OK;
+}
 
 // ---- timing ---------------------------------------------------------------------------
 TimeScope::TimeScope(ck_ctx* c, const char* name) : ctx(c)
@@ -398,13 +386,6 @@ static int check_img(ck_ctx* ctx, const void* p, int n, int h, int w)
     return CK_OK;
 }
 
-static int finish(ck_ctx* ctx)
-{
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CK_HIP(ctx, hipGetLastError());
-    return CK_OK;
-}
-
 int ck_median15(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, uint8_t* out, int out_space)
 {
     return ck_median(ctx, bgr, n, h, w, 15, in_space, out, out_space);
@@ -648,1357 +629,6 @@ int ck_i420_to_bgr_pyr(ck_ctx* ctx, const uint8_t* i420, int n, int h, int w, in
     if (levels > 1) CK_TRY(pyr_levels(ctx, d_first, n, h / 2, w / 2, 2, levels, o.dev));
     CK_TRY(o.deliver(ctx));
     return finish(ctx);
-    CK_API_END(ctx)
-}
-
-// ---- baseline JPEG: host half (ck_jpeg.cpp) behind the ABI, and the two calls that reach the GPU ----
-int ck_jpeg_probe(const uint8_t* data, size_t len, ck_jpeg_info* info)
-{
-    if (!info) return ck_fail(nullptr, CK_ERR_ARG, "info is NULL");
-    try {
-        auto f = std::make_unique<CkJpegFrame>();
-        char msg[CK_JPEG_MSG];
-        const int rc = ck_jpeg_parse(data, len, f.get(), msg);
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "%s", msg);
-        *info = f->info;
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-// the Huffman stage of n frames, in parallel: coef n * geom.blocks * 64, quant n * 192.  On failure *bad is the first
-// frame that failed and `why` its message.
-static int jpeg_entropy_batch(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info& geom, int16_t* coef,
-                              uint16_t* quant, int* bad, std::string& why)
-{
-    std::vector<int> rcs((size_t)n, CK_OK);
-    std::vector<std::string> msgs((size_t)n);
-    ck_parallel_for(n, 16, [&](int f) {
-        auto fr = std::make_unique<CkJpegFrame>();
-        char msg[CK_JPEG_MSG];
-        int rc = ck_jpeg_parse(data[f], len[f], fr.get(), msg);
-        if (rc == CK_OK && (fr->info.h != geom.h || fr->info.w != geom.w || fr->info.sampling != geom.sampling)) {
-            snprintf(msg, sizeof msg, "%dx%d sampling %d where the batch is %dx%d sampling %d", fr->info.w, fr->info.h,
-                     fr->info.sampling, geom.w, geom.h, geom.sampling);
-            rc = CK_ERR_DATA;
-        }
-        if (rc == CK_OK) rc = ck_jpeg_entropy(data[f], len[f], *fr, coef + (size_t)f * geom.blocks * 64, msg);
-        if (rc == CK_OK) memcpy(quant + (size_t)f * 192, fr->quant, 192 * sizeof(uint16_t));
-        rcs[f] = rc;
-        if (rc != CK_OK) msgs[f] = msg;
-    });
-    for (int f = 0; f < n; f++)
-        if (rcs[f] != CK_OK) { *bad = f; why = msgs[f]; return rcs[f]; }
-    return CK_OK;
-}
-
-static int check_jpeg_geom(ck_ctx* ctx, int h, int w, int sampling, long long blocks)
-{
-    if (h <= 0 || w <= 0 || h > 65535 || w > 65535) return ck_fail(ctx, CK_ERR_ARG, "bad JPEG frame size %dx%d", w, h);
-    if (sampling < CK_JPEG_GREY || sampling > CK_JPEG_420) return ck_fail(ctx, CK_ERR_ARG, "bad JPEG sampling %d", sampling);
-    if (blocks >= 0 && blocks != ck_jpeg_blocks(h, w, sampling))
-        return ck_fail(ctx, CK_ERR_ARG, "%lld blocks where a %dx%d frame of sampling %d has %lld", blocks, w, h, sampling,
-                       ck_jpeg_blocks(h, w, sampling));
-    if ((long long)h * w > (1LL << 28)) return ck_fail(ctx, CK_ERR_ARG, "image too large");
-    return CK_OK;
-}
-
-int ck_jpeg_coefficients(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
-                         int16_t* coef, uint16_t* quant, int32_t* bad_frame)
-{
-    if (bad_frame) *bad_frame = -1;
-    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
-    try {
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_entropy_batch(data, len, n, *geom, coef, quant, &bad, why);
-        if (rc != CK_OK) {
-            if (bad_frame) *bad_frame = bad;
-            return ck_fail(nullptr, rc, "frame %d: %s", bad, why.c_str());
-        }
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_reconstruct(ck_ctx* ctx, const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling,
-                        int in_space, uint8_t* bgr, int out_space)
-{
-    CK_API_BEGIN(ctx)
-    if (!coef || !quant || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
-    const size_t cbytes = (size_t)n * (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
-    const void *d_coef, *d_quant;
-    CK_TRY(ck_to_device(ctx, coef, cbytes, in_space, ctx->in_stage, &d_coef));
-    CK_TRY(ck_to_device(ctx, quant, (size_t)n * 192 * sizeof(uint16_t), in_space, ctx->in_stage2, &d_quant));
-    if (((uintptr_t)d_coef | (uintptr_t)d_quant) & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients and quant tables must lie on 16 bytes");
-    OutStage<uint8_t> o;
-    CK_TRY(o.open(ctx, bgr, (size_t)n * h * w * 3, out_space, ctx->out_stage));
-    CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)d_coef, (const uint16_t*)d_quant, n, h, w, sampling, o.dev));
-    CK_TRY(o.deliver(ctx));
-    return finish(ctx);
-    CK_API_END(ctx)
-}
-
-// frames per pass of ck_jpeg_decode: the pinned block and its device twin hold the coefficients of one pass, not of the
-// whole batch (a 1080p 4:2:0 frame is 6.2 MB of coefficients, a batch of 256 would pin 1.6 GB) -- 256 MB, or what
-// CK_JPEG_PASS_BYTES says (a developer knob: the tests set it to a few KB to run several passes on small frames)
-static int jpeg_pass_frames(int n, size_t frame_bytes)
-{
-    size_t budget = (size_t)256 << 20;
-    if (const char* e = getenv("CK_JPEG_PASS_BYTES")) {
-        const long long v = atoll(e);
-        if (v > 0) budget = (size_t)v;
-    }
-    const size_t fit = budget / (frame_bytes ? frame_bytes : 1);
-    return fit < 1 ? 1 : (fit < (size_t)n ? (int)fit : n);
-}
-
-// frames per pass in the device entropy mode: the same rule applied to what that mode stages.  Its pinned block and device
-// twin hold the COMPRESSED bytes of a pass (plan rows, table sets and quant tables are small beside them), so the budget
-// buys many more frames -- and the kernel needs them: one lane per strand, so a pass is as fast as its longest strand
-// however many strands it has.  The coefficients of a pass exist in HBM only; they are held to 2 GiB.
-static int jpeg_pass_frames_device(int n, const size_t* len, size_t cframe)
-{
-    size_t sum = 0;
-    for (int f = 0; f < n; f++) sum += len[f];
-    const int fit = jpeg_pass_frames(n, sum / (size_t)n + 192 * sizeof(uint16_t) + 16);
-    const size_t hbm = ((size_t)2 << 30) / (cframe ? cframe : 1);
-    return hbm < 1 ? 1 : (hbm < (size_t)fit ? (int)hbm : fit);
-}
-
-// The Huffman stage of m frames on the GPU (CK_JPEG_ENTROPY_DEVICE), one pass: the plan on the host, then the entropy-coded
-// segments (each starting on 16 bytes, zeroed slack behind the last), the plan rows, the table sets and the quant tables in
-// the context's pinned block -> one upload -> k_jpeg_huff -> the status words down.  d_coef: m * geom.blocks * 64 int16 on
-// the device.  *d_quant: the m * 192 quant tables in HBM (inside in_stage2, 16-byte aligned), h_quant (nullable): the same
-// on the host.  Returns with the stream idle.  On a refusal *bad is the lowest frame with a failed strand (or the frame
-// the planner refused, when no frame before it failed) and `why` the cause at its lowest MCU; a failure that is no frame's
-// fault (HIP, memory) leaves *bad at -1 and its message in the context.
-// span_bytes > 0 (CK_JPEG_ENTROPY_DEVICE_SPANS): the first span of every strand goes up behind the quant tables, the five
-// steps of k_jpeg_span.hip decode, the verdict words come down, and only the frames that hold a suspect strand go through
-// k_jpeg_huff (k_jpeg_huff_frame), whose status words decide as above; every other strand's status is 0.
-static int jpeg_huff_pass(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int m, const ck_jpeg_info& geom,
-                          int16_t* d_coef, const uint16_t** d_quant, uint16_t* h_quant, int* bad, std::string& why, int span_bytes = 0)
-{
-    CkJpegPlan plan;
-    const int prc = ck_jpeg_plan_build(data, len, m, geom, &plan);
-    if (prc != CK_OK && prc != CK_ERR_DATA) { *bad = plan.frames; why = plan.msg; return prc; }
-    const int frames = plan.frames;
-    const size_t ns = plan.strands.size();
-    if (ns > 0x7fffffff) return ck_fail(ctx, CK_ERR_ARG, "%zu strands in one pass", ns);
-    if (ns) {
-        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        std::vector<size_t> seg((size_t)frames);                   // where each frame's entropy-coded segment is staged
-        size_t at = 0;
-        for (int f = 0; f < frames; f++) { seg[f] = at; at = up16(at + (len[f] - plan.scan[f])); }
-        const size_t n_bytes = at + 16;                            // (zeroed slack: a wide load at the last byte stays inside)
-        const size_t rows_at = up16(n_bytes), sets_at = up16(rows_at + ns * sizeof(CkStrand));
-        const size_t quant_at = up16(sets_at + plan.sets.size() * sizeof(CkHuffSet));
-        const size_t span0_at = up16(quant_at + (size_t)frames * 192 * sizeof(uint16_t));
-        const size_t total = span_bytes > 0 ? span0_at + (ns + 1) * sizeof(int32_t) : quant_at + (size_t)frames * 192 * sizeof(uint16_t);
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
-        uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
-        for (int f = 0; f < frames; f++) {
-            const size_t sl = len[f] - plan.scan[f], gap = (f + 1 < frames ? seg[f + 1] : n_bytes) - seg[f] - sl;
-            memcpy(hp + seg[f], data[f] + plan.scan[f], sl);
-            memset(hp + seg[f] + sl, 0, gap);
-        }
-        memset(hp + n_bytes, 0, rows_at - n_bytes);
-        CkStrand* rows = (CkStrand*)(hp + rows_at);
-        for (size_t s = 0; s < ns; s++) {
-            rows[s] = plan.strands[s];
-            const int64_t shift = (int64_t)seg[(size_t)rows[s].frame] - (int64_t)plan.scan[(size_t)rows[s].frame];
-            rows[s].begin += shift;
-            rows[s].end += shift;
-        }
-        memcpy(hp + sets_at, plan.sets.data(), plan.sets.size() * sizeof(CkHuffSet));
-        memcpy(hp + quant_at, plan.quant.data(), (size_t)frames * 192 * sizeof(uint16_t));
-        long long n_spans = 0;
-        if (span_bytes > 0) {
-            memset(hp + quant_at + (size_t)frames * 192 * sizeof(uint16_t), 0, span0_at - (quant_at + (size_t)frames * 192 * sizeof(uint16_t)));
-            int32_t* span0 = (int32_t*)(hp + span0_at);
-            for (size_t s = 0; s < ns; s++) {
-                span0[s] = (int32_t)n_spans;
-                n_spans += ck_span_count(rows[s].end - rows[s].begin, span_bytes);
-                if (n_spans > 0x7fffffff / 8) return ck_fail(ctx, CK_ERR_ARG, "%lld spans in one pass", n_spans);
-            }
-            span0[ns] = (int32_t)n_spans;
-        }
-        const void* d_in;
-        CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage2, &d_in));
-        ctx->jpeg_uploaded += (long long)total;
-        const uint8_t* d = (const uint8_t*)d_in;
-        CK_TRY(ck_ensure(ctx, ctx->misc, ns * sizeof(uint32_t)));
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ns * sizeof(uint32_t)));
-        uint32_t* status = (uint32_t*)ctx->host_pinned2.p;
-        if (span_bytes > 0) {
-            CkSpanJob J{};
-            J.bytes = d; J.n_bytes = (long long)n_bytes;
-            J.rows = (const CkStrand*)(d + rows_at); J.n_strands = (int)ns;
-            J.span0 = (const int32_t*)(d + span0_at);
-            J.sets = (const CkHuffSet*)(d + sets_at); J.n_sets = (int)plan.sets.size();
-            J.g = plan.g; J.cframe = (long long)geom.blocks * 64; J.n_frames = frames; J.span_bytes = span_bytes; J.bpm = ck_span_bpm(plan.g);
-            // the work arrays of the pass, the 8-byte ones first
-            const size_t cand = (size_t)n_spans * (size_t)J.bpm;
-            const size_t a_at = 0, x_at = a_at + cand * 8, e_at = x_at + cand * 8, c_at = e_at + (size_t)n_spans * 8, o_at = c_at + cand * 4;
-            const size_t f_at = o_at + (size_t)n_spans * 4, u_at = f_at + ns * 4, v_at = u_at + ns * 4;
-            CK_TRY(ck_ensure(ctx, ctx->jspan, v_at + ns * 4));
-            uint8_t* wk = (uint8_t*)ctx->jspan.p;
-            J.cand_a = (uint64_t*)(wk + a_at); J.cand_x = (uint64_t*)(wk + x_at); J.entry = (uint64_t*)(wk + e_at);
-            J.cand_c = (uint32_t*)(wk + c_at); J.ord = (int32_t*)(wk + o_at);
-            J.flags = (uint32_t*)(wk + f_at); J.unresolved = (uint32_t*)(wk + u_at); J.verdict = (uint32_t*)(wk + v_at);
-            J.coef = d_coef;
-            CK_TRY(k_jpeg_span(ctx, J, n_spans));
-            CK_HIP(ctx, hipMemcpyAsync(status, J.verdict, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            // the frames that hold a suspect strand (their rows lie together: the plan is frame-major)
-            std::vector<int> first_row((size_t)frames, -1), n_rows((size_t)frames, 0);
-            std::vector<uint8_t> again((size_t)frames, 0);
-            ctx->jpeg_span_stats[0] += n_spans;
-            bool any = false;
-            for (size_t s = 0; s < ns; s++) {
-                const size_t f = (size_t)plan.strands[s].frame;
-                if (first_row[f] < 0) first_row[f] = (int)s;
-                n_rows[f]++;
-                ctx->jpeg_span_stats[1] += status[s] >> 1;
-                if (status[s] & 1) { ctx->jpeg_span_stats[2]++; again[f] = 1; any = true; }
-            }
-            memset(status, 0, ns * sizeof(uint32_t));
-            if (any) {
-                CK_HIP(ctx, hipMemsetAsync(ctx->misc.p, 0, ns * sizeof(uint32_t), ctx->stream));
-                for (int f = 0; f < frames; f++)
-                    if (again[f]) {
-                        ctx->jpeg_span_stats[3]++;
-                        CK_TRY(k_jpeg_huff_frame(ctx, d, (long long)n_bytes, J.rows, first_row[f], n_rows[f], J.sets, J.n_sets, plan.g, J.cframe,
-                                                 frames, f, d_coef, (uint32_t*)ctx->misc.p));
-                    }
-                CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-                CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            }
-        } else {
-            CK_TRY(k_jpeg_huff(ctx, d, (long long)n_bytes, (const CkStrand*)(d + rows_at), (int)ns, (const CkHuffSet*)(d + sets_at),
-                               (int)plan.sets.size(), plan.g, (long long)geom.blocks * 64, frames, d_coef, (uint32_t*)ctx->misc.p));
-            CK_HIP(ctx, hipMemcpyAsync(status, ctx->misc.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        for (size_t s = 0; s < ns; s++)
-            if (status[s]) {
-                char msg[CK_JPEG_MSG];
-                *bad = (int)plan.strands[s].frame;
-                ck_strand_message(status[s], plan.ri[(size_t)*bad], msg);
-                why = msg;
-                return CK_ERR_DATA;
-            }
-        *d_quant = (const uint16_t*)(d + quant_at);
-        if (h_quant) memcpy(h_quant, plan.quant.data(), (size_t)frames * 192 * sizeof(uint16_t));
-    }
-    if (prc != CK_OK) { *bad = plan.frames; why = plan.msg; return prc; }
-    return CK_OK;
-}
-
-int ck_jpeg_set_entropy(ck_ctx* ctx, int mode)
-{
-    CK_API_BEGIN(ctx)
-    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE && mode != CK_JPEG_ENTROPY_DEVICE_SPANS)
-        return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
-    ctx->jpeg_entropy = mode;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_set_span_bytes(ck_ctx* ctx, int bytes)
-{
-    CK_API_BEGIN(ctx)
-    if (bytes < CK_SPAN_MIN || bytes > CK_SPAN_MAX) return ck_fail(ctx, CK_ERR_ARG, "span size %d outside %d .. %d bytes", bytes, CK_SPAN_MIN, CK_SPAN_MAX);
-    ctx->jpeg_span_bytes = bytes;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_span_bytes(int32_t* bytes)
-{
-    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
-    *bytes = CK_SPAN_DEFAULT;
-    return CK_OK;
-}
-
-int ck_jpeg_span_stats(ck_ctx* ctx, long long* stats)
-{
-    CK_API_BEGIN(ctx)
-    if (!stats) return ck_fail(ctx, CK_ERR_ARG, "stats is NULL");
-    for (int i = 0; i < CK_SPAN_STATS; i++) stats[i] = ctx->jpeg_span_stats[i];
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-// in that mode the frame a call refuses is named in the host decoder's words (ck_jpeg_span_host_wording)
-static void jpeg_span_wording(const ck_ctx* ctx, const uint8_t* data, size_t len, const ck_jpeg_info& geom, std::string& why)
-{
-    if (ctx->jpeg_entropy != CK_JPEG_ENTROPY_DEVICE_SPANS) return;
-    char msg[CK_JPEG_MSG] = {0};
-    snprintf(msg, sizeof msg, "%s", why.c_str());
-    ck_jpeg_span_host_wording(data, len, geom, msg);
-    why = msg;
-}
-// the context's span size when its mode decodes inside strands, else 0 (jpeg_huff_pass)
-static int jpeg_ctx_spans(const ck_ctx* ctx) { return ctx->jpeg_entropy == CK_JPEG_ENTROPY_DEVICE_SPANS ? ctx->jpeg_span_bytes : 0; }
-
-int ck_jpeg_coefficients_device(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
-                                int16_t* coef, uint16_t* quant, int out_space, int32_t* bad_frame)
-{
-    CK_API_BEGIN(ctx)
-    if (bad_frame) *bad_frame = -1;
-    ctx->jpeg_bad_frame = -1;
-    ctx->jpeg_uploaded = 0;
-    for (long long& v : ctx->jpeg_span_stats) v = 0;
-    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(ctx, geom->h, geom->w, geom->sampling, geom->blocks));
-    if (out_space != CK_HOST && (((uintptr_t)coef | (uintptr_t)quant) & 15))
-        return ck_fail(ctx, CK_ERR_ARG, "coefficients and quant tables must lie on 16 bytes");
-    const size_t cframe = (size_t)geom->blocks * 64 * sizeof(int16_t), qframe = 192 * sizeof(uint16_t);
-    const int pass = jpeg_pass_frames_device(n, len, cframe);
-    if (out_space == CK_HOST) CK_TRY(ck_ensure(ctx, ctx->in_stage, (size_t)pass * cframe));
-    for (int f0 = 0; f0 < n; f0 += pass) {
-        const int m = n - f0 < pass ? n - f0 : pass;
-        int16_t* d_coef = out_space == CK_HOST ? (int16_t*)ctx->in_stage.p : coef + (size_t)f0 * (cframe / sizeof(int16_t));
-        const uint16_t* d_quant = nullptr;
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, *geom, d_coef, &d_quant, out_space == CK_HOST ? quant + (size_t)f0 * 192 : nullptr,
-                                      &bad, why, jpeg_ctx_spans(ctx));
-        if (rc != CK_OK && bad < 0) return rc;                    // no frame's fault (HIP, memory): the message is stored
-        if (rc != CK_OK) {
-            jpeg_span_wording(ctx, data[f0 + bad], len[f0 + bad], *geom, why);
-            if (bad_frame) *bad_frame = f0 + bad;
-            ctx->jpeg_bad_frame = f0 + bad;
-            (void)hipStreamSynchronize(ctx->stream);
-            return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-        }
-        if (out_space == CK_HOST) {
-            CK_TRY(ck_from_device(ctx, coef + (size_t)f0 * (cframe / sizeof(int16_t)), d_coef, (size_t)m * cframe, CK_HOST));
-        } else {
-            CK_TRY(ck_from_device(ctx, quant + (size_t)f0 * 192, d_quant, (size_t)m * qframe, CK_DEVICE));
-        }
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));            // the next pass stages into the same blocks
-    }
-    return finish(ctx);
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_plan(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
-                 int64_t* strands, long long cap, long long* n_strands, int32_t* n_table_sets, int32_t* bad_frame)
-{
-    if (bad_frame) *bad_frame = -1;
-    if (!data || !len || !geom || !n_strands || !n_table_sets || n <= 0 || cap < 0 || (cap > 0 && !strands))
-        return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer, n <= 0 or cap < 0");
-    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
-    try {
-        CkJpegPlan plan;
-        const int rc = ck_jpeg_plan_build(data, len, n, *geom, &plan);
-        if (rc != CK_OK) {
-            if (bad_frame) *bad_frame = plan.frames;
-            return ck_fail(nullptr, rc, "frame %d: %s", plan.frames, plan.msg);
-        }
-        *n_strands = (long long)plan.strands.size();
-        *n_table_sets = (int32_t)plan.sets.size();
-        if (*n_strands > cap) return ck_fail(nullptr, CK_ERR_CAPACITY, "%lld strands where the array holds %lld", *n_strands, cap);
-        static_assert(sizeof(CkStrand) == 6 * sizeof(int64_t), "a plan row is 6 int64");
-        if (*n_strands) memcpy(strands, plan.strands.data(), plan.strands.size() * sizeof(CkStrand));
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_coefficients_strands(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom,
-                                 int16_t* coef, uint16_t* quant, int32_t* bad_frame)
-{
-    if (bad_frame) *bad_frame = -1;
-    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
-    try {
-        int bad = -1;
-        char msg[CK_JPEG_MSG] = {0};
-        const int rc = ck_jpeg_strands_host(data, len, n, *geom, coef, quant, false, &bad, msg);
-        if (rc != CK_OK) {
-            if (bad_frame) *bad_frame = bad;
-            return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
-        }
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_coefficients_spans(const uint8_t* const* data, const size_t* len, int n, const ck_jpeg_info* geom, int span_bytes,
-                               int16_t* coef, uint16_t* quant, int32_t* bad_frame, long long* stats)
-{
-    if (bad_frame) *bad_frame = -1;
-    if (!data || !len || !geom || !coef || !quant || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    if (span_bytes < CK_SPAN_MIN || span_bytes > CK_SPAN_MAX)
-        return ck_fail(nullptr, CK_ERR_ARG, "span size %d outside %d .. %d bytes", span_bytes, CK_SPAN_MIN, CK_SPAN_MAX);
-    CK_TRY(check_jpeg_geom(nullptr, geom->h, geom->w, geom->sampling, geom->blocks));
-    try {
-        int bad = -1;
-        char msg[CK_JPEG_MSG] = {0};
-        long long st[CK_SPAN_STATS];
-        const int rc = ck_jpeg_spans_host(data, len, n, *geom, span_bytes, coef, quant, &bad, msg, st);
-        if (stats) memcpy(stats, st, sizeof st);
-        if (rc != CK_OK) {
-            if (bad_frame) *bad_frame = bad;
-            return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
-        }
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space)
-{
-    CK_API_BEGIN(ctx)
-    ctx->jpeg_bad_frame = -1;
-    ctx->jpeg_uploaded = 0;
-    for (long long& v : ctx->jpeg_span_stats) v = 0;
-    if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    auto first = std::make_unique<CkJpegFrame>();
-    char msg[CK_JPEG_MSG];
-    const int rc0 = ck_jpeg_parse(data[0], len[0], first.get(), msg);
-    if (rc0 != CK_OK) { ctx->jpeg_bad_frame = 0; return ck_fail(ctx, rc0, "frame 0: %s", msg); }
-    const ck_jpeg_info geom = first->info;
-    CK_TRY(check_jpeg_geom(ctx, geom.h, geom.w, geom.sampling, geom.blocks));
-    const size_t cframe = (size_t)geom.blocks * 64 * sizeof(int16_t), qframe = 192 * sizeof(uint16_t);
-    const size_t oframe = (size_t)geom.h * geom.w * 3;
-    const int pass = jpeg_pass_frames(n, cframe + qframe);
-    OutStage<uint8_t> o;
-    CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
-    if (ctx->jpeg_entropy != CK_JPEG_ENTROPY_HOST) {
-        // per pass: the compressed bytes up, the Huffman kernel, the reconstruct kernel: the coefficients stay in HBM
-        const int pass = jpeg_pass_frames_device(n, len, cframe);
-        CK_TRY(ck_ensure(ctx, ctx->in_stage, (size_t)pass * cframe));
-        for (int f0 = 0; f0 < n; f0 += pass) {
-            const int m = n - f0 < pass ? n - f0 : pass;
-            const uint16_t* d_quant = nullptr;
-            int bad = -1;
-            std::string why;
-            const int rc = jpeg_huff_pass(ctx, data + f0, len + f0, m, geom, (int16_t*)ctx->in_stage.p, &d_quant, nullptr, &bad, why, jpeg_ctx_spans(ctx));
-            if (rc != CK_OK && bad < 0) return rc;                // no frame's fault (HIP, memory): the message is stored
-            if (rc != CK_OK) {
-                jpeg_span_wording(ctx, data[f0 + bad], len[f0 + bad], geom, why);
-                ctx->jpeg_bad_frame = f0 + bad;
-                (void)hipStreamSynchronize(ctx->stream);
-                return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-            }
-            CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)ctx->in_stage.p, d_quant, m, geom.h, geom.w, geom.sampling,
-                                      o.dev + (size_t)f0 * oframe));
-            if (f0 + pass < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        CK_TRY(o.deliver(ctx));
-        return finish(ctx);
-    }
-    // per pass: coefficients, then quant tables, in one pinned block -> one upload -> the kernel.  The stream is waited
-    // for before the next pass decodes into the same block.
-    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, (size_t)pass * (cframe + qframe)));
-    for (int f0 = 0; f0 < n; f0 += pass) {
-        const int m = n - f0 < pass ? n - f0 : pass;
-        const size_t cbytes = (size_t)m * cframe, qbytes = (size_t)m * qframe;
-        int16_t* coef = (int16_t*)ctx->host_pinned.p;
-        uint16_t* quant = (uint16_t*)((uint8_t*)ctx->host_pinned.p + cbytes);
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_entropy_batch(data + f0, len + f0, m, geom, coef, quant, &bad, why);
-        if (rc != CK_OK) {
-            ctx->jpeg_bad_frame = f0 + bad;
-            (void)hipStreamSynchronize(ctx->stream);
-            return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-        }
-        const void* d_in;
-        CK_TRY(ck_to_device(ctx, coef, cbytes + qbytes, CK_HOST, ctx->in_stage, &d_in));
-        ctx->jpeg_uploaded += (long long)(cbytes + qbytes);
-        CK_TRY(k_jpeg_reconstruct(ctx, (const int16_t*)d_in, (const uint16_t*)((const uint8_t*)d_in + cbytes), m, geom.h, geom.w,
-                                  geom.sampling, o.dev + (size_t)f0 * oframe));
-        if (f0 + pass < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    CK_TRY(o.deliver(ctx));
-    return finish(ctx);
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_uploaded_bytes(ck_ctx* ctx, long long* bytes)
-{
-    CK_API_BEGIN(ctx)
-    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
-    *bytes = ctx->jpeg_uploaded;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_bad_frame(ck_ctx* ctx, int32_t* frame)
-{
-    CK_API_BEGIN(ctx)
-    if (!frame) return ck_fail(ctx, CK_ERR_ARG, "frame is NULL");
-    *frame = ctx->jpeg_bad_frame;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-// ---- baseline JPEG encode: the forward kernel (k_jpeg_enc.hip) and the host half (ck_jpeg_enc.cpp) behind the ABI ----
-int ck_jpeg_quant(int quality, uint16_t* quant)
-{
-    if (!quant) return ck_fail(nullptr, CK_ERR_ARG, "quant is NULL");
-    ck_jpeg_enc_quant(quality, quant);
-    return CK_OK;
-}
-
-int ck_jpeg_encode_bound(int h, int w, int sampling, size_t* bytes)
-{
-    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
-    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
-    *bytes = ck_jpeg_enc_bound(h, w, sampling);
-    return CK_OK;
-}
-
-static int check_jpeg_quant(ck_ctx* ctx, const uint16_t* quant)
-{
-    for (int i = 0; i < 192; i++)
-        if (quant[i] < 1 || quant[i] > 255) return ck_fail(ctx, CK_ERR_ARG, "quant entry %d is %d: baseline tables hold 1 .. 255", i, quant[i]);
-    return CK_OK;
-}
-
-static int check_jpeg_out(ck_ctx* ctx, int h, int w, int sampling, int restart_interval, size_t stride)
-{
-    if (restart_interval < 0 || restart_interval > 65535) return ck_fail(ctx, CK_ERR_ARG, "restart interval %d: 0 .. 65535 MCUs", restart_interval);
-    if (stride < ck_jpeg_enc_bound(h, w, sampling))
-        return ck_fail(ctx, CK_ERR_ARG, "output buffer of %zu bytes per frame: smaller than the bound of %zu for a %dx%d frame", stride,
-                       ck_jpeg_enc_bound(h, w, sampling), w, h);
-    return CK_OK;
-}
-
-// the Huffman stage of n frames, in parallel; on failure *bad is the first frame that failed and `why` its message
-static int jpeg_encode_batch(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                             uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why, bool optimise = false)
-{
-    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64;
-    std::vector<int> rcs((size_t)n, CK_OK);
-    std::vector<std::string> msgs((size_t)n);
-    ck_parallel_for(n, 16, [&](int f) {
-        char msg[CK_JPEG_MSG];
-        rcs[f] = (optimise ? ck_jpeg_enc_entropy_opt : ck_jpeg_enc_entropy)(coef + (size_t)f * cframe, quant, h, w, sampling, restart_interval,
-                                                                            out + (size_t)f * stride, stride, len + f, msg);
-        if (rcs[f] != CK_OK) msgs[f] = msg;
-    });
-    for (int f = 0; f < n; f++)
-        if (rcs[f] != CK_OK) { *bad = f; why = msgs[f]; return rcs[f]; }
-    return CK_OK;
-}
-
-int ck_jpeg_forward(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, const uint16_t* quant, int sampling,
-                    int16_t* coef, int out_space)
-{
-    CK_API_BEGIN(ctx)
-    if (!bgr || !quant || !coef || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
-    CK_TRY(check_jpeg_quant(ctx, quant));
-    const void *d_in, *d_quant;
-    CK_TRY(ck_to_device(ctx, bgr, (size_t)n * h * w * 3, in_space, ctx->in_stage, &d_in));
-    CK_TRY(ck_to_device(ctx, quant, 192 * sizeof(uint16_t), CK_HOST, ctx->in_stage2, &d_quant));
-    OutStage<int16_t> o;
-    CK_TRY(o.open(ctx, coef, (size_t)n * (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t), out_space, ctx->out_stage));
-    if ((uintptr_t)o.dev & 15) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
-    CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, n, h, w, sampling, o.dev));
-    CK_TRY(o.deliver(ctx));
-    return finish(ctx);           // (also: the quant tables were read from the caller's memory by the time this returns)
-    CK_API_END(ctx)
-}
-
-// optimised tables count a frame's symbols in 32 bits
-static int check_jpeg_opt_blocks(ck_ctx* ctx, int h, int w, int sampling)
-{
-    if ((long long)ck_jpeg_blocks(h, w, sampling) > (long long)CK_ENC_OPT_MAX_BLOCKS)
-        return ck_fail(ctx, CK_ERR_ARG, "a %dx%d frame has %d blocks: optimised Huffman tables take 2^25", w, h, ck_jpeg_blocks(h, w, sampling));
-    return CK_OK;
-}
-
-static int jpeg_entropy_encode_host(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                                    uint8_t* out, size_t stride, size_t* len, bool optimise)
-{
-    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
-    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
-    if (optimise) CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
-    try {
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_encode_batch(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, why, optimise);
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, why.c_str());
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_entropy_encode(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                           uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_host(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
-}
-
-int ck_jpeg_entropy_encode_opt(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                               uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_host(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
-}
-
-static int jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                                      uint8_t* out, size_t stride, size_t* len, bool optimise)
-{
-    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
-    CK_TRY(check_jpeg_out(nullptr, h, w, sampling, restart_interval, stride));
-    if (optimise) CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
-    try {
-        int bad = -1;
-        char msg[CK_JPEG_MSG] = {0};
-        const int rc = (optimise ? ck_jpeg_enc_staged_opt : ck_jpeg_enc_staged)(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, &bad, msg);
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", bad, msg);
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_entropy_encode_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                                  uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
-}
-
-int ck_jpeg_entropy_encode_opt_staged(const int16_t* coef, const uint16_t* quant, int n, int h, int w, int sampling, int restart_interval,
-                                      uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_staged(coef, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
-}
-
-int ck_jpeg_histogram(const int16_t* coef, int n, int h, int w, int sampling, int restart_interval, uint32_t* counts)
-{
-    if (!coef || !counts || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(nullptr, h, w, sampling, -1));
-    CK_TRY(check_jpeg_opt_blocks(nullptr, h, w, sampling));
-    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64;
-    for (int f = 0; f < n; f++) {
-        char msg[CK_JPEG_MSG];
-        const int rc = ck_jpeg_enc_histogram(coef + (size_t)f * cframe, h, w, sampling, restart_interval, counts + (size_t)f * 4 * 256, msg);
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "frame %d: %s", f, msg);
-    }
-    return CK_OK;
-}
-
-int ck_jpeg_optimal_table(const uint32_t* counts, uint8_t* bits, uint8_t* vals, int32_t* count)
-{
-    if (!counts || !bits || !vals || !count) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    try {
-        ck_jpeg_enc_optimal_table(counts, bits, vals, count);
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_jpeg_set_encode_tables(ck_ctx* ctx, int mode)
-{
-    CK_API_BEGIN(ctx)
-    if (mode != CK_JPEG_TABLES_STANDARD && mode != CK_JPEG_TABLES_OPTIMISED) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG table mode %d", mode);
-    ctx->jpeg_enc_tables = mode;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_encode_histograms(ck_ctx* ctx, int n, uint32_t* counts)
-{
-    CK_API_BEGIN(ctx)
-    if (!counts) return ck_fail(ctx, CK_ERR_ARG, "counts is NULL");
-    if (n <= 0 || n != ctx->jenc_freq_frames) return ck_fail(ctx, CK_ERR_STATE, "the last pass counted %d frames, not %d", ctx->jenc_freq_frames, n);
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CK_HIP(ctx, hipMemcpy(counts, (const uint8_t*)ctx->jenc_work.p + ctx->jenc_freq_at, (size_t)n * 4 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_enc_tiles(int32_t* blocks_per_tile, int32_t* bytes_per_tile)
-{
-    if (!blocks_per_tile || !bytes_per_tile) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    *blocks_per_tile = CK_ENC_TILE_BLOCKS;
-    *bytes_per_tile = CK_ENC_TILE_BYTES;
-    return CK_OK;
-}
-
-int ck_jpeg_set_encode_entropy(ck_ctx* ctx, int mode)
-{
-    CK_API_BEGIN(ctx)
-    if (mode != CK_JPEG_ENTROPY_HOST && mode != CK_JPEG_ENTROPY_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown JPEG entropy mode %d", mode);
-    ctx->jpeg_enc_entropy = mode;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_downloaded_bytes(ck_ctx* ctx, long long* bytes)
-{
-    CK_API_BEGIN(ctx)
-    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
-    *bytes = ctx->jpeg_downloaded;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-// frames per pass in the encoder's device mode: ck_jpeg_encode's rule, the coefficients of a pass held to 2 GiB of HBM
-static int jpeg_enc_pass_frames_device(int n, size_t cframe)
-{
-    const int fit = jpeg_pass_frames(n, cframe);
-    const size_t hbm = ((size_t)2 << 30) / (cframe ? cframe : 1);
-    return hbm < 1 ? 1 : (hbm < (size_t)fit ? (int)hbm : fit);
-}
-
-// The Huffman stage of m frames on the GPU (CK_JPEG_ENTROPY_DEVICE), one pass over coefficients that lie in HBM: size and
-// scan -> 16 bytes down (the lowest block that cannot be coded, the bytes of the bit buffer) -> put, FF counts, lengths ->
-// 8 bytes per frame down -> stuff into the packed buffer -> the streams down in one copy into the pinned block, scattered
-// to out + f * stride from there.  Returns with the stream idle.  On a refusal *bad is the lowest frame that has one and
-// `why` what the host coder says of it; a failure that is no frame's fault leaves *bad at -1, its message in the context.
-// With `optimise` the counters, tables, DHT segments and headers of the frames lie in the work block as well, the header in
-// front of and behind the DHT segments goes up with the constants, and nothing more comes down.
-static int jpeg_enc_huff_pass(ck_ctx* ctx, const int16_t* d_coef, const uint16_t* quant, int m, int h, int w, int sampling,
-                              int restart_interval, uint8_t* out, size_t stride, size_t* len, int* bad, std::string& why, bool optimise)
-{
-    const CkEncGeom g = ck_enc_geom(h, w, sampling, restart_interval);
-    const size_t blocks = (size_t)m * g.blocks, tiles = (size_t)m * g.nseg * g.seg_tiles, segs = (size_t)m * g.nseg;
-    const size_t consts_std = sizeof(CkEncTables) + 64 + CK_JPEG_ENC_HEADER_BOUND;
-    const size_t consts_bytes = consts_std + (optimise ? (size_t)CK_ENC_HEADER_SLOT + 64 : 0);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    // the work block: 64-bit arrays first, then the 32-bit ones, then the constants
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t a = at; at = up16(at + bytes); return a; };
-    const size_t a_head = take(2 * 8), a_tile_off = take(tiles * 8), a_seg_bits = take(segs * 8), a_seg_u0 = take((segs + m) * 8);
-    const size_t a_frame_u0 = take(((size_t)m + 1) * 8), a_len = take((size_t)m * 8), a_out_off = take(((size_t)m + 1) * 8);
-    const size_t a_bits = take(blocks * 4), a_tile_bits = take(tiles * 4), a_consts = take(consts_bytes);
-    const size_t om = optimise ? (size_t)m : 0;
-    const size_t a_freq = take(om * 4 * 256 * 4), a_tables = take(om * sizeof(CkEncTables)), a_dht = take(om * 4 * CK_ENC_DHT_SLOT);
-    const size_t a_dht_len = take(om * 4 * 4), a_headers = take(om * CK_ENC_HEADER_SLOT), a_hlen = take(om * 4);
-    CK_TRY(ck_ensure(ctx, ctx->jenc_work, at));
-    uint8_t* wp = (uint8_t*)ctx->jenc_work.p;
-    CkEncWork wk;
-    wk.head = (uint64_t*)(wp + a_head); wk.tile_off = (uint64_t*)(wp + a_tile_off); wk.seg_bits = (uint64_t*)(wp + a_seg_bits);
-    wk.seg_u0 = (uint64_t*)(wp + a_seg_u0); wk.frame_u0 = (uint64_t*)(wp + a_frame_u0); wk.len = (uint64_t*)(wp + a_len);
-    wk.out_off = (uint64_t*)(wp + a_out_off); wk.bits = (uint32_t*)(wp + a_bits); wk.tile_bits = (uint32_t*)(wp + a_tile_bits);
-    wk.consts = wp + a_consts;
-    ctx->jenc_freq_at = a_freq;
-    ctx->jenc_freq_frames = optimise ? m : 0;
-    if (optimise) {
-        wk.freq = (uint32_t*)(wp + a_freq); wk.tables = wp + a_tables; wk.dht = wp + a_dht; wk.dht_len = (uint32_t*)(wp + a_dht_len);
-        wk.headers = wp + a_headers; wk.hlen = (uint32_t*)(wp + a_hlen);
-        wk.pre = wk.consts + consts_std; wk.post = wk.pre + CK_ENC_HEADER_SLOT;
-    }
-    // pinned: the constants going up, the size words coming down
-    const size_t p_words = up16(consts_bytes);
-    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, p_words + 16 + (size_t)m * 8));
-    uint8_t* hp = (uint8_t*)ctx->host_pinned2.p;
-    memcpy(hp, &ck_jpeg_enc_tables(), sizeof(CkEncTables));
-    memcpy(hp + sizeof(CkEncTables), ck_jpeg_enc_zigzag(), 64);
-    memset(hp + sizeof(CkEncTables) + 64, 0, CK_JPEG_ENC_HEADER_BOUND);
-    const uint32_t hl = (uint32_t)ck_jpeg_enc_headers(quant, h, w, sampling, restart_interval, hp + sizeof(CkEncTables) + 64);
-    if (optimise) {
-        memset(hp + consts_std, 0, (size_t)CK_ENC_HEADER_SLOT + 64);
-        ck_jpeg_enc_header_parts(quant, h, w, sampling, restart_interval, hp + consts_std, &wk.pre_len, hp + consts_std + CK_ENC_HEADER_SLOT, &wk.post_len);
-    }
-    CK_HIP(ctx, hipMemcpyAsync(wp + a_consts, hp, consts_bytes, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t* words = (uint64_t*)(hp + p_words);
-
-    CK_TRY(k_jpeg_enc_measure(ctx, d_coef, m, g, wk));
-    CK_HIP(ctx, hipMemcpyAsync(words, wk.head, 16, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->jpeg_downloaded += 16;
-    if (words[0] != ~(uint64_t)0) {
-        const uint64_t f = words[0] >> 32, b = words[0] & 0xffffffffu;
-        if (f >= (uint64_t)m || b >= (uint64_t)g.blocks) return ck_fail(ctx, CK_ERR_STATE, "the size kernel names block %llu of frame %llu", (unsigned long long)b, (unsigned long long)f);
-        CK_HIP(ctx, hipMemcpyAsync(words, wk.bits + f * (uint64_t)g.blocks + b, 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        char msg[CK_JPEG_MSG];
-        ck_jpeg_enc_status_message(*(const uint32_t*)words, (long long)(b / (uint64_t)g.mcu_blocks), msg);
-        *bad = (int)f;
-        why = msg;
-        return CK_ERR_ARG;
-    }
-    const uint64_t total_u = words[1];
-    const size_t byte_tiles = (size_t)(total_u / CK_ENC_TILE_BYTES);
-    if (!total_u || total_u % CK_ENC_TILE_BYTES) return ck_fail(ctx, CK_ERR_STATE, "a bit buffer of %llu bytes", (unsigned long long)total_u);
-    CK_TRY(ck_ensure(ctx, ctx->jenc_bits, (size_t)total_u + byte_tiles * 8));
-    uint32_t* d_buf = (uint32_t*)ctx->jenc_bits.p;
-    uint32_t* d_ff_cnt = (uint32_t*)((uint8_t*)ctx->jenc_bits.p + total_u);
-    uint32_t* d_ff_off = d_ff_cnt + byte_tiles;
-    CK_TRY(k_jpeg_enc_put(ctx, d_coef, m, g, wk, d_buf, total_u, d_ff_cnt, d_ff_off, hl));
-    CK_HIP(ctx, hipMemcpyAsync(words, wk.len, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->jpeg_downloaded += (long long)m * 8;
-    std::vector<size_t> off((size_t)m + 1, 0);
-    for (int f = 0; f < m; f++) {
-        if (words[f] > stride) return ck_fail(ctx, CK_ERR_STATE, "frame %d: a stream of %llu bytes, above the bound", f, (unsigned long long)words[f]);
-        len[f] = (size_t)words[f];
-        off[(size_t)f + 1] = off[f] + up16(len[f]);
-    }
-    const size_t total = off[m];
-    CK_TRY(ck_ensure(ctx, ctx->jenc_pack, total));
-    CK_TRY(k_jpeg_enc_stuff(ctx, m, g, wk, d_buf, total_u, d_ff_off, hl, (uint8_t*)ctx->jenc_pack.p, total));
-    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
-    CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, ctx->jenc_pack.p, total, hipMemcpyDeviceToHost, ctx->stream));
-    CK_TRY(finish(ctx));
-    ctx->jpeg_downloaded += (long long)total;
-    for (int f = 0; f < m; f++) memcpy(out + (size_t)f * stride, (const uint8_t*)ctx->host_pinned.p + off[f], len[f]);
-    return CK_OK;
-}
-
-static int jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
-                                      int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len, bool optimise)
-{
-    CK_API_BEGIN(ctx)
-    ctx->jpeg_downloaded = 0;
-    if (!coef || !quant || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    if (in_space != CK_HOST && in_space != CK_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "bad memory space %d", in_space);
-    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
-    CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
-    if (optimise) CK_TRY(check_jpeg_opt_blocks(ctx, h, w, sampling));
-    if (in_space == CK_DEVICE && ((uintptr_t)coef & 15)) return ck_fail(ctx, CK_ERR_ARG, "coefficients must lie on 16 bytes");
-    for (int f = 0; f < n; f++) len[f] = 0;
-    char msg[CK_JPEG_MSG];
-    if (ck_jpeg_enc_check(quant, h, w, sampling, restart_interval, msg) != CK_OK) return ck_fail(ctx, CK_ERR_ARG, "frame 0: %s", msg);
-    const size_t cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
-    const int pass = jpeg_enc_pass_frames_device(n, cframe);
-    for (int f0 = 0; f0 < n; f0 += pass) {
-        const int m = n - f0 < pass ? n - f0 : pass;
-        const void* d_coef;
-        CK_TRY(ck_to_device(ctx, coef + (size_t)f0 * (cframe / sizeof(int16_t)), (size_t)m * cframe, in_space, ctx->in_stage, &d_coef));
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)d_coef, quant, m, h, w, sampling, restart_interval, out + (size_t)f0 * stride,
-                                          stride, len + f0, &bad, why, optimise);
-        if (rc != CK_OK && bad < 0) return rc;
-        if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-    }
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_jpeg_entropy_encode_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
-                                  int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_device(ctx, coef, in_space, quant, n, h, w, sampling, restart_interval, out, stride, len, false);
-}
-
-int ck_jpeg_entropy_encode_opt_device(ck_ctx* ctx, const int16_t* coef, int in_space, const uint16_t* quant, int n, int h, int w,
-                                      int sampling, int restart_interval, uint8_t* out, size_t stride, size_t* len)
-{
-    return jpeg_entropy_encode_device(ctx, coef, in_space, quant, n, h, w, sampling, restart_interval, out, stride, len, true);
-}
-
-int ck_jpeg_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int quality, int sampling,
-                   int restart_interval, uint8_t* out, size_t stride, size_t* len)
-{
-    CK_API_BEGIN(ctx)
-    if (!bgr || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_jpeg_geom(ctx, h, w, sampling, -1));
-    CK_TRY(check_jpeg_out(ctx, h, w, sampling, restart_interval, stride));
-    const bool optimise = ctx->jpeg_enc_tables == CK_JPEG_TABLES_OPTIMISED;
-    if (optimise) CK_TRY(check_jpeg_opt_blocks(ctx, h, w, sampling));
-    uint16_t quant[192];
-    ck_jpeg_enc_quant(quality, quant);
-    const size_t iframe = (size_t)h * w * 3, cframe = (size_t)ck_jpeg_blocks(h, w, sampling) * 64 * sizeof(int16_t);
-    ctx->jpeg_downloaded = 0;
-    if (ctx->jpeg_enc_entropy == CK_JPEG_ENTROPY_DEVICE) {
-        // per pass: frames up (when they are the host's) -> the forward kernel -> the entropy kernels: the coefficients stay
-        // in HBM, the streams come down
-        const int pass = jpeg_enc_pass_frames_device(n, cframe);
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, sizeof quant));
-        CK_TRY(ck_ensure(ctx, ctx->out_stage, (size_t)pass * cframe));
-        memcpy(ctx->host_pinned2.p, quant, sizeof quant);
-        const void* d_quant;
-        CK_TRY(ck_to_device(ctx, ctx->host_pinned2.p, sizeof quant, CK_HOST, ctx->in_stage2, &d_quant));
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the pass stages its own words in that pinned block)
-        for (int f0 = 0; f0 < n; f0 += pass) {
-            const int m = n - f0 < pass ? n - f0 : pass;
-            const void* d_in;
-            CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
-            CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, m, h, w, sampling, (int16_t*)ctx->out_stage.p));
-            int bad = -1;
-            std::string why;
-            const int rc = jpeg_enc_huff_pass(ctx, (const int16_t*)ctx->out_stage.p, quant, m, h, w, sampling, restart_interval,
-                                              out + (size_t)f0 * stride, stride, len + f0, &bad, why, optimise);
-            if (rc != CK_OK && bad < 0) return rc;
-            if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-        }
-        return CK_OK;
-    }
-    const int pass = jpeg_pass_frames(n, cframe);
-    // per pass: frames up (when they are the host's) -> the kernel -> the coefficients down in one copy into the pinned
-    // block -> the Huffman coder on the worker threads.  The stream is idle while they code, as in ck_jpeg_decode.
-    // The tables go up from the tail of the pinned block, not from this frame: the copy may outlive an early return.
-    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, (size_t)pass * cframe + sizeof quant));
-    CK_TRY(ck_ensure(ctx, ctx->out_stage, (size_t)pass * cframe));
-    void* pinned_quant = (uint8_t*)ctx->host_pinned.p + (size_t)pass * cframe;
-    memcpy(pinned_quant, quant, sizeof quant);
-    const void* d_quant;
-    CK_TRY(ck_to_device(ctx, pinned_quant, sizeof quant, CK_HOST, ctx->in_stage2, &d_quant));
-    for (int f0 = 0; f0 < n; f0 += pass) {
-        const int m = n - f0 < pass ? n - f0 : pass;
-        const void* d_in;
-        CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
-        CK_TRY(k_jpeg_forward(ctx, (const uint8_t*)d_in, (const uint16_t*)d_quant, m, h, w, sampling, (int16_t*)ctx->out_stage.p));
-        CK_TRY(ck_from_device(ctx, ctx->host_pinned.p, ctx->out_stage.p, (size_t)m * cframe, CK_HOST));
-        CK_TRY(finish(ctx));
-        ctx->jpeg_downloaded += (long long)((size_t)m * cframe);
-        int bad = -1;
-        std::string why;
-        const int rc = jpeg_encode_batch((const int16_t*)ctx->host_pinned.p, quant, m, h, w, sampling, restart_interval,
-                                         out + (size_t)f0 * stride, stride, len + f0, &bad, why, optimise);
-        if (rc != CK_OK) return ck_fail(ctx, rc, "frame %d: %s", f0 + bad, why.c_str());
-    }
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-// ---- PNG: the host half (ck_png.cpp) behind the ABI, and the two calls that reach the GPU (k_png.hip) ----
-static void png_info_of(const CkPngHead& hd, ck_png_info* info)
-{
-    info->h = hd.h; info->w = hd.w; info->color_type = hd.color_type; info->bit_depth = hd.bit_depth;
-    info->palette_entries = hd.palette_n; info->reserved = 0; info->rowbytes = hd.rowbytes;
-}
-
-static int png_host_call(const uint8_t* data, size_t len, ck_png_info* info, bool deep)
-{
-    if (!data || !info) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    try {
-        CkPngHead hd;
-        char msg[CK_PNG_MSG];
-        int rc = ck_png_walk(data, len, &hd, msg);
-        if (rc == CK_OK && deep) {
-            std::vector<uint8_t> rows(hd.inflated());
-            rc = ck_png_rows(hd, rows.data(), msg);
-        }
-        if (rc != CK_OK) return ck_fail(nullptr, rc, "%s", msg);
-        png_info_of(hd, info);
-        return CK_OK;
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_png_header(const uint8_t* data, size_t len, ck_png_info* info) { return png_host_call(data, len, info, false); }
-int ck_png_probe(const uint8_t* data, size_t len, ck_png_info* info) { return png_host_call(data, len, info, true); }
-
-int ck_png_inflate(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total)
-{
-    if (!data || !total || (!out && cap)) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    try {
-        char msg[CK_PNG_MSG];
-        const int rc = ck_png_unzip(data, len, out, cap, total, msg);
-        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-static int check_png_size(ck_ctx* ctx, int h, int w)
-{
-    if (h <= 0 || w <= 0 || h > CK_PNG_MAX_SIDE || w > CK_PNG_MAX_SIDE || (long long)h * w > CK_PNG_MAX_PIXELS)
-        return ck_fail(ctx, CK_ERR_ARG, "bad PNG frame size %dx%d: 1 .. %d a side and up to 2^28 pixels", w, h, CK_PNG_MAX_SIDE);
-    return CK_OK;
-}
-
-int ck_png_tiles(int32_t* band_rows, int32_t* tile_bytes, int32_t* chunk_bytes, int32_t* group_rows)
-{
-    if (!band_rows || !tile_bytes || !chunk_bytes || !group_rows) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    *band_rows = CK_PNG_BAND_ROWS; *tile_bytes = CK_PNG_TILE_BYTES; *chunk_bytes = CK_PNG_CHUNK; *group_rows = CK_PNG_GROUP_ROWS;
-    return CK_OK;
-}
-
-int ck_png_inflate_geometry(int32_t* window_bits, int32_t* flush_bytes)
-{
-    if (!window_bits || !flush_bytes) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    *window_bits = CK_INF_WINDOW; *flush_bytes = CK_INF_FLUSH;
-    return CK_OK;
-}
-
-int ck_png_inflate_staged(const uint8_t* data, size_t len, uint8_t* out, size_t cap, size_t* total, int h, long long rowbytes,
-                          int32_t* cause, long long* produced)
-{
-    if (!data || !total || (!out && cap)) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer");
-    if (h < 0 || rowbytes < 0 || (h > 0 && rowbytes == 0)) return ck_fail(nullptr, CK_ERR_ARG, "bad rows: %d of 1 + %lld bytes", h, rowbytes);
-    try {
-        char msg[CK_PNG_MSG];
-        CkInfRecord rec;
-        const int rc = ck_png_unzip_staged_rows(data, len, out, cap, total, &rec, msg, h, rowbytes);
-        if (cause) *cause = rec.cause;
-        if (produced) *produced = rec.produced;
-        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_png_set_inflate(ck_ctx* ctx, int mode)
-{
-    CK_API_BEGIN(ctx)
-    if (mode != CK_PNG_INFLATE_HOST && mode != CK_PNG_INFLATE_DEVICE) return ck_fail(ctx, CK_ERR_ARG, "unknown PNG inflate mode %d", mode);
-    ctx->png_inflate = mode;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_png_uploaded_bytes(ck_ctx* ctx, long long* bytes)
-{
-    CK_API_BEGIN(ctx)
-    if (!bytes) return ck_fail(ctx, CK_ERR_ARG, "bytes is NULL");
-    *bytes = ctx->png_uploaded;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_png_inflate_stats(ck_ctx* ctx, long long* stats)
-{
-    CK_API_BEGIN(ctx)
-    if (!stats) return ck_fail(ctx, CK_ERR_ARG, "stats is NULL");
-    for (int k = 0; k < 4; k++) stats[k] = ctx->png_inf_stats[k];
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-static void png_inflate_count(ck_ctx* ctx, const std::vector<CkInfRecord>& recs)
-{
-    for (const CkInfRecord& r : recs) {
-        ctx->png_inf_stats[0] += 1; ctx->png_inf_stats[1] += r.steps; ctx->png_inf_stats[2] += r.tokens; ctx->png_inf_stats[3] += r.produced;
-    }
-}
-
-int ck_png_inflate_device(ck_ctx* ctx, const uint8_t* const* z, const size_t* zlen, int n, uint8_t* out, const size_t* cap, size_t stride,
-                          size_t* total, int32_t* cause, long long* produced)
-{
-    CK_API_BEGIN(ctx)
-    if (!z || !zlen || !out || !cap || !total || !cause || !produced || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    size_t z_bytes = 0, most = 0;
-    for (int f = 0; f < n; f++) {
-        if (!z[f] && zlen[f]) return ck_fail(ctx, CK_ERR_ARG, "stream %d is NULL", f);
-        if (cap[f] > stride) return ck_fail(ctx, CK_ERR_ARG, "stream %d: room for %zu bytes, above the stride of %zu", f, cap[f], stride);
-        z_bytes += up16(zlen[f]);
-        most = cap[f] > most ? cap[f] : most;
-    }
-    const size_t dstride = up16(most), a_z = up16((size_t)n * sizeof(CkInfJob)), a_rec = a_z + z_bytes,
-                 a_out = a_rec + up16((size_t)n * sizeof(CkInfRecord)), all = a_out + (size_t)n * dstride;
-    CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, a_rec > (size_t)n * dstride ? a_rec : (size_t)n * dstride));
-    CK_TRY(ck_ensure(ctx, ctx->png_inf, all));
-    uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
-    CkInfJob* jobs = (CkInfJob*)hp;
-    size_t zat = a_z;
-    for (int f = 0; f < n; f++) {
-        jobs[f].z_off = (int64_t)zat; jobs[f].zlen = (int64_t)zlen[f]; jobs[f].out_off = (int64_t)(a_out + (size_t)f * dstride);
-        jobs[f].cap = (int64_t)cap[f]; jobs[f].need = 0; jobs[f].pitch = 0;
-        if (zlen[f]) memcpy(hp + zat, z[f], zlen[f]);
-        zat += up16(zlen[f]);
-    }
-    uint8_t* dev = (uint8_t*)ctx->png_inf.p;
-    CK_HIP(ctx, hipMemcpyAsync(dev, hp, a_rec, hipMemcpyHostToDevice, ctx->stream));
-    CK_TRY(k_png_inflate(ctx, dev, dev, (const CkInfJob*)dev, (CkInfRecord*)(dev + a_rec), n));
-    std::vector<CkInfRecord> recs((size_t)n);
-    CK_HIP(ctx, hipMemcpyAsync(recs.data(), dev + a_rec, (size_t)n * sizeof(CkInfRecord), hipMemcpyDeviceToHost, ctx->stream));
-    if (dstride) CK_HIP(ctx, hipMemcpyAsync(hp, dev + a_out, (size_t)n * dstride, hipMemcpyDeviceToHost, ctx->stream));
-    CK_TRY(finish(ctx));
-    for (int k = 0; k < 4; k++) ctx->png_inf_stats[k] = 0;
-    png_inflate_count(ctx, recs);
-    for (int f = 0; f < n; f++) {
-        const CkInfRecord& r = recs[(size_t)f];
-        cause[f] = r.cause; produced[f] = r.produced; total[f] = r.cause == CK_INF_OK ? (size_t)r.produced : 0;
-        const size_t have = r.cause != CK_INF_OK ? 0 : (size_t)r.produced < cap[f] ? (size_t)r.produced : cap[f];   // (a refused stream's pending bytes never left the ring)
-        if (have) memcpy(out + (size_t)f * stride, hp + (size_t)f * dstride, have);
-    }
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_png_decode(ck_ctx* ctx, const uint8_t* const* data, const size_t* len, int n, uint8_t* bgr, int out_space, int32_t* bad_frame)
-{
-    if (bad_frame) *bad_frame = -1;
-    CK_API_BEGIN(ctx)
-    if (!data || !len || !bgr || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    std::vector<CkPngHead> heads((size_t)n);
-    std::vector<int> rcs((size_t)n, CK_OK);
-    std::vector<std::string> msgs((size_t)n);
-    auto refused = [&](int f0) {
-        for (size_t f = 0; f < rcs.size(); f++)
-            if (rcs[f] != CK_OK) {
-                if (bad_frame) *bad_frame = f0 + (int)f;
-                (void)hipStreamSynchronize(ctx->stream);
-                return ck_fail(ctx, rcs[f], "frame %d: %s", f0 + (int)f, msgs[f].c_str());
-            }
-        return (int)CK_OK;
-    };
-    ck_parallel_for(n, 16, [&](int f) {
-        char msg[CK_PNG_MSG];
-        rcs[f] = ck_png_walk(data[f], len[f], &heads[f], msg);          // (a NULL stream is refused there)
-        if (rcs[f] != CK_OK) msgs[f] = msg;
-    });
-    CK_TRY(refused(0));
-    const int h = heads[0].h, w = heads[0].w;
-    for (int f = 1; f < n; f++)
-        if (heads[f].h != h || heads[f].w != w) {
-            if (bad_frame) *bad_frame = f;
-            return ck_fail(ctx, CK_ERR_DATA, "frame %d: %dx%d where the batch is %dx%d", f, heads[f].w, heads[f].h, w, h);
-        }
-    const size_t oframe = (size_t)h * w * 3;
-    OutStage<uint8_t> o;
-    CK_TRY(o.open(ctx, bgr, (size_t)n * oframe, out_space, ctx->out_stage));
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    ctx->png_uploaded = 0;
-    if (ctx->png_inflate == CK_PNG_INFLATE_DEVICE) {
-        // per pass: descriptors, palettes, jobs and the zlib streams in one pinned block -> one upload -> the inflate kernel
-        // writes the rows behind them -> the verdict records come down -> the unfilter kernel, unless a frame was refused
-        for (int k = 0; k < 4; k++) ctx->png_inf_stats[k] = 0;
-        for (int f0 = 0; f0 < n;) {
-            int m = 0;
-            size_t rows_bytes = 0, z_bytes = 0;
-            while (f0 + m < n && (m == 0 || rows_bytes + up16(heads[f0 + m].inflated()) <= ((size_t)256 << 20))) {
-                z_bytes += up16(heads[f0 + m].zlen);
-                rows_bytes += up16(heads[f0 + m++].inflated());
-            }
-            const size_t a_pal = up16((size_t)m * sizeof(CkPngDesc)), a_jobs = a_pal + (size_t)m * 768, a_z = a_jobs + up16((size_t)m * sizeof(CkInfJob)),
-                         a_rec = a_z + z_bytes, a_rows = a_rec + up16((size_t)m * sizeof(CkInfRecord)), total = a_rows + rows_bytes;
-            CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, a_rec));     // (the records and the rows exist on the device only)
-            CK_TRY(ck_ensure(ctx, ctx->in_stage, total));
-            uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
-            CkPngDesc* desc = (CkPngDesc*)hp;
-            CkInfJob* jobs = (CkInfJob*)(hp + a_jobs);
-            size_t at = a_rows, zat = a_z;
-            for (int i = 0; i < m; i++) {
-                const CkPngHead& hd = heads[f0 + i];
-                desc[i].off = (int64_t)at; desc[i].rowbytes = hd.rowbytes; desc[i].color_type = hd.color_type; desc[i].depth = hd.bit_depth;
-                desc[i].bpp = hd.bpp; desc[i].palette_n = hd.palette_n;
-                memcpy(hp + a_pal + (size_t)i * 768, hd.palette, 768);
-                jobs[i].z_off = (int64_t)zat; jobs[i].zlen = (int64_t)hd.zlen; jobs[i].out_off = (int64_t)at;
-                jobs[i].cap = jobs[i].need = (int64_t)hd.inflated(); jobs[i].pitch = 1 + hd.rowbytes;
-                if (hd.zlen) memcpy(hp + zat, hd.z, hd.zlen);
-                at += up16(hd.inflated()); zat += up16(hd.zlen);
-            }
-            uint8_t* dev = (uint8_t*)ctx->in_stage.p;
-            CK_HIP(ctx, hipMemcpyAsync(dev, hp, a_rec, hipMemcpyHostToDevice, ctx->stream));
-            ctx->png_uploaded += (long long)a_rec;
-            CK_TRY(k_png_inflate(ctx, dev, dev, (const CkInfJob*)(dev + a_jobs), (CkInfRecord*)(dev + a_rec), m));
-            std::vector<CkInfRecord> recs((size_t)m);
-            CK_HIP(ctx, hipMemcpyAsync(recs.data(), dev + a_rec, (size_t)m * sizeof(CkInfRecord), hipMemcpyDeviceToHost, ctx->stream));
-            CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            png_inflate_count(ctx, recs);
-            for (int i = 0; i < m; i++)
-                if (recs[(size_t)i].cause != CK_INF_OK) {
-                    char msg[CK_PNG_MSG];
-                    ck_png_inflate_message(recs[(size_t)i], heads[f0 + i].h, (long long)heads[f0 + i].rowbytes, msg);
-                    if (bad_frame) *bad_frame = f0 + i;
-                    return ck_fail(ctx, CK_ERR_DATA, "frame %d: %s", f0 + i, msg);
-                }
-            CK_TRY(k_png_unfilter(ctx, dev, (const CkPngDesc*)dev, dev + a_pal, m, h, w, o.dev + (size_t)f0 * oframe));
-            f0 += m;
-            if (f0 < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next pass uploads into the same block
-        }
-        CK_TRY(o.deliver(ctx));
-        return finish(ctx);
-    }
-    // per pass: descriptors, palettes and the inflated rows of its frames in one pinned block -> one upload -> the kernel.
-    // A pass takes frames while their rows stay within 256 MB (one frame at least).
-    for (int f0 = 0; f0 < n;) {
-        int m = 0;
-        size_t rows_bytes = 0;
-        while (f0 + m < n && (m == 0 || rows_bytes + up16(heads[f0 + m].inflated()) <= ((size_t)256 << 20))) rows_bytes += up16(heads[f0 + m++].inflated());
-        const size_t a_pal = up16((size_t)m * sizeof(CkPngDesc)), a_rows = a_pal + (size_t)m * 768, total = a_rows + rows_bytes;
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
-        uint8_t* hp = (uint8_t*)ctx->host_pinned.p;
-        CkPngDesc* desc = (CkPngDesc*)hp;
-        size_t at = a_rows;
-        for (int i = 0; i < m; i++) {
-            const CkPngHead& hd = heads[f0 + i];
-            desc[i].off = (int64_t)at; desc[i].rowbytes = hd.rowbytes; desc[i].color_type = hd.color_type; desc[i].depth = hd.bit_depth;
-            desc[i].bpp = hd.bpp; desc[i].palette_n = hd.palette_n;
-            memcpy(hp + a_pal + (size_t)i * 768, hd.palette, 768);
-            at += up16(hd.inflated());
-        }
-        rcs.assign((size_t)m, CK_OK);
-        msgs.assign((size_t)m, std::string());
-        ck_parallel_for(m, 16, [&](int i) {
-            char msg[CK_PNG_MSG];
-            rcs[i] = ck_png_rows(heads[f0 + i], hp + desc[i].off, msg);
-            if (rcs[i] != CK_OK) msgs[i] = msg;
-        });
-        CK_TRY(refused(f0));
-        const void* d_in;
-        CK_TRY(ck_to_device(ctx, hp, total, CK_HOST, ctx->in_stage, &d_in));
-        ctx->png_uploaded += (long long)total;
-        CK_TRY(k_png_unfilter(ctx, (uint8_t*)ctx->in_stage.p, (const CkPngDesc*)d_in, (const uint8_t*)d_in + a_pal, m, h, w, o.dev + (size_t)f0 * oframe));
-        f0 += m;
-        if (f0 < n) CK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the next pass inflates into the same block
-    }
-    CK_TRY(o.deliver(ctx));
-    return finish(ctx);
-    CK_API_END(ctx)
-}
-
-int ck_png_encode_bound(int h, int w, size_t* bytes)
-{
-    if (!bytes) return ck_fail(nullptr, CK_ERR_ARG, "bytes is NULL");
-    CK_TRY(check_png_size(nullptr, h, w));
-    *bytes = ck_png_bound(h, w);
-    return CK_OK;
-}
-
-int ck_png_encode_staged_mode(const uint8_t* bgr, int n, int h, int w, int filter, int matches, uint8_t* out, size_t stride, size_t* len)
-{
-    if (!bgr || !out || !len || n <= 0) return ck_fail(nullptr, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_png_size(nullptr, h, w));
-    if (filter < -1 || filter > 4) return ck_fail(nullptr, CK_ERR_ARG, "filter %d: 0 .. 4, or -1 to choose per row", filter);
-    if (matches != CK_PNG_MATCH_NONE && matches != CK_PNG_MATCH_RUNS) return ck_fail(nullptr, CK_ERR_ARG, "unknown PNG match mode %d", matches);
-    try {
-        char msg[CK_PNG_MSG];
-        const int rc = ck_png_stage_encode(bgr, n, h, w, filter, out, stride, len, msg, matches == CK_PNG_MATCH_RUNS);
-        return rc == CK_OK ? CK_OK : ck_fail(nullptr, rc, "%s", msg);
-    } catch (const std::exception& e) {
-        return ck_fail(nullptr, CK_ERR_STATE, "C++ exception inside the library: %s", e.what());
-    }
-}
-
-int ck_png_encode_staged(const uint8_t* bgr, int n, int h, int w, int filter, uint8_t* out, size_t stride, size_t* len)
-{
-    return ck_png_encode_staged_mode(bgr, n, h, w, filter, CK_PNG_MATCH_NONE, out, stride, len);
-}
-
-int ck_png_set_encode_matches(ck_ctx* ctx, int mode)
-{
-    CK_API_BEGIN(ctx)
-    if (mode != CK_PNG_MATCH_NONE && mode != CK_PNG_MATCH_RUNS) return ck_fail(ctx, CK_ERR_ARG, "unknown PNG match mode %d", mode);
-    ctx->png_matches = mode;
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-// the histograms the count step of the last pass left in png_work -> png_tokens, two numbers a frame.  known_literals >= 0
-// (the literal-only mode between two passes of one call, where every byte of a frame is one literal token): that number
-// for every frame, nothing is copied
-static int png_read_counts(ck_ctx* ctx, long long known_literals = -1)
-{
-    const int m = ctx->png_count_frames;
-    if (m <= 0) return CK_OK;
-    if (known_literals >= 0 && !ctx->png_count_runs) {
-        for (int f = 0; f < m; f++) { ctx->png_tokens.push_back(known_literals); ctx->png_tokens.push_back(0); }
-        ctx->png_count_frames = 0;
-        return CK_OK;
-    }
-    const size_t pitch = (size_t)ck_png_pitch(ctx->png_count_runs), per = (size_t)ctx->png_count_bands * pitch;
-    std::vector<uint32_t> count((size_t)m * per);
-    CK_HIP(ctx, hipMemcpyAsync(count.data(), (const uint8_t*)ctx->png_work.p + ctx->png_count_at, count.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int f = 0; f < m; f++) {
-        long long lit = 0, match = 0;
-        for (long long band = 0; band < ctx->png_count_bands; band++) {
-            const uint32_t* c = count.data() + (size_t)f * per + (size_t)band * pitch;
-            for (int s = 0; s < 256; s++) lit += c[s];
-            if (ctx->png_count_runs)
-                for (int s = 257; s < CK_PNG_RUN_SYMS; s++) match += c[s];
-        }
-        ctx->png_tokens.push_back(lit);
-        ctx->png_tokens.push_back(match);
-    }
-    ctx->png_count_frames = 0;
-    return CK_OK;
-}
-
-int ck_png_run_stats(ck_ctx* ctx, int n, long long* literals, long long* matches)
-{
-    CK_API_BEGIN(ctx)
-    if (!literals || !matches) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer");
-    CK_TRY(png_read_counts(ctx));
-    if (ctx->png_tokens.empty()) return ck_fail(ctx, CK_ERR_STATE, "no ck_png_encode of this context has completed: there are no tokens to report");
-    if (n <= 0 || (size_t)n * 2 != ctx->png_tokens.size())
-        return ck_fail(ctx, CK_ERR_STATE, "the last ck_png_encode took %zu frames, not %d", ctx->png_tokens.size() / 2, n);
-    for (int f = 0; f < n; f++) { literals[f] = ctx->png_tokens[2 * (size_t)f]; matches[f] = ctx->png_tokens[2 * (size_t)f + 1]; }
-    return CK_OK;
-    CK_API_END(ctx)
-}
-
-int ck_png_encode(ck_ctx* ctx, const uint8_t* bgr, int n, int h, int w, int in_space, int filter, uint8_t* out, size_t stride, size_t* len)
-{
-    CK_API_BEGIN(ctx)
-    if (!bgr || !out || !len || n <= 0) return ck_fail(ctx, CK_ERR_ARG, "NULL pointer or n <= 0");
-    CK_TRY(check_png_size(ctx, h, w));
-    if (filter < -1 || filter > 4) return ck_fail(ctx, CK_ERR_ARG, "filter %d: 0 .. 4, or -1 to choose per row", filter);
-    if (stride < ck_png_bound(h, w))
-        return ck_fail(ctx, CK_ERR_ARG, "output buffer of %zu bytes per frame: smaller than the bound of %zu for a %dx%d frame", stride, ck_png_bound(h, w), w, h);
-    const CkPngGeom g = ck_png_geom(h, w);
-    const size_t iframe = (size_t)h * w * 3;
-    const int runs = ctx->png_matches == CK_PNG_MATCH_RUNS;
-    const size_t PITCH = (size_t)ck_png_pitch(runs);
-    ctx->png_tokens.clear();
-    ctx->png_count_frames = 0;
-    // a pass: frames whose filtered rows stay within 1 GiB (one frame at least)
-    const size_t fit = ((size_t)1 << 30) / (size_t)g.fbytes;
-    const int pass = fit < 1 ? 1 : fit < (size_t)n ? (int)fit : n;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    for (int f0 = 0; f0 < n; f0 += pass) {
-        const int m = n - f0 < pass ? n - f0 : pass;
-        const size_t bands = (size_t)m * g.bands, tiles = (size_t)m * g.tiles;
-        // the histograms of the pass before this one are overwritten now: the runs mode reads them first (a copy and a wait
-        // per further pass of a call above 1 GiB); the literal-only mode copies nothing, its tokens are the frame's bytes
-        CK_TRY(png_read_counts(ctx, (long long)g.fbytes));
-        const void* d_in;
-        CK_TRY(ck_to_device(ctx, bgr + (size_t)f0 * iframe, (size_t)m * iframe, in_space, ctx->in_stage, &d_in));
-        // the work block: 64-bit arrays first, then the 32-bit ones, the 16-bit ones, the bytes
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t a = at; at = up16(at + bytes); return a; };
-        const size_t a_head = take(((size_t)m + 1) * 8), a_tile_off = take(tiles * 8), a_band_off = take(bands * 8), a_frame_bits = take((size_t)m * 8);
-        const size_t a_out_off = take(((size_t)m + 1) * 8), a_count = take(bands * PITCH * 4), a_tile_bits = take(tiles * 4);
-        const size_t a_tile_a = take(tiles * 4), a_tile_b = take(tiles * 4), a_adler = take((size_t)m * 4);
-        const size_t a_band_bits = take(bands * 8), a_band_a = take(bands * 4), a_band_b = take(bands * 4);
-        const size_t a_codes = take(bands * PITCH * 2), a_lens = take(bands * PITCH), a_filt = take((size_t)m * g.fbytes);
-        // (the runs mode's arrays come last: the literal-only mode's block is what it was)
-        const size_t a_before = runs ? take(tiles * 4) : 0, a_after = runs ? take(tiles * 4) : 0, a_edge = runs ? take(tiles * sizeof(CkPngEdge)) : 0;
-        CK_TRY(ck_ensure(ctx, ctx->png_work, at));
-        uint8_t* wp = (uint8_t*)ctx->png_work.p;
-        CkPngWork wk;
-        wk.head = (uint64_t*)(wp + a_head); wk.tile_off = (uint64_t*)(wp + a_tile_off); wk.band_off = (uint64_t*)(wp + a_band_off);
-        wk.frame_bits = (uint64_t*)(wp + a_frame_bits); wk.out_off = (uint64_t*)(wp + a_out_off); wk.count = (uint32_t*)(wp + a_count);
-        wk.tile_bits = (uint32_t*)(wp + a_tile_bits); wk.tile_a = (uint32_t*)(wp + a_tile_a); wk.tile_b = (uint32_t*)(wp + a_tile_b);
-        wk.band_bits = (uint64_t*)(wp + a_band_bits); wk.band_a = (uint32_t*)(wp + a_band_a); wk.band_b = (uint32_t*)(wp + a_band_b);
-        wk.adler = (uint32_t*)(wp + a_adler); wk.codes = (uint16_t*)(wp + a_codes); wk.lens = wp + a_lens; wk.filt = wp + a_filt;
-        wk.before = runs ? (uint32_t*)(wp + a_before) : nullptr; wk.after = runs ? (uint32_t*)(wp + a_after) : nullptr;
-        wk.edge = runs ? (CkPngEdge*)(wp + a_edge) : nullptr;
-        CK_TRY(k_png_enc_measure(ctx, (const uint8_t*)d_in, m, g, filter, wk, runs));
-        ctx->png_count_at = a_count; ctx->png_count_frames = m; ctx->png_count_runs = runs; ctx->png_count_bands = g.bands;
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned2, ((size_t)m + 1) * 8));
-        uint64_t* words = (uint64_t*)ctx->host_pinned2.p;
-        CK_HIP(ctx, hipMemcpyAsync(words, wk.head, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        CK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t total = (size_t)words[0];
-        size_t sum = 0;
-        for (int f = 0; f < m; f++) {
-            if (CK_PNG_CONTAINER + words[1 + f] > stride) return ck_fail(ctx, CK_ERR_STATE, "frame %d: a stream of %llu bytes, above the bound", f0 + f, (unsigned long long)words[1 + f]);
-            sum += up16((size_t)words[1 + f]);
-        }
-        if (sum != total) return ck_fail(ctx, CK_ERR_STATE, "the streams of a pass: %zu bytes where their sizes give %zu", total, sum);
-        CK_TRY(ck_ensure(ctx, ctx->png_pack, total + 16));
-        CK_TRY(k_png_enc_put(ctx, m, g, wk, (uint32_t*)ctx->png_pack.p, total + 16, runs));
-        CK_TRY(ck_ensure_pinned(ctx, ctx->host_pinned, total));
-        CK_HIP(ctx, hipMemcpyAsync(ctx->host_pinned.p, ctx->png_pack.p, total, hipMemcpyDeviceToHost, ctx->stream));
-        CK_TRY(finish(ctx));
-        // the container around every stream -- a copy and a CRC-32 over its bytes -- the frames on the worker threads
-        std::vector<size_t> off((size_t)m + 1, 0);
-        for (int f = 0; f < m; f++) off[(size_t)f + 1] = off[f] + up16((size_t)words[1 + f]);
-        ck_parallel_for(m, 16, [&](int f) {
-            len[f0 + f] = ck_png_wrap((const uint8_t*)ctx->host_pinned.p + off[f], (size_t)words[1 + f], h, w, out + (size_t)(f0 + f) * stride);
-        });
-    }
-    return CK_OK;
     CK_API_END(ctx)
 }
 
@@ -2682,8 +1312,6 @@ int ck_train_handover(ck_ctx* ctx, int handle)
 }
 
 // ---- labelled patches from goban images (k_harvest.hip) ------------------------------------------------------------------
-static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 int ck_harvest_patches(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, const int32_t* fgcount, int fg_space,
                        const int32_t* state_of, const uint8_t* positions, int n_pos, int calm_max, int empty_keep, uint32_t seed,
                        long long first_frame, uint8_t* x, uint8_t* labels, int32_t* src, int cap, int out_space, int32_t* n_found)
@@ -2712,13 +1340,12 @@ int ck_harvest_patches(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, c
         return ck_fail(ctx, CK_ERR_ARG, "x in device memory must be 8-byte aligned, src 4-byte aligned");
     // one scratch block: state_of | positions | codes of the n * 100 candidates | block totals + the grand total
     const int nb = ck_harvest_blocks(n);
-    const size_t at_pos = up16((size_t)n * 4), at_code = at_pos + up16((size_t)n_pos * 361 + 1);
-    const size_t at_blocks = at_code + up16((size_t)n * 400), bytes = at_blocks + up16(((size_t)nb + 1) * 4);
-    CK_TRY(ck_ensure(ctx, ctx->harvest, bytes));
+    const CkHarvestLayout L = ck_harvest_layout(n, n_pos, nb);
+    CK_TRY(ck_ensure(ctx, ctx->harvest, L.total));
     uint8_t* scratch = (uint8_t*)ctx->harvest.p;
-    CK_HIP(ctx, hipMemcpyAsync(scratch, state_of, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    CK_HIP(ctx, hipMemcpyAsync(scratch + L.state, state_of, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (n_pos > 0)
-        CK_HIP(ctx, hipMemcpyAsync(scratch + at_pos, positions, (size_t)n_pos * 361, hipMemcpyHostToDevice, ctx->stream));
+        CK_HIP(ctx, hipMemcpyAsync(scratch + L.pos, positions, (size_t)n_pos * 361, hipMemcpyHostToDevice, ctx->stream));
     const void *d_goban, *d_fg;
     CK_TRY(ck_to_device(ctx, goban, (size_t)n * 380 * 380 * 3, in_space, ctx->in_stage, &d_goban));
     CK_TRY(ck_to_device(ctx, fgcount, (size_t)n * 361 * sizeof(int32_t), fg_space, ctx->in_stage2, &d_fg));
@@ -2729,9 +1356,9 @@ int ck_harvest_patches(ck_ctx* ctx, const uint8_t* goban, int n, int in_space, c
         CK_TRY(ol.open(ctx, labels, (size_t)cap, out_space, ctx->lblbuf));
         CK_TRY(os.open(ctx, src, (size_t)cap * 2 * sizeof(int32_t), out_space, ctx->harvest_src));
     }
-    int32_t* d_blocks = (int32_t*)(scratch + at_blocks);
-    CK_TRY(k_harvest(ctx, (const uint8_t*)d_goban, (const int32_t*)d_fg, (const int32_t*)scratch, scratch + at_pos, n, calm_max,
-                     empty_keep, seed, (uint32_t)(unsigned long long)first_frame, (int32_t*)(scratch + at_code), d_blocks,
+    int32_t* d_blocks = (int32_t*)(scratch + L.blocks);
+    CK_TRY(k_harvest(ctx, (const uint8_t*)d_goban, (const int32_t*)d_fg, (const int32_t*)(scratch + L.state), scratch + L.pos, n, calm_max,
+                     empty_keep, seed, (uint32_t)(unsigned long long)first_frame, (int32_t*)(scratch + L.code), d_blocks,
                      ox.dev, ol.dev, os.dev, cap));
     int32_t total = 0;
     CK_HIP(ctx, hipMemcpyAsync(&total, d_blocks + nb, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));

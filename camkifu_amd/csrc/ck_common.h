@@ -375,18 +375,11 @@ int k_jpeg_enc_stuff(ck_ctx* ctx, int m, const CkEncGeom& g, const CkEncWork& w,
 // unfiltered in place and expanded to BGR; palettes: 768 bytes an image.
 constexpr int CK_PNG_CHUNK = 24;           // bytes a lane handles per step: whole pixels at every depth (1 .. 64 bits a pixel)
 constexpr int CK_PNG_GROUP_ROWS = 256;     // rows in flight: the lanes of the workgroup
-struct CkPngDesc {
-    int64_t off, rowbytes;
-    int32_t color_type, depth, bpp, palette_n;
-};
-static_assert(sizeof(CkPngDesc) == 32, "a descriptor row is 32 bytes");
 int k_png_unfilter(ck_ctx* ctx, uint8_t* d_rows, const CkPngDesc* d_desc, const uint8_t* d_palettes, int n, int h, int w, uint8_t* d_bgr);
 // The device inflate (k_png_inflate.hip): a wave per zlib stream.  Stream i lies at d_z + z_off; its first `cap` bytes go to
 // d_out + out_off (a multiple of 16); pitch > 0: it holds rows of `pitch` bytes, `need` bytes of them, whose filter bytes
 // are checked.  One verdict record (ck_png_inflate_stage.h) a stream.
-struct CkInfJob {
-    int64_t z_off, zlen, out_off, cap, need, pitch;
-};
+struct CkInfJob;                  // (ck_png_inflate_stage.h, with the verdict record)
 struct CkInfRecord;
 int k_png_inflate(ck_ctx* ctx, const uint8_t* d_z, uint8_t* d_out, const CkInfJob* d_jobs, CkInfRecord* d_rec, int n);
 // Writing, m frames: where the arrays of a pass lie in HBM -- per band (count, lens, codes: ck_png_pitch(runs) each; band_off),

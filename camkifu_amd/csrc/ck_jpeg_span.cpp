@@ -1,5 +1,5 @@
 // ck_jpeg_span.cpp -- the steps of ck_jpeg_span.h on the host, in the order and on the staged layout the GPU runs them
-// (jpeg_huff_pass in ck_api.hip, k_jpeg_span.hip): one loop where the device has one launch.  Plain C++: no HIP, no context;
+// (jpeg_huff_pass in ck_api_jpeg.hip, k_jpeg_span.hip): one loop where the device has one launch.  Plain C++: no HIP, no context;
 // tools/sanitize/jpeg_span_fuzz.cpp links it with ck_jpeg.cpp and ck_jpeg_plan.cpp on its own.
 #include "ck_jpeg_span.h"
 #include "ck_jpeg_tables.h"

@@ -95,6 +95,10 @@ struct CkInfRecord {
     int64_t steps, tokens;                                   // window steps; literals and matches applied
 };
 static_assert(sizeof(CkInfRecord) == 40, "a verdict record is 40 bytes");
+// what k_png_inflate is told of a stream (ck_common.h): offsets into the staged block, in bytes
+struct CkInfJob {
+    int64_t z_off, zlen, out_off, cap, need, pitch;
+};
 
 struct CkInfIn {
     const uint8_t* z;

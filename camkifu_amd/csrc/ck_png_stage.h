@@ -102,6 +102,13 @@ CK_HD inline int ck_png_tile_len(const CkPngGeom& g, int64_t band, int64_t t)
     return left <= 0 ? 0 : left < CK_PNG_TILE_BYTES ? (int)left : CK_PNG_TILE_BYTES;
 }
 
+// reading (k_png_unfilter): where the inflated rows of an image lie in the staged block, and how to expand them
+struct CkPngDesc {
+    int64_t off, rowbytes;
+    int32_t color_type, depth, bpp, palette_n;
+};
+static_assert(sizeof(CkPngDesc) == 32, "a descriptor row is 32 bytes");
+
 // ---- filter ----
 // (a frame holds B, G, R; the PNG holds R, G, B: byte i of a row is channel 2 - i % 3 of pixel i / 3)
 CK_HD inline int ck_png_paeth(int a, int b, int c)

@@ -1,4 +1,4 @@
-"""The argument contract of the C ABI (camkifu_amd/csrc/ck_api.hip): one case per distinct refusal that an entry point
+"""The argument contract of the C ABI (camkifu_amd/csrc/ck_api.hip, ck_api_jpeg.hip, ck_api_png.hip): one case per distinct refusal that an entry point
 makes before it launches anything -- the error number and a fragment of the message ck_last_error gives.  The calls go
 through ctypes directly, past the checks of capi.Context.  Every pointer that is not NULL points at a buffer large
 enough for the shapes used (2 frames of 8 x 8), so no case hands a kernel a bad pointer even if a check were lost; an
